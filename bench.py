@@ -9,6 +9,7 @@ PFB+FFT+DDC -> IQ low-pass/2 + phase (materialised, fp32) -> matched filter + ba
 Prints ONE JSON line on rank 0.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,3,5}] [--baseline {ema,svf}]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
 Without an external launcher (no WORLD_SIZE in the environment), `--gpus N > 1` starts N fresh
@@ -16,6 +17,17 @@ rank processes itself (`launch_ranks`: child processes, never an exec; the paren
 and relays rank 0's line — one feedline per GPU, as the reference runs one ROACH per feedline into
 one PacketMaster (PacketMaster.c:216-218, 577-625). Under an external launcher WORLD_SIZE must
 equal --gpus.
+
+A plain run does only what the headline figure needs: set-up (feedline, synthetic input, loop
+calibration and thresholds), W warm-up steps, K timed steps, the result line (`value`,
+`ms_per_step`, the front end's HIP-event roofline share and the warm-up's per-kernel breakdown).
+`--full` adds everything else, after the timed steps: the detector score of the last step's
+packets, the measured stream-copy roof, the CPU baseline legs and the full-size parity witness
+(N = 1) or every rank's parity witness (N > 1).
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller as DIR/<name>.npy
+(`dump_outputs`); the inputs are seeded, so two builds run with the same arguments can be compared
+array for array.
 
 Configs (BASELINE.json `configs`; the default is configs[2], the one the
 metric is quoted on):
@@ -57,12 +69,18 @@ CONFIGS = {
 def parse():
     p = argparse.ArgumentParser()
     p.add_argument('--gpus', type=int, default=1)
-    p.add_argument('--steps', type=int, default=10)
+    p.add_argument('--steps', type=int, default=10, help='timed steps (>= 1)')
     # the first launches of a fresh process run slower while the clock ramps (rocprofv3 traces,
     # profiles/r04/r04_v_*: config 3 k_front3 4.99, 4.65, 4.33, 4.30 ms then ~4.25; config 5 6.69 ->
     # 5.45 over six launches): ten untimed steps reach the steady state of a continuous stream
     p.add_argument('--warmup', type=int, default=10)
     p.add_argument('--config', type=int, default=3, choices=sorted(CONFIGS))
+    p.add_argument('--full', action='store_true',
+                   help='after the timed steps also run what the headline figure does not need: detector '
+                        'score, stream-copy roof, CPU baseline legs, parity witness(es)')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='after the timed steps write the last step\'s outputs (phase sample, packets, '
+                        'counts, config-5 heights) of rank 0 as DIR/<name>.npy')
     p.add_argument('--baseline', default='ema', choices=['ema', 'svf'])
     p.add_argument('--rearm-q8', type=int, default=None,
                    help='trigger re-arm hysteresis /256 (mkid_set_rearm); default 96 for svf (removes the '
@@ -97,7 +115,12 @@ def parse():
                    help='skip the parity witness: the one-core CPU sample (the first 2^cpu-samples-log2 '
                         'samples of the step input) re-run on the GPU from a reset context and compared '
                         'with the oracle outputs the CPU leg computes anyway')
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error('--steps must be at least 1')
+    if args.warmup < 0:
+        p.error('--warmup must not be negative')
+    return args
 
 
 def setup_feedline(C, fs, seed, atten_span=20.0, ratio_min=0.1):
@@ -538,7 +561,9 @@ def main():
     counts = d_counts.cpu().numpy()
     ev_last = int(counts[0])
     det = None
-    if rank == 0:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, phase, d_events, counts, heights)
+    if rank == 0 and args.full:
         det = detector_score(d_events[:int(counts[1])].cpu().numpy().view(np.uint64),
                              (args.warmup + args.steps - 1) * J, ps, pt, N,
                              atten=feed['attens'], loop_R=feed['loop_R'])
@@ -549,7 +574,7 @@ def main():
     # the oracle in a CPU child pinned to a CPU of its own; rank 0 reports all ranks. Outside the
     # timed region; the CPU throughput legs stay at N = 1.
     parity_ranks = None
-    if world > 1 and not args.no_witness:
+    if args.full and world > 1 and not args.no_witness:
         n_w = min(1 << args.witness_samples_log2, S)
         wit_r = witness_device(ch, x, n_w, C, N, dev, heights is not None)
         par_r = cpu_baseline(x, C, feed, lpf, mf, thr, n_w, n_w, base_mode, wit_r, witness_only=True,
@@ -561,27 +586,11 @@ def main():
     if rank == 0:
         # measured HBM roof in the same run: stream copy of copy_mib MiB (the library's float4
         # copy, HIP-event timed on the context stream) and torch's copy_ (torch events); the
-        # faster of the two is the measured roof
-        nb = args.copy_mib << 20
-        src = torch.empty(nb // 4, dtype=torch.int32, device=dev).fill_(1)
-        dst = torch.empty_like(src)
-        torch.cuda.synchronize(dev)
-        ch.set_timing(True)
-        for _ in range(6):
-            ch.stream_copy(dst, src, nb)
-        ct = ch.timing()['k_stream_copy']
-        ch.set_timing(False)
-        lib_copy = 2.0 * nb / (ct[0] / ct[1] * 1e-3) / 1e9
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        dst.copy_(src)
-        e0.record()
-        for _ in range(6):
-            dst.copy_(src)
-        e1.record()
-        torch.cuda.synchronize(dev)
-        torch_copy = 2.0 * nb * 6 / (e0.elapsed_time(e1) * 1e-3) / 1e9
-        copy_gbps = max(lib_copy, torch_copy)
-        del src, dst
+        # faster of the two is the measured roof (--full; a plain run quotes the spec roof alone)
+        lib_copy = torch_copy = copy_gbps = None
+        if args.full:
+            lib_copy, torch_copy = copy_probe(ch, args.copy_mib << 20, dev)
+            copy_gbps = max(lib_copy, torch_copy)
 
         total = S * args.steps * world
         value = total / dt / 1e6
@@ -665,13 +674,14 @@ def main():
                          'overhead_bytes_per_sample': overhead.get(dom, 0.0),
                          'alg_bytes_per_launch': a_bytes, 'avg_launch_ms': round(kt[dom], 4),
                          'avg_launch_ms_rocprof': prof_ms,
-                         'stream_copy_GBps': round(copy_gbps, 1),
+                         'stream_copy_GBps': round(copy_gbps, 1) if copy_gbps else None,
                          'stream_copy_detail': {'mkid_stream_copy': round(lib_copy, 1),
-                                                'torch_copy_': round(torch_copy, 1), 'MiB': args.copy_mib},
-                         'frac_vs_measured': round(achieved / copy_gbps, 4) if copy_gbps > 0 else None,
+                                                'torch_copy_': round(torch_copy, 1),
+                                                'MiB': args.copy_mib} if copy_gbps else None,
+                         'frac_vs_measured': round(achieved / copy_gbps, 4) if copy_gbps else None,
                          'chain_alg_GBps': round(chain_gbps, 1),
                          'chain_frac': round(chain_gbps / HBM_PEAK_GBPS, 4),
-                         'chain_frac_vs_measured': round(chain_gbps / copy_gbps, 4) if copy_gbps > 0 else None,
+                         'chain_frac_vs_measured': round(chain_gbps / copy_gbps, 4) if copy_gbps else None,
                          'compute_tflops_est': round(flops_per_sample * total / dt / 1e12, 2),
                          'compute_peak_tflops': FP32_PEAK_TFLOPS},
             'kernel_ms': {k: round(v, 4) for k, v in kall.items()},
@@ -682,7 +692,7 @@ def main():
         if parity_ranks is not None:
             out['parity_ranks'] = parity_ranks
             out['parity_ranks_green'] = all(p.get('green') for p in parity_ranks)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             n1 = min(1 << args.cpu_samples_log2, S)
             wit = None
             if not args.no_witness:
@@ -696,6 +706,74 @@ def main():
     ch.close()
     if grouped:
         dist.destroy_process_group()
+
+
+def copy_probe(ch, nb, dev):
+    """Measured HBM roof (--full): stream copy of nb bytes by the library's float4 copy (HIP-event
+    timed on the context stream) and by torch's copy_ (torch events). Returns both in GB/s."""
+    import torch
+    src = torch.empty(nb // 4, dtype=torch.int32, device=dev).fill_(1)
+    dst = torch.empty_like(src)
+    torch.cuda.synchronize(dev)
+    ch.set_timing(True)
+    for _ in range(6):
+        ch.stream_copy(dst, src, nb)
+    ct = ch.timing()['k_stream_copy']
+    ch.set_timing(False)
+    lib_copy = 2.0 * nb / (ct[0] / ct[1] * 1e-3) / 1e9
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    dst.copy_(src)
+    e0.record()
+    for _ in range(6):
+        dst.copy_(src)
+    e1.record()
+    torch.cuda.synchronize(dev)
+    torch_copy = 2.0 * nb * 6 / (e0.elapsed_time(e1) * 1e-3) / 1e9
+    return lib_copy, torch_copy
+
+
+DUMP_PHASE_EDGE = 1 << 18       # phase values kept from each end of the step's stream
+DUMP_PHASE_RANDOM = 1 << 21     # seeded positions in between
+DUMP_SEED = 20240229
+
+
+def dump_outputs(path, phase, d_events, counts, heights):
+    """--dump-outputs: what the last timed step handed back, as float32 / float64 .npy files
+    (under 64 MB in all):
+      counts.npy              float64 [2]: packets produced, packets written (the step's count words)
+      packets.npy             float64 [n][4]: channel, peak, base, time stamp of every written packet
+                              (the 12 + 12 + 12 + 28 bit fields of the 64-bit word, each exact in
+                              float64), sorted by the packet word: the compaction's order within a
+                              step is not defined
+      heights.npy             float32 [n] (config 5): the pulse height of each packet, same order
+      phase.npy               float32: the whole phase stream [J][C] flattened if it has at most
+                              2^22 values, else its values at
+      phase_index.npy         float64: fixed positions, the first and last 2^18 of the stream and
+                              2^21 seeded ones in between (written in both cases)"""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    c = np.asarray(counts, np.int64)
+    n = int(c[1])
+    np.save(os.path.join(path, 'counts.npy'), c.astype(np.float64))
+    w = d_events[:n].cpu().numpy().view(np.uint64)
+    o = np.argsort(w, kind='stable')
+    w = w[o]
+    f = [(w >> np.uint64(52)) & np.uint64(0xFFF), (w >> np.uint64(40)) & np.uint64(0xFFF),
+         (w >> np.uint64(28)) & np.uint64(0xFFF), w & np.uint64((1 << 28) - 1)]
+    np.save(os.path.join(path, 'packets.npy'), np.stack(f, axis=1).astype(np.float64))
+    if heights is not None:
+        np.save(os.path.join(path, 'heights.npy'), heights[:n].cpu().numpy()[o].astype(np.float32))
+    if phase is not None:
+        total = phase.numel()
+        if total <= (1 << 22):
+            idx = np.arange(total, dtype=np.int64)
+        else:
+            rng = np.random.default_rng(DUMP_SEED)
+            idx = np.unique(np.concatenate([np.arange(DUMP_PHASE_EDGE), total - 1 - np.arange(DUMP_PHASE_EDGE),
+                                            rng.integers(0, total, DUMP_PHASE_RANDOM)]).astype(np.int64))
+        vals = phase[torch.from_numpy(idx).to(phase.device)].cpu().numpy()
+        np.save(os.path.join(path, 'phase.npy'), vals.astype(np.float32))
+        np.save(os.path.join(path, 'phase_index.npy'), idx.astype(np.float64))
 
 
 def witness_device(ch, x, n, C, N, dev, with_heights):

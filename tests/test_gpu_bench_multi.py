@@ -31,7 +31,7 @@ def test_bench_two_ranks_gloo_gather(gpu):
            '--master-addr', '127.0.0.1', '--master-port', str(_free_port()),
            os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--backend', 'gloo', '--check-gather',
            '--config', '3', '--log2-samples', '26', '--steps', '3', '--warmup', '1',
-           '--no-cpu-baseline', '--copy-mib', '256']
+           '--full', '--no-cpu-baseline', '--copy-mib', '256']
     env = dict(os.environ, MASTER_ADDR='127.0.0.1')
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -66,7 +66,7 @@ def test_bench_gpus2_self_launch(gpu):
     """The driver's command line: `bench.py --gpus 2`, no wrapper; backend auto (one GPU for two
     ranks -> gloo)."""
     out = _run_bench(['--gpus', '2', '--check-gather', '--config', '3', '--log2-samples', '26',
-                      '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--copy-mib', '256'])
+                      '--steps', '3', '--warmup', '1', '--full', '--no-cpu-baseline', '--copy-mib', '256'])
     assert out['n_gpus'] == 2
     g = out['gather']
     assert g['backend'] == 'gloo' and g['ranks'] == 2
@@ -80,7 +80,7 @@ def test_bench_gpus8_rehearsal(gpu):
     rank 0 (the reference's 8 boards into one PacketMaster, PacketMaster.c:216-220, 589), and every
     rank's parity witness (its own feedline's first 2^24 samples against the oracle, item 3)."""
     out = _run_bench(['--gpus', '8', '--backend', 'gloo', '--check-gather', '--config', '3',
-                      '--log2-samples', '24', '--steps', '3', '--warmup', '1', '--no-cpu-baseline',
+                      '--log2-samples', '24', '--steps', '3', '--warmup', '1', '--full', '--no-cpu-baseline',
                       '--copy-mib', '256'], timeout=280)
     assert out['n_gpus'] == 8
     g = out['gather']
@@ -99,7 +99,7 @@ def test_bench_rccl_gather_world1(gpu):
     timing, all in a world-size-1 group."""
     out = _run_bench(['--gpus', '1', '--force-gather', '--backend', 'nccl', '--check-gather',
                       '--config', '3', '--log2-samples', '26', '--steps', '4', '--warmup', '1',
-                      '--no-cpu-baseline', '--copy-mib', '256'])
+                      '--full', '--no-cpu-baseline', '--copy-mib', '256'])
     assert out['n_gpus'] == 1
     g = out['gather']
     assert g['backend'] == 'nccl' and g['ranks'] == 1
