@@ -294,6 +294,47 @@ int mkid_pulse_heights_counted(mkid_ctx* ctx, const float* d_phase, int64_t rows
                                const uint64_t* d_events, const int64_t* d_count, int64_t cap,
                                float* d_heights);
 
+/* Pulse capture: the firmware-style capture block between the stream and the template analysis.
+ * For every photon packet the phase window around its stamp is copied into a caller-owned,
+ * per-channel record bank on the device, for all channels at once and across streamed calls (the
+ * scale-up of contsnapshot's one-channel host cut, ROACH_Pulses.py:557-762; window saving of
+ * pulse_triggering_v2.py:104-174). A channel's records [P][length] then feed mkid_make_template.
+ * mkid_set_capture: 1 <= length <= 4096 rows per record, 0 <= pre < length rows before the stamp,
+ * max_per_ch >= 1 records per channel (R); it (re)allocates the context's capture state and starts
+ * a new stream segment.
+ * mkid_capture_pulses: d_phase [rows][C] are global phase rows j0 .. j0 + rows - 1 (as for
+ * mkid_pulse_heights), d_events the n wide packets of that call (channel-major, time-ascending in
+ * a channel, each passed exactly once, with the call that produced it). Bank: d_records
+ * [C][R][length] float32, d_stamps [C][R] int64, d_info [C][2] int32 {ready, dropped}; the caller
+ * zeroes d_info to start a bank, and a bank with ready > 0 is continued.
+ *   - A stream segment is a run of calls whose j0 each equal the previous j0 + rows, covering rows
+ *     [j_first, j_end). A call that does not continue the previous one starts a new segment (the
+ *     carried rows and pending packets are forgotten, the bank keeps what it has), as do
+ *     mkid_reset_stream and mkid_set_capture.
+ *   - Stamps are unwrapped as for mkid_pulse_heights: base = max(j0 - 2^27, 0),
+ *     jg = base + ((ts - base) mod 2^28).
+ *   - A packet of channel c < C is eligible when s = jg - pre >= j_first (and >= j0 - the rows
+ *     carried, max(length - 1, pre + 1): true of any stamp >= j0 - 1); channels >= C are ignored.
+ *   - It completes in the call where s + length <= j_end first holds; until then it waits in a
+ *     device-side pending list, so a window may span any number of calls. Windows still open when
+ *     the stream ends are not recorded.
+ *   - Completions of a channel are in stamp order. The first R are recorded: d_records[c][k][:] =
+ *     phase[s : s + length, c], bit-identical, d_stamps[c][k] = jg, ready = records held. Later
+ *     ones only add to dropped, as do packets beyond the pending list's room of
+ *     (length - pre) / max(cfg.dead_time, 1) + 2 per channel, which the device trigger's own
+ *     packets never exceed.
+ *   - Any chunking of a segment, 1-row calls included, gives the result of one call over it.
+ * rows == 0 and n == 0 are valid. Device pointers only; asynchronous on the context stream; the
+ * counted form reads min(*d_count, cap) packets (d_count = &d_counts[1] of the process call: no
+ * host round trip). MKID_E_STATE before mkid_set_capture. Timed as MKID_K_CAPTURE. */
+int mkid_set_capture(mkid_ctx* ctx, int32_t length, int32_t pre, int32_t max_per_ch);
+int mkid_capture_pulses(mkid_ctx* ctx, const float* d_phase, int64_t rows, int64_t j0,
+                        const uint64_t* d_events, int64_t n, float* d_records, int64_t* d_stamps,
+                        int32_t* d_info);
+int mkid_capture_pulses_counted(mkid_ctx* ctx, const float* d_phase, int64_t rows, int64_t j0,
+                                const uint64_t* d_events, const int64_t* d_count, int64_t cap,
+                                float* d_records, int64_t* d_stamps, int32_t* d_info);
+
 /* Kernel timing with HIP events on the context stream (for bench roofline numbers). */
 #define MKID_K_CHANNELIZE 0
 #define MKID_K_FIR_PHASE 1
@@ -302,7 +343,8 @@ int mkid_pulse_heights_counted(mkid_ctx* ctx, const float* d_phase, int64_t rows
 #define MKID_K_FRONT 4        /* fused K1-K6 (replaces CHANNELIZE + FIR_PHASE when used) */
 #define MKID_K_COPY 5         /* mkid_stream_copy (measured HBM roof)                     */
 #define MKID_K_HEIGHTS 6      /* mkid_pulse_heights                                       */
-#define MKID_K_COUNT 7
+#define MKID_K_CAPTURE 7      /* mkid_capture_pulses                                      */
+#define MKID_K_COUNT 8
 /* mkid_set_timing: enable 0 off, any other value times every kernel (the round-1..3 meaning).
  * mkid_set_timing_mask: an OR of MKID_TIMING_ONLY(k) times only those kernels (0 = off). Each timed
  * launch records two events on the stream, and an event record costs a few microseconds of

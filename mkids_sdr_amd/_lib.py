@@ -19,7 +19,7 @@ MKID_E_OVERFLOW = -4
 MKID_E_NODEV = -5
 
 BASE_NONE, BASE_EMA, BASE_SVF = 0, 1, 2
-K_CHANNELIZE, K_FIR_PHASE, K_TRIGGER, K_COMPACT, K_FRONT, K_COPY, K_HEIGHTS, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7
+K_CHANNELIZE, K_FIR_PHASE, K_TRIGGER, K_COMPACT, K_FRONT, K_COPY, K_HEIGHTS, K_CAPTURE, K_COUNT = range(9)
 FRONT_AUTO, FRONT_SPLIT = 0, 1
 
 PKT_CH_SHIFT, PKT_PEAK_SHIFT, PKT_BASE_SHIFT = 52, 40, 28
@@ -106,6 +106,9 @@ _SIGS = {
     'mkid_set_pulse_filter': [P, P, I32, I32, I32],
     'mkid_pulse_heights': [P, P, I64, I64, P, I64, P],
     'mkid_pulse_heights_counted': [P, P, I64, I64, P, P, I64, P],
+    'mkid_set_capture': [P, I32, I32, I32],
+    'mkid_capture_pulses': [P, P, I64, I64, P, I64, P, P, P],
+    'mkid_capture_pulses_counted': [P, P, I64, I64, P, P, I64, P, P, P],
     'mkid_stream_copy': [P, P, P, I64],
     'mkid_synth_adc': [P, P, I64, I64, P, P, P, I64, ctypes.c_float, ctypes.c_float, I32,
                        ctypes.c_float, ctypes.c_uint32],

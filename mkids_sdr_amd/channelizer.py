@@ -251,6 +251,52 @@ class Channelizer:
         torch.cuda.synchronize(dev)
         return out.cpu().numpy()
 
+    # ---- pulse capture: phase windows around the packets, into a per-channel record bank -----------
+    def set_capture(self, length=2000, pre=1000, max_per_ch=256):
+        """Records of `length` phase rows starting `pre` rows before each packet's stamp, at most
+        `max_per_ch` per channel (mkid_set_capture; the defaults are the reference's
+        [bob-500, bob+1500) RawPulse length, centred). Starts a new stream segment."""
+        self._chk(self._L.mkid_set_capture(self._h, int(length), int(pre), int(max_per_ch)))
+        self._capture = (int(length), int(pre), int(max_per_ch))
+
+    def capture_bank(self):
+        """A fresh bank on this context's GPU: (records [C][R][L] float32, stamps [C][R] int64,
+        info [C][2] int32 {ready, dropped}, zeroed)."""
+        import torch
+        if getattr(self, '_capture', None) is None:
+            raise _lib.MkidError(_lib.MKID_E_STATE, 'capture_bank: set_capture first')
+        L, _, R = self._capture
+        dev = self.torch_device()
+        return (torch.zeros((self.C, R, L), dtype=torch.float32, device=dev),
+                torch.zeros((self.C, R), dtype=torch.int64, device=dev),
+                torch.zeros((self.C, 2), dtype=torch.int32, device=dev))
+
+    def capture_pulses_device(self, d_phase, rows, j0, d_events, n, d_records, d_stamps, d_info):
+        """Device pointers; asynchronous on the context stream (include/mkidgpu.h)."""
+        self._chk(self._L.mkid_capture_pulses(self._h, _ptr(d_phase), int(rows), int(j0), _ptr(d_events), int(n),
+                                              _ptr(d_records), _ptr(d_stamps), _ptr(d_info)))
+
+    def capture_pulses_counted(self, d_phase, rows, j0, d_events, d_count, cap, d_records, d_stamps, d_info):
+        """As capture_pulses_device with the packet count read on the device (d_count: an int64
+        device pointer/tensor, e.g. the d_counts[1:] of the process call)."""
+        self._chk(self._L.mkid_capture_pulses_counted(self._h, _ptr(d_phase), int(rows), int(j0), _ptr(d_events),
+                                                      _ptr(d_count), int(cap), _ptr(d_records), _ptr(d_stamps),
+                                                      _ptr(d_info)))
+
+    def capture_pulses(self, phase, events, j0=0, bank=None):
+        """Host convenience: phase float32 [rows][C] (rad) of global rows j0.., events uint64 [n]
+        (channel-major, time-ascending) -> the bank (device tensors; a new one when not given)."""
+        import torch
+        dev = self.torch_device()
+        ph = torch.from_numpy(np.ascontiguousarray(phase, np.float32).reshape(-1, self.C)).to(dev)
+        ev = torch.from_numpy(np.ascontiguousarray(events, np.uint64).view(np.int64)).to(dev)
+        if bank is None:
+            bank = self.capture_bank()
+        torch.cuda.synchronize(dev)  # the uploads run on torch's stream, the kernels on the context's
+        self.capture_pulses_device(ph, ph.shape[0], j0, ev, ev.numel(), *bank)
+        torch.cuda.synchronize(dev)
+        return bank
+
     # ---- timing ------------------------------------------------------------------------------
     def set_timing(self, on, kernels=None):
         """on: time every kernel (HIP events); kernels: names (e.g. ['k_front']) to time only

@@ -122,6 +122,14 @@ struct mkid_ctx {
     float *d_phist = nullptr, *d_phist_tmp = nullptr;  // [h_ncoeff][C] last phase rows seen by pulse_heights
     int64_t phist_end = -1, phist_rows = 0;          // global row after its last row; valid rows
     int64_t iq_rows = 0;
+    // pulse capture (mkid_set_capture): carried phase rows and the double-buffered pending list
+    int32_t cap_L = 0, cap_pre = 0, cap_R = 0, cap_PC = 0;   // cap_L = 0: not configured
+    int64_t cap_H = 0;                                         // rows carried: max(L - 1, pre + 1)
+    float *d_chist = nullptr, *d_chist_tmp = nullptr;         // [cap_H][C], the valid rows are the last chist_rows
+    int64_t *d_cpend[2] = {nullptr, nullptr};                 // [C][cap_PC] unwrapped stamps
+    int32_t *d_cpend_n[2] = {nullptr, nullptr}, *d_cwork = nullptr;   // [C]; [C][2]
+    int cpend_cur = 0;
+    int64_t cap_end = -1, chist_rows = 0;                     // j0 + rows of the last call (-1: no segment)
     // host copies behind the folded LO table (d_lo = conj(LUT)/2^15 with the (-1)^(b (k+1))
     // bin-parity sign of K4 folded in: P is even, so the sign depends on k mod P only)
     std::vector<float2> h_lo;      // [P][C]
@@ -209,7 +217,9 @@ static void free_all(mkid_ctx* c) {
                     c->d_rtmp,  c->d_tstate, c->d_zb[0], c->d_zb[1], c->d_raw, c->d_filt, c->d_ysum, c->d_slots,
                     c->d_chcounts, c->d_scan, c->d_counts, c->d_in,  c->d_phase_ws, c->d_ev_ws,
                     c->d_sspec, c->d_send,  c->d_scratch, c->d_reruns, c->d_rflags, c->d_rmeans, c->d_iqtap, c->d_hcoeff,
-                    c->d_phist, c->d_phist_tmp, c->d_slot_ch, c->d_refix, c->d_refix_pk};
+                    c->d_phist, c->d_phist_tmp, c->d_slot_ch, c->d_refix, c->d_refix_pk,
+                    c->d_chist, c->d_chist_tmp, c->d_cpend[0], c->d_cpend[1], c->d_cpend_n[0], c->d_cpend_n[1],
+                    c->d_cwork};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (auto& kt : c->pending) {
@@ -690,6 +700,8 @@ int mkid_reset_stream(mkid_ctx* c) {
     c->last_raw_row = 0;
     c->phist_end = -1;     // pulse-height phase history: a reset starts a new stream
     c->phist_rows = 0;
+    c->cap_end = -1;       // pulse capture: the next call starts a segment (rows and pending list forgotten)
+    c->chist_rows = 0;
     return MKID_OK;
 }
 
@@ -1222,6 +1234,97 @@ int mkid_pulse_heights_counted(mkid_ctx* c, const float* d_phase, int64_t rows, 
     return pulse_heights(c, d_phase, rows, j0, d_events, d_count, cap, d_heights);
 }
 
+static void capture_free(mkid_ctx* c) {
+    void** ps[] = {(void**)&c->d_chist, (void**)&c->d_chist_tmp, (void**)&c->d_cpend[0], (void**)&c->d_cpend[1],
+                   (void**)&c->d_cpend_n[0], (void**)&c->d_cpend_n[1], (void**)&c->d_cwork};
+    for (void** p : ps) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+    }
+    c->cap_L = 0;   // not configured: a failed mkid_set_capture leaves nothing half-allocated behind
+}
+
+int mkid_set_capture(mkid_ctx* c, int32_t length, int32_t pre, int32_t max_per_ch) {
+    if (!c) return MKID_E_ARG;
+    if (length < 1 || length > 4096 || pre < 0 || pre >= length || max_per_ch < 1)
+        FAIL(c, MKID_E_ARG, "capture: need 1 <= length <= 4096, 0 <= pre < length, max_per_ch >= 1");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    capture_free(c);
+    const int64_t H = std::max<int64_t>(length - 1, pre + 1);
+    // windows still open after a call have stamps in (j_end - (length - pre), j_end): packets at
+    // least max(dead_time, 1) rows apart (trig_common.h) never outnumber this
+    const int32_t PC = (length - pre) / std::max(c->cfg.dead_time, 1) + 2;
+    const size_t C = (size_t)c->C;
+    hipError_t e = dalloc(&c->d_chist, C * H);
+    if (e == hipSuccess) e = dalloc(&c->d_chist_tmp, C * H);
+    for (int b = 0; b < 2 && e == hipSuccess; ++b) {
+        e = dalloc(&c->d_cpend[b], C * PC);
+        if (e == hipSuccess) e = dalloc(&c->d_cpend_n[b], C);
+    }
+    if (e == hipSuccess) e = dalloc(&c->d_cwork, 2 * C);
+    if (e != hipSuccess) {   // free what was allocated, so that a later mkid_set_capture starts over
+        capture_free(c);
+        c->err = std::string("capture: hipMalloc: ") + hipGetErrorString(e);
+        return MKID_E_HIP;
+    }
+    c->cap_L = length; c->cap_pre = pre; c->cap_R = max_per_ch; c->cap_PC = PC; c->cap_H = H;
+    c->cpend_cur = 0;
+    c->cap_end = -1;
+    c->chist_rows = 0;
+    return MKID_OK;
+}
+
+static int capture_pulses(mkid_ctx* c, const float* d_phase, int64_t rows, int64_t j0, const uint64_t* d_events,
+                          const int64_t* d_n, int64_t n, float* d_records, int64_t* d_stamps, int32_t* d_info) {
+    if (!c || (rows > 0 && !d_phase) || (n > 0 && !d_events) || !d_records || !d_stamps || !d_info)
+        return MKID_E_ARG;
+    if (rows < 0 || j0 < 0 || n < 0) FAIL(c, MKID_E_ARG, "capture: negative rows/j0/n");
+    if (c->cap_L <= 0) FAIL(c, MKID_E_STATE, "capture: not configured (mkid_set_capture)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int cur = c->cpend_cur;
+    if (c->cap_end != j0) {   // a new segment: no carried rows, no pending packets
+        c->chist_rows = 0;
+        c->cap_end = -1;      // until this call's launches are in, no segment stands
+        HIPCHK(c, hipMemsetAsync(c->d_cpend_n[cur], 0, (size_t)c->C * 4, c->stream));
+    }
+    const int64_t hrows = c->chist_rows, H = c->cap_H;
+    CaptureArgs a{d_phase, c->d_chist + (H - hrows) * c->C, d_events, d_n, d_records, d_stamps, d_info,
+                  c->d_cpend[cur], c->d_cpend_n[cur], c->d_cpend[cur ^ 1], c->d_cpend_n[cur ^ 1], c->d_cwork,
+                  rows, j0, n, hrows, c->C, c->cap_L, c->cap_pre, c->cap_R, c->cap_PC, 0};
+    KTime kt;
+    tstart(c, MKID_K_CAPTURE, &kt, c->stream);
+    hipError_t e = launch_capture(a, c->stream);
+    tstop(c, &kt, c->stream);
+    if (e == hipSuccess && rows > 0)   // keep the last H rows of (carried rows, these rows)
+        e = launch_hist_roll(c->d_chist_tmp, c->d_chist, d_phase, H, rows, (int64_t)c->C * 4, c->stream);
+    if (e != hipSuccess) {   // partly enqueued: the segment ends here
+        c->cap_end = -1;
+        c->chist_rows = 0;
+        c->err = std::string("capture launch: ") + hipGetErrorString(e);
+        return MKID_E_HIP;
+    }
+    if (rows > 0) {
+        std::swap(c->d_chist, c->d_chist_tmp);
+        c->chist_rows = std::min<int64_t>(H, hrows + rows);
+    }
+    c->cpend_cur = cur ^ 1;
+    c->cap_end = j0 + rows;
+    return MKID_OK;
+}
+
+int mkid_capture_pulses(mkid_ctx* c, const float* d_phase, int64_t rows, int64_t j0, const uint64_t* d_events,
+                        int64_t n, float* d_records, int64_t* d_stamps, int32_t* d_info) {
+    return capture_pulses(c, d_phase, rows, j0, d_events, nullptr, n, d_records, d_stamps, d_info);
+}
+
+int mkid_capture_pulses_counted(mkid_ctx* c, const float* d_phase, int64_t rows, int64_t j0,
+                                const uint64_t* d_events, const int64_t* d_count, int64_t cap, float* d_records,
+                                int64_t* d_stamps, int32_t* d_info) {
+    if (!d_count) return MKID_E_ARG;
+    return capture_pulses(c, d_phase, rows, j0, d_events, d_count, cap, d_records, d_stamps, d_info);
+}
+
 int mkid_stream_copy(mkid_ctx* c, void* d_dst, const void* d_src, int64_t bytes) {
     if (!c || !d_dst || !d_src || bytes < 0) return MKID_E_ARG;
     if (bytes % 16 != 0 || ((uintptr_t)d_dst & 15) != 0 || ((uintptr_t)d_src & 15) != 0)
@@ -1260,7 +1363,7 @@ int mkid_get_timing(mkid_ctx* c, int32_t k, double* total_ms, int64_t* launches)
 
 const char* mkid_kernel_name(int32_t k) {
     static const char* names[MKID_K_COUNT] = {"k_channelize", "k_lpf_phase", "k_trigger", "k_compact",
-                                              "k_front",      "k_stream_copy", "k_pulse_heights"};
+                                              "k_front",      "k_stream_copy", "k_pulse_heights", "k_capture"};
     return (k >= 0 && k < MKID_K_COUNT) ? names[k] : "?";
 }
 

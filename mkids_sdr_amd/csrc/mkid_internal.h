@@ -167,7 +167,26 @@ struct HeightArgs {
     int32_t pad;
 };
 
+// Pulse capture (k_capture.hip; the contract is in its header comment)
+struct CaptureArgs {
+    const float* phase;      // [rows][C] rad, global phase rows j0 .. j0 + rows - 1
+    const float* hist;       // [hrows][C] carried rows j0 - hrows .. j0 - 1 (hrows = 0: none)
+    const uint64_t* events;  // [n] wide packets, channel-major, time-ascending within a channel
+    const int64_t* d_n;      // nullable: device packet count (min(*d_n, n) packets are read)
+    float* records;          // [C][R][L] caller's bank
+    int64_t* stamps;         // [C][R] unwrapped stamp of each record
+    int32_t* info;           // [C][2] {ready, dropped}
+    const int64_t* pend_in;  // [C][PC] unwrapped stamps of the windows still open, per channel
+    const int32_t* pend_n_in;  // [C]
+    int64_t* pend_out;       // the list after this call (the other half of the double buffer)
+    int32_t* pend_n_out;
+    int32_t* work;           // [C][2] this call's records of a channel: {first slot, count}
+    int64_t rows, j0, n, hrows;
+    int32_t C, L, pre, R, PC, pad;
+};
+
 // launchers (return hipError_t of the launch)
+hipError_t launch_capture(const CaptureArgs& a, hipStream_t s);
 hipError_t launch_pulse_heights(const HeightArgs& a, hipStream_t s);
 hipError_t launch_channelize(int N, const ChanArgs& a, hipStream_t s);
 hipError_t launch_lpf_phase(const LpfArgs& a, hipStream_t s);

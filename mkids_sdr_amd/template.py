@@ -57,6 +57,55 @@ def optimal_filter(ch, template, noise, pre=100, ncoeff=100):
     return out.cpu().numpy()
 
 
+def iq_from_phase(records, sign=-1.0):
+    """Phase records (rad, e.g. one channel of a capture bank) -> unit-circle pulse records
+    I = cos(sign phi), Q = sin(sign phi), float32, which `make_template` takes with centre (0, 0).
+    sign = -1: phase pulses are negative-going at the trigger and MakeTemplate wants positive peaks."""
+    ph = np.float32(sign) * np.asarray(records, np.float32)
+    return np.cos(ph), np.sin(ph)
+
+
+def filters_from_bank(ch, bank, ncoeff=100, pre=100, min_records=20, fallback=None, keep_templates=False):
+    """Per-channel optimal filters from a capture bank (Channelizer.capture_bank, records of 2000
+    rows): every channel with at least `min_records` ready records goes iq_from_phase ->
+    make_template -> optimal_filter (one pair of launches per channel) and fills its row of coeff
+    [C][ncoeff] float32, ready for Channelizer.set_pulse_filter (the weights start 10 rows before
+    the template peak). A channel with fewer records, or on which make_template raises (no
+    surviving pulse), takes its row from `fallback` ([C][ncoeff] or [ncoeff]; default zeros).
+    Returns dict(coeff, count [C] float64, flag [C] int32, pstart [C] int32, ready [C] int32,
+    used [C] bool); flag and pstart are -1 where the fallback was taken. keep_templates adds
+    templates {channel: (template [2000], noise [800])}."""
+    records, _, info = bank
+    C = records.shape[0]
+    if records.shape[2] != NPTS:
+        raise ValueError('filters_from_bank needs records of %d rows (set_capture(length=%d))' % (NPTS, NPTS))
+    ready = info.cpu().numpy()[:, 0].astype(np.int32)
+    coeff = np.zeros((C, ncoeff), np.float32)
+    if fallback is not None:
+        coeff[:] = np.asarray(fallback, np.float32)
+    count = np.zeros(C, np.float64)
+    flag = np.full(C, -1, np.int32)
+    pstart = np.full(C, -1, np.int32)
+    used = np.zeros(C, bool)
+    templates = {}
+    for c in np.flatnonzero(ready >= max(int(min_records), 1)):
+        I, Q = iq_from_phase(records[c, :ready[c]].cpu().numpy())
+        try:
+            r = make_template(ch, I, Q)
+        except _lib.MkidError as e:
+            if e.code != _lib.MKID_E_STATE:
+                raise
+            continue
+        coeff[c] = optimal_filter(ch, r['d_template'], r['d_noise'], pre=pre, ncoeff=ncoeff)
+        count[c], flag[c], pstart[c], used[c] = r['count'], r['flag'], r['pstart'], True
+        if keep_templates:
+            templates[int(c)] = (r['template'], r['noise'])
+    out = dict(coeff=coeff, count=count, flag=flag, pstart=pstart, ready=ready, used=used)
+    if keep_templates:
+        out['templates'] = templates
+    return out
+
+
 def matched_fir_taps(coeff, ntaps=26, sign=-1.0):
     """Firmware FIR taps from correlation weights: the ntaps-long window of largest energy,
     reversed into convolution order (f_j = sum_i a_i raw_{j-i}), scaled to max |a| = 2047/2048
