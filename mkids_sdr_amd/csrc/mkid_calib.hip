@@ -1,0 +1,249 @@
+// C ABI of libmkidgpu.so (include/mkidgpu.h): calibration and pulse analysis — replay trigger,
+// template, optimal filter, pulse heights, pulse capture, the synthetic ADC stream, stream copy.
+// Every entry point that replaces buffers of the context allocates the new ones into locals and
+// moves them in, with the scalars that describe them, only once every allocation has succeeded.
+#include "mkid_ctx.h"
+
+using namespace mkid;
+
+extern "C" {
+
+int mkid_replay_trigger(mkid_ctx* c, const int16_t* d_raw, int64_t n, int64_t ld, int32_t nch,
+                        const mkid_replay_cfg* rc, int32_t* d_hits, int32_t cap, int32_t* d_counts) {
+    if (!c || !d_raw || !rc || !d_counts || (cap > 0 && !d_hits)) return MKID_E_ARG;
+    if (n <= 0 || nch <= 0 || ld < nch || cap < 0) FAIL(c, MKID_E_ARG, "replay: bad shape");
+    if (rc->mode != MKID_REPLAY_ROLLING && rc->mode != MKID_REPLAY_BLOCK) FAIL(c, MKID_E_ARG, "replay: bad mode");
+    if (rc->length <= 0 || rc->start < 0 || rc->need < 0 || rc->skip <= 0)
+        FAIL(c, MKID_E_ARG, "replay: length/start/need/skip out of range");
+    if (rc->mode == MKID_REPLAY_ROLLING && rc->start < rc->length)
+        FAIL(c, MKID_E_ARG, "replay: rolling start must be >= meanlength");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nf = (size_t)nch * (size_t)((n + 31) / 32);
+    const size_t nm = rc->mode == MKID_REPLAY_BLOCK ? (size_t)nch * (size_t)(n / rc->length) : 0;
+    if (nf > c->rflags_n || nm > c->rmeans_n) {   // grow the workspace
+        DevBuf<uint32_t> fl;
+        DevBuf<double> mn;
+        if (nf > c->rflags_n) HIPCHK(c, fl.alloc(nf));
+        if (nm > c->rmeans_n) HIPCHK(c, mn.alloc(nm));
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // an earlier replay may still read the old ones
+        if (fl.get()) c->d_rflags = std::move(fl), c->rflags_n = nf;
+        if (mn.get()) c->d_rmeans = std::move(mn), c->rmeans_n = nm;
+    }
+    HIPCHK(c, launch_replay(d_raw, n, ld, nch, rc->mode, rc->length, rc->start, rc->need, rc->skip,
+                            rc->wrap_negative, rc->threshold_deg, c->d_rflags.get(), c->d_rmeans.get(), d_hits, cap,
+                            d_counts, c->stream));
+    return MKID_OK;
+}
+
+int mkid_make_template(mkid_ctx* c, const float* d_I, const float* d_Q, int64_t P, double* d_template,
+                       double* d_noise, mkid_template_info* info) {
+    if (!c || !d_I || !d_Q || !d_template || !d_noise || !info) return MKID_E_ARG;
+    if (P <= 0) FAIL(c, MKID_E_ARG, "make_template: need pulses");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t N = 2000, NN = 800;
+    DevBuf<float> I, Q, refmed;
+    DevBuf<double> rows, nrows, peaks, scratch, tP, stats;
+    DevBuf<int32_t> accept, appended;
+    HIPCHK(c, I.alloc((size_t)P * N));
+    HIPCHK(c, Q.alloc((size_t)P * N));
+    HIPCHK(c, rows.alloc((size_t)P * N));
+    HIPCHK(c, nrows.alloc((size_t)P * NN));
+    HIPCHK(c, peaks.alloc((size_t)P));
+    HIPCHK(c, scratch.alloc((size_t)2 * P + 8));
+    HIPCHK(c, tP.alloc(N));
+    HIPCHK(c, stats.alloc(8));
+    HIPCHK(c, refmed.alloc(2));
+    HIPCHK(c, accept.alloc((size_t)P));
+    HIPCHK(c, appended.alloc((size_t)P));
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipMemcpyAsync(I.get(), d_I, (size_t)P * N * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(Q.get(), d_Q, (size_t)P * N * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(c, hipMemsetAsync(appended.get(), 0, (size_t)P * 4, s));
+    HIPCHK(c, hipMemsetAsync(stats.get(), 0, 64, s));
+    hipError_t e = launch_make_template(I.get(), Q.get(), P, rows.get(), nrows.get(), accept.get(), peaks.get(),
+                                        appended.get(), scratch.get(), tP.get(), d_template, d_noise, stats.get(),
+                                        refmed.get(), s);
+    if (e == hipErrorInvalidValue) FAIL(c, MKID_E_STATE, "make_template: no pulse passed the first pass");
+    HIPCHK(c, e);
+    double st[5];
+    std::vector<double> t(N);
+    HIPCHK(c, hipMemcpyAsync(st, stats.get(), 40, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(t.data(), d_template, N * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    info->pm = st[0];
+    info->pdev = st[1];
+    info->count1 = st[3];
+    info->count = st[4];
+    info->flag = (st[4] < 500 || st[0] < 10 || st[0] > 150) ? 1 : 0;
+    int ps = 0;
+    for (size_t i = 1; i < N; ++i)
+        if (t[i] > t[ps]) ps = (int)i;
+    info->pstart = ps;
+    return MKID_OK;
+}
+
+int mkid_optimal_filter(mkid_ctx* c, const double* d_template, const double* d_noise, int32_t pre, int32_t ncoeff,
+                        double* d_coeff) {
+    if (!c || !d_template || !d_noise || !d_coeff) return MKID_E_ARG;
+    if (pre < 10 || pre > 2000 || ncoeff <= 0 || ncoeff > 800) FAIL(c, MKID_E_ARG, "optimal_filter: bad pre/ncoeff");
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf<double> work;
+    HIPCHK(c, work.alloc(3 * 800));
+    HIPCHK(c, launch_optimal_filter(d_template, d_noise, pre, ncoeff, d_coeff, work.get(), c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MKID_OK;
+}
+
+int mkid_set_pulse_filter(mkid_ctx* c, const float* coeff, int32_t nch, int32_t ncoeff, int32_t pre) {
+    if (!c || !coeff) return MKID_E_ARG;
+    if (nch != c->C) FAIL(c, MKID_E_ARG, "pulse filter: need one filter per channel");
+    if (ncoeff < 1 || ncoeff > 4096 || pre < 0) FAIL(c, MKID_E_ARG, "pulse filter: bad ncoeff/pre");
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf<float> co;
+    RollBuf<float> hist;
+    HIPCHK(c, co.alloc((size_t)nch * ncoeff));
+    HIPCHK(c, hist.alloc(ncoeff, (int64_t)nch * 4));
+    // the upload drains the stream: no kernel still reads the filter and the rows replaced below
+    if (int r = upload(c, co.get(), coeff, (size_t)nch * ncoeff * 4)) return r;
+    c->d_hcoeff = std::move(co);
+    c->phist = std::move(hist);
+    c->pcarry = plan::Carry{ncoeff};   // the rows carried for the old filter are forgotten
+    c->h_ncoeff = ncoeff;
+    c->h_pre = pre;
+    return MKID_OK;
+}
+
+static int pulse_heights(mkid_ctx* c, const float* d_phase, int64_t rows, int64_t j0, const uint64_t* d_events,
+                         const int64_t* d_n, int64_t n, float* d_heights) {
+    if (!c || (n > 0 && (!d_phase || !d_events || !d_heights))) return MKID_E_ARG;
+    if (rows < 0 || j0 < 0 || n < 0) FAIL(c, MKID_E_ARG, "pulse heights: negative rows/j0/n");
+    if (!c->d_hcoeff.get()) FAIL(c, MKID_E_STATE, "pulse heights: no filter set (mkid_set_pulse_filter)");
+    HIPCHK(c, hipSetDevice(c->device));
+    // the carried rows precede this call's rows only if the calls are contiguous in j
+    const plan::Carry& k = c->pcarry;
+    HeightArgs a{d_phase, d_events, c->d_hcoeff.get(), d_heights, rows, j0, n, c->C, c->h_ncoeff, c->h_pre, d_n,
+                 c->phist.get() + k.offset(j0) * c->C, k.before(j0), c->ncu, 0};
+    KTime kt;
+    tstart(c, MKID_K_HEIGHTS, &kt, c->stream);
+    HIPCHK(c, launch_pulse_heights(a, c->stream));
+    tstop(c, &kt, c->stream);
+    // keep the last h_ncoeff rows of (history, these rows) for the next call's early windows
+    if (rows > 0) {
+        HIPCHK(c, c->phist.roll(d_phase, rows, c->stream));
+        c->pcarry.advance(j0, rows);
+    }
+    return MKID_OK;
+}
+
+int mkid_pulse_heights(mkid_ctx* c, const float* d_phase, int64_t rows, int64_t j0, const uint64_t* d_events,
+                       int64_t n, float* d_heights) {
+    return pulse_heights(c, d_phase, rows, j0, d_events, nullptr, n, d_heights);
+}
+
+int mkid_pulse_heights_counted(mkid_ctx* c, const float* d_phase, int64_t rows, int64_t j0,
+                               const uint64_t* d_events, const int64_t* d_count, int64_t cap, float* d_heights) {
+    if (!d_count) return MKID_E_ARG;
+    return pulse_heights(c, d_phase, rows, j0, d_events, d_count, cap, d_heights);
+}
+
+int mkid_set_capture(mkid_ctx* c, int32_t length, int32_t pre, int32_t max_per_ch) {
+    if (!c) return MKID_E_ARG;
+    if (length < 1 || length > 4096 || pre < 0 || pre >= length || max_per_ch < 1)
+        FAIL(c, MKID_E_ARG, "capture: need 1 <= length <= 4096, 0 <= pre < length, max_per_ch >= 1");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t H = std::max<int64_t>(length - 1, pre + 1);   // rows carried
+    // windows still open after a call have stamps in (j_end - (length - pre), j_end): packets at
+    // least max(dead_time, 1) rows apart (trig_common.h) never outnumber this
+    const int32_t PC = (length - pre) / std::max(c->cfg.dead_time, 1) + 2;
+    const size_t C = (size_t)c->C;
+    RollBuf<float> hist;
+    DevBuf<int64_t> pend[2];
+    DevBuf<int32_t> pend_n[2], work;
+    hipError_t e = hist.alloc(H, (int64_t)C * 4);
+    for (int b = 0; b < 2 && e == hipSuccess; ++b) {
+        e = pend[b].alloc(C * PC);
+        if (e == hipSuccess) e = pend_n[b].alloc(C);
+    }
+    if (e == hipSuccess) e = work.alloc(2 * C);
+    if (e != hipSuccess) {   // the context keeps the capture it had (or none)
+        c->err = std::string("capture: hipMalloc: ") + hipGetErrorString(e);
+        return MKID_E_HIP;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // an earlier capture may still read the old buffers
+    c->chist = std::move(hist);
+    for (int b = 0; b < 2; ++b) c->d_cpend[b] = std::move(pend[b]), c->d_cpend_n[b] = std::move(pend_n[b]);
+    c->d_cwork = std::move(work);
+    c->cap_L = length; c->cap_pre = pre; c->cap_R = max_per_ch; c->cap_PC = PC;
+    c->cpend_cur = 0;
+    c->ccarry = plan::Carry{H};   // no segment
+    return MKID_OK;
+}
+
+static int capture_pulses(mkid_ctx* c, const float* d_phase, int64_t rows, int64_t j0, const uint64_t* d_events,
+                          const int64_t* d_n, int64_t n, float* d_records, int64_t* d_stamps, int32_t* d_info) {
+    if (!c || (rows > 0 && !d_phase) || (n > 0 && !d_events) || !d_records || !d_stamps || !d_info)
+        return MKID_E_ARG;
+    if (rows < 0 || j0 < 0 || n < 0) FAIL(c, MKID_E_ARG, "capture: negative rows/j0/n");
+    if (c->cap_L <= 0) FAIL(c, MKID_E_STATE, "capture: not configured (mkid_set_capture)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int cur = c->cpend_cur;
+    plan::Carry& k = c->ccarry;
+    if (k.end != j0) {   // a new segment: no carried rows, no pending packets
+        k.drop();        // until this call's launches are in, no segment stands
+        HIPCHK(c, hipMemsetAsync(c->d_cpend_n[cur].get(), 0, (size_t)c->C * 4, c->stream));
+    }
+    CaptureArgs a{d_phase, c->chist.get() + k.offset(j0) * c->C, d_events, d_n, d_records, d_stamps, d_info,
+                  c->d_cpend[cur].get(), c->d_cpend_n[cur].get(), c->d_cpend[cur ^ 1].get(),
+                  c->d_cpend_n[cur ^ 1].get(), c->d_cwork.get(),
+                  rows, j0, n, k.before(j0), c->C, c->cap_L, c->cap_pre, c->cap_R, c->cap_PC, 0};
+    KTime kt;
+    tstart(c, MKID_K_CAPTURE, &kt, c->stream);
+    hipError_t e = launch_capture(a, c->stream);
+    tstop(c, &kt, c->stream);
+    if (e == hipSuccess && rows > 0)   // keep the last rows of (carried rows, these rows)
+        e = c->chist.roll(d_phase, rows, c->stream);
+    if (e != hipSuccess) {   // partly enqueued: the segment ends here
+        k.drop();
+        c->err = std::string("capture launch: ") + hipGetErrorString(e);
+        return MKID_E_HIP;
+    }
+    c->cpend_cur = cur ^ 1;
+    k.advance(j0, rows);
+    return MKID_OK;
+}
+
+int mkid_capture_pulses(mkid_ctx* c, const float* d_phase, int64_t rows, int64_t j0, const uint64_t* d_events,
+                        int64_t n, float* d_records, int64_t* d_stamps, int32_t* d_info) {
+    return capture_pulses(c, d_phase, rows, j0, d_events, nullptr, n, d_records, d_stamps, d_info);
+}
+
+int mkid_capture_pulses_counted(mkid_ctx* c, const float* d_phase, int64_t rows, int64_t j0,
+                                const uint64_t* d_events, const int64_t* d_count, int64_t cap, float* d_records,
+                                int64_t* d_stamps, int32_t* d_info) {
+    if (!d_count) return MKID_E_ARG;
+    return capture_pulses(c, d_phase, rows, j0, d_events, d_count, cap, d_records, d_stamps, d_info);
+}
+
+int mkid_stream_copy(mkid_ctx* c, void* d_dst, const void* d_src, int64_t bytes) {
+    if (!c || !d_dst || !d_src || bytes < 0) return MKID_E_ARG;
+    if (bytes % 16 != 0 || ((uintptr_t)d_dst & 15) != 0 || ((uintptr_t)d_src & 15) != 0)
+        FAIL(c, MKID_E_ARG, "stream copy: 16-byte aligned pointers and sizes only");
+    HIPCHK(c, hipSetDevice(c->device));
+    KTime kt;
+    tstart(c, MKID_K_COPY, &kt, c->stream);
+    HIPCHK(c, launch_stream_copy(d_dst, d_src, bytes, c->stream));
+    tstop(c, &kt, c->stream);
+    return MKID_OK;
+}
+int mkid_synth_adc(mkid_ctx* c, int16_t* d_out, int64_t n, int64_t n0, const int16_t* d_base,
+                   const mkid_synth_tone* d_tones, const mkid_pulse* d_pulses, int64_t npulses, float tr,
+                   float tf, int32_t window, float sigma, uint32_t seed) {
+    if (!c || !d_out || !d_base || n < 0 || (npulses > 0 && (!d_pulses || !d_tones))) return MKID_E_ARG;
+    if (tr <= 0.f || tf <= 0.f || window < 0) FAIL(c, MKID_E_ARG, "bad pulse shape");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_synth(d_out, n, n0, d_base, d_tones, d_pulses, npulses, tr, tf, window, sigma, seed,
+                           c->stream));
+    return MKID_OK;
+}
+
+}  // extern "C"

@@ -190,7 +190,6 @@ hipError_t launch_capture(const CaptureArgs& a, hipStream_t s);
 hipError_t launch_pulse_heights(const HeightArgs& a, hipStream_t s);
 hipError_t launch_channelize(int N, const ChanArgs& a, hipStream_t s);
 hipError_t launch_lpf_phase(const LpfArgs& a, hipStream_t s);
-hipError_t launch_front(int N, const FrontArgs& a, hipStream_t s);
 hipError_t launch_trigger(const TrigSpecArgs& a, hipStream_t s);
 // resident wave slots of the speculative trigger kernel on a device (occupancy x CUs)
 int64_t trigger_wave_slots(int device);

@@ -64,6 +64,7 @@ const char* size_workspace(const mkid_cfg& cfg, bool fused, int64_t trig_slots, 
 SubPlan plan_sub(const Workspace& ws, int C, int mode, int dead, int64_t J) {
     SubPlan p;
     p.J = J;
+    p.seg_off = 0;
     if (mode == MKID_BASE_SVF) {
         // svf_lanes segments over all channels (the per-lane walk is latency bound), each
         // >= kSvfLmin rows; short sub-chunks run as one exact segment
@@ -101,6 +102,7 @@ const char* plan_call(const Workspace& ws, int C, int N, int mode, int dead, int
     if (n <= 0 || n % N != 0 || n > ws.max_chunk) return "call size outside the workspace";
     for (int64_t off = 0; off < n; off += ws.G) {
         subs.push_back(plan_sub(ws, C, mode, dead, std::min<int64_t>(ws.G, n - off) / N));
+        subs.back().seg_off = stride;
         stride += subs.back().nseg;
         capseg = std::max(capseg, subs.back().capseg);
         if (subs.back().nseg > ws.nseg_max) return "trigger plan exceeds the segment tables";

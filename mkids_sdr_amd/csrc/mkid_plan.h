@@ -2,10 +2,12 @@
 // AddressSanitizer / UndefinedBehaviorSanitizer (make -C mkids_sdr_amd/csrc asan; tools/plan_fuzz.cpp):
 // workspace sizing at context creation, the per-call trigger segmentation and its slot-table
 // geometry, the k_front3 select-slot order, the K1 tap quantisation, the merge of per-chunk packet
-// lists and the reference packet re-encode. mkid_api.hip is the only product caller.
+// lists, the reference packet re-encode and the validity bookkeeping of a carried history. The host
+// files mkid_api.hip, mkid_stream.hip and mkid_calib.hip are the only product callers.
 #pragma once
 #include <stdint.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "mkidgpu.h"
@@ -62,10 +64,10 @@ const char* size_workspace(const mkid_cfg& cfg, bool fused, int64_t trig_slots, 
                            int64_t svf_w, Workspace& ws);
 
 // Trigger geometry of one sub-chunk of J phase rows: segment length L, warm-up W, nseg segments and
-// the per-segment packet capacity.
+// the per-segment packet capacity; seg_off (plan_call): its first segment in the call's slot table.
 struct SubPlan {
     int64_t J;
-    int32_t L, W, nseg, capseg;
+    int32_t L, W, nseg, capseg, seg_off;
 };
 SubPlan plan_sub(const Workspace& ws, int C, int mode, int dead, int64_t J);
 // The sub-chunk plans of a call of n samples (n a positive multiple of N, n <= max_chunk) and the
@@ -73,6 +75,16 @@ SubPlan plan_sub(const Workspace& ws, int C, int mode, int dead, int64_t J);
 // capacity. Returns nullptr, or the error text when the plan exceeds the workspace.
 const char* plan_call(const Workspace& ws, int C, int N, int mode, int dead, int64_t n,
                       std::vector<SubPlan>& subs, int32_t& stride, int32_t& capseg);
+
+// Which rows of a history buffer of H rows are valid: the last `rows`, and they precede a call that
+// starts at global row j0 only if they end there (pulse heights and capture, mkid_calib.hip).
+struct Carry {
+    int64_t H = 0, end = -1, rows = 0;   // end: global row after the last carried one (-1: none)
+    int64_t before(int64_t j0) const { return end == j0 ? rows : 0; }
+    int64_t offset(int64_t j0) const { return H - before(j0); }   // first valid row of the buffer
+    void advance(int64_t j0, int64_t n) { rows = std::min(H, before(j0) + n), end = j0 + n; }   // n rows rolled in
+    void drop() { end = -1, rows = 0; }
+};
 
 // k_front3 select-slot order (mkid_api.hip / include/mkidgpu.h mkid_slot_order): out[slot] = channel
 void slot_order(const std::vector<int32_t>& bins, int C, std::vector<int16_t>& out);

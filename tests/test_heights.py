@@ -128,7 +128,8 @@ def test_heights_history_across_calls(gpu):
     the context's carried copy of the previous call's last rows, so every packet of the second
     call whose window ends inside the stream equals the oracle on the concatenated phase. The
     first call's packets whose windows ran past its last row come back NaN; passed again with the
-    second call (include/mkidgpu.h: deferral) they get their heights too."""
+    second call (include/mkidgpu.h: deferral) they get their heights too. A third and a fourth call
+    follow mkid_set_pulse_filter with a filter of another length, which forgets the carried rows."""
     import torch
     from mkids_sdr_amd.channelizer import Channelizer
     C, S, pre, nco = 1024, 2 ** 20, 20, 100
@@ -168,9 +169,38 @@ def test_heights_history_across_calls(gpu):
                 deferred = ev[tail]
             else:
                 h_def, ev_def = h[:nd], ev[:nd]
+        # the same stream goes on under a filter of another length
+        nco2 = 37
+        coeff2 = np.random.default_rng(67).normal(size=(C, nco2)).astype(np.float32)
+        ch.set_pulse_filter(coeff2, pre=pre)
+        x2 = torch.from_numpy(_noise_iq(2 * S, 68)).cuda()
+        for k in (2, 3):
+            d_ph = torch.empty((J, C), dtype=torch.float32, device='cuda')
+            d_ev = torch.empty(J * C, dtype=torch.int64, device='cuda')
+            d_cnt = torch.zeros(2, dtype=torch.int64, device='cuda')
+            ch.process_device(x2[(k - 2) * S:(k - 1) * S], S, d_ph, d_ev, J * C, d_cnt)
+            torch.cuda.synchronize()
+            n = int(d_cnt[1].item())
+            d_h = torch.empty(max(n, 1), dtype=torch.float32, device='cuda')
+            ch.pulse_heights_device(d_ph, J, k * J, d_ev, n, d_h)
+            torch.cuda.synchronize()
+            phases.append(d_ph.cpu().numpy())
+            evs.append(d_ev[:n].cpu().numpy().view(np.uint64))
+            hs.append(d_h[:n].cpu().numpy())
     finally:
         ch.close()
-    phase = np.concatenate(phases)
+    # the filter change forgot the carried rows: the third call's windows that start before its first
+    # row come back NaN, the fourth call's early windows equal the oracle on calls 3 and 4 concatenated
+    ts3 = (evs[2] & np.uint64(oh.TS_MASK)).astype(np.int64)
+    before3 = ts3 - pre < 2 * J
+    assert before3.sum() > 5
+    assert np.array_equal(np.isnan(hs[2]), before3 | (ts3 - pre + nco2 > 3 * J))
+    ts4 = (evs[3] & np.uint64(oh.TS_MASK)).astype(np.int64)
+    early4 = (ts4 - pre >= 3 * J - nco2) & (ts4 - pre < 3 * J)
+    assert early4.sum() > 5
+    assert np.all(np.isfinite(hs[3][early4]))
+    _check(np.concatenate(phases[2:]), evs[3], coeff2.astype(np.float64), pre, 2 * J, hs[3])
+    phase = np.concatenate(phases[:2])
     ev2 = evs[1]
     ts = (ev2 & np.uint64(oh.TS_MASK)).astype(np.int64)
     early = (ts - pre >= J - nco) & (ts - pre < J)      # windows reaching into the first call

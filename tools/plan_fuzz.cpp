@@ -95,6 +95,7 @@ static void fuzz_plans(int iters) {
             if (pe) continue;
             int64_t Jsum = 0, segs = 0;
             for (const SubPlan& sp : subs) {
+                CHECK(sp.seg_off == segs, "seg_off %d of %lld", sp.seg_off, (long long)segs);
                 Jsum += sp.J;
                 segs += sp.nseg;
                 CHECK(sp.J >= 1 && sp.J <= ws.Jmax, "sub-chunk rows %lld", (long long)sp.J);
@@ -113,17 +114,15 @@ static void fuzz_plans(int iters) {
             if (ws.slot_cap <= (int64_t)1 << 22 && (int64_t)C * ws.scratch_cap <= (int64_t)1 << 22) {
                 std::vector<uint8_t> slots((size_t)ws.slot_cap), scratch((size_t)(C * ws.scratch_cap));
                 const int64_t ch[] = {0, C - 1, rint_(0, C - 1)};
-                int32_t seg_off = 0;
                 for (const SubPlan& sp : subs) {
                     for (int64_t c : ch)
                         for (int32_t s = 0; s < sp.nseg; s += std::max<int32_t>(1, sp.nseg - 1)) {
-                            const int64_t base = (c * stride + seg_off + s) * (int64_t)capseg;
+                            const int64_t base = (c * stride + sp.seg_off + s) * (int64_t)capseg;
                             for (int32_t k = 0; k < sp.capseg; k += std::max<int32_t>(1, sp.capseg - 1))
                                 slots[(size_t)(base + k)] = 1;
                             for (int32_t k = 0; k < sp.capseg; k += std::max<int32_t>(1, sp.capseg - 1))
                                 scratch[(size_t)(c * capseg + k)] = 1;
                         }
-                    seg_off += sp.nseg;
                 }
             }
         }
@@ -312,6 +311,45 @@ static void fuzz_merge_pack(int iters) {
     }
 }
 
+// Carry (the validity bookkeeping of a carried history, pulse heights and capture) against a model
+// that remembers which global row each row of the H-row buffer holds: calls of random length
+// (0 included) that continue the stream, break it (a j0 that does not continue) or follow a drop().
+// before(j0) must be the run of rows ..., j0 - 2, j0 - 1 at the buffer's end, offset(j0) its start.
+static void fuzz_carry(int iters) {
+    for (int it = 0; it < iters; ++it) {
+        const int64_t H = rint_(1, 40);
+        Carry k{H};
+        std::vector<int64_t> buf((size_t)H, -1);   // global row held by each buffer row (-1: none)
+        int64_t next = rint_(0, 1000);
+        for (int call = 0; call < 30; ++call) {
+            const int what = (int)rint_(0, 9);
+            if (what == 0) {
+                k.drop();
+                std::fill(buf.begin(), buf.end(), -1);   // a drop forgets the rows even if j0 continues
+            }
+            const int64_t j0 = what == 1 ? next + rint_(1, 50) : (what == 2 ? std::max<int64_t>(0, next - rint_(1, 50)) : next);
+            const int64_t n = rint_(0, 3) == 0 ? 0 : rint_(1, 2 * H + 3);
+            int64_t want = 0;
+            while (want < H && buf[(size_t)(H - 1 - want)] >= 0 && buf[(size_t)(H - 1 - want)] == j0 - 1 - want) ++want;
+            CHECK(k.before(j0) == want, "before(%lld) = %lld, model %lld (H %lld)", (long long)j0,
+                  (long long)k.before(j0), (long long)want, (long long)H);
+            CHECK(k.offset(j0) == H - want && k.offset(j0) >= 0 && k.offset(j0) <= H, "offset(%lld) = %lld",
+                  (long long)j0, (long long)k.offset(j0));
+            // the roll: the last H of (the rows valid before j0, the n new rows); n = 0 does not roll,
+            // but a call that broke the stream still starts a new one at j0 (capture's empty call)
+            std::vector<int64_t> all;
+            for (int64_t i = H - want; i < H; ++i) all.push_back(buf[(size_t)i]);
+            for (int64_t i = 0; i < n; ++i) all.push_back(j0 + i);
+            std::fill(buf.begin(), buf.end(), -1);
+            for (int64_t i = 0; i < H && i < (int64_t)all.size(); ++i) buf[(size_t)(H - 1 - i)] = all[all.size() - 1 - (size_t)i];
+            k.advance(j0, n);
+            CHECK(k.end == j0 + n && k.rows == std::min<int64_t>(H, want + n), "advance: end %lld rows %lld",
+                  (long long)k.end, (long long)k.rows);
+            next = j0 + n;
+        }
+    }
+}
+
 int main(int argc, char** argv) {
     const int iters = argc > 1 ? atoi(argv[1]) : 300;
     rng.seed(argc > 2 ? strtoull(argv[2], nullptr, 10) : 12345);
@@ -321,6 +359,7 @@ int main(int argc, char** argv) {
     fuzz_slot_order(iters / 10 + 2);
     fuzz_quantize(iters / 3 + 1);
     fuzz_merge_pack(iters);
+    fuzz_carry(iters);
     if (failures) {
         fprintf(stderr, "%d failures\n", failures);
         return 1;
