@@ -252,7 +252,8 @@ int mkid_replay_trigger(mkid_ctx* ctx, const int16_t* d_raw, int64_t n, int64_t 
  * reference's RawPulse rows I, Q float32 [npulses][2000] (pulses.py:30-43; not modified).
  * Outputs the PulseAnalysis fields (pulses.py:44-51): template [2000] f64 (deg-normalised,
  * peak at pstart), noise PSD [800] f64, and the scalars below. Fails with MKID_E_STATE when no
- * pulse survives the first pass. */
+ * pulse survives the first pass or none survives the second; d_template, d_noise and info are
+ * then left as they were. */
 typedef struct mkid_template_info {
     double count;   /* pulses in the final template (pass 2)                         */
     double count1;  /* pulses in the preliminary template (pass 1, first 1000 pulses) */
@@ -266,7 +267,9 @@ int mkid_make_template(mkid_ctx* ctx, const float* d_I, const float* d_Q, int64_
 /* The optimal filter the reference stubs (pulses.py:398; PulseAnalysis.coeff Float32Col(100)):
  * correlation weights g = ifft(S / J) (S = fft of the 800-sample template window starting `pre`
  * samples before its peak, deg->rad; J = noise PSD; DC bin zeroed), normalised to unit response
- * to the template; d_coeff[0..ncoeff) = g[pre-10 ...]. Device in, device out. */
+ * to the template; d_coeff[0..ncoeff) = g[pre-10 ...]. Where the window leaves the record, its
+ * samples outside [0, 2000) are zero, and so are the weights g[m] at m >= 800. 10 <= pre <= 2000,
+ * 1 <= ncoeff <= 800. Device in, device out. */
 int mkid_optimal_filter(mkid_ctx* ctx, const double* d_template, const double* d_noise, int32_t pre,
                         int32_t ncoeff, double* d_coeff);
 

@@ -16,7 +16,7 @@
 // medians are exact order statistics (workgroup radix select), pm / pdev / std / mean follow
 // numpy's pairwise float64 summation. Results agree with oracle/template_ref.py to float rounding
 // (atan2f and the least-squares fit differ in the last bits), and every accept/skip decision away
-// from a threshold is identical (tests/test_template.py).
+// from a threshold is identical (tests/test_template.py, tests/test_gpu_template.py).
 #include "mkid_internal.h"
 
 namespace mkid {

@@ -42,7 +42,7 @@ int mkid_make_template(mkid_ctx* c, const float* d_I, const float* d_Q, int64_t 
     HIPCHK(c, hipSetDevice(c->device));
     const size_t N = 2000, NN = 800;
     DevBuf<float> I, Q, refmed;
-    DevBuf<double> rows, nrows, peaks, scratch, tP, stats;
+    DevBuf<double> rows, nrows, peaks, scratch, tP, tPf, noise, stats;
     DevBuf<int32_t> accept, appended;
     HIPCHK(c, I.alloc((size_t)P * N));
     HIPCHK(c, Q.alloc((size_t)P * N));
@@ -51,6 +51,8 @@ int mkid_make_template(mkid_ctx* c, const float* d_I, const float* d_Q, int64_t 
     HIPCHK(c, peaks.alloc((size_t)P));
     HIPCHK(c, scratch.alloc((size_t)2 * P + 8));
     HIPCHK(c, tP.alloc(N));
+    HIPCHK(c, tPf.alloc(N));     // the caller's template and noise are written only on success
+    HIPCHK(c, noise.alloc(NN));
     HIPCHK(c, stats.alloc(8));
     HIPCHK(c, refmed.alloc(2));
     HIPCHK(c, accept.alloc((size_t)P));
@@ -61,14 +63,19 @@ int mkid_make_template(mkid_ctx* c, const float* d_I, const float* d_Q, int64_t 
     HIPCHK(c, hipMemsetAsync(appended.get(), 0, (size_t)P * 4, s));
     HIPCHK(c, hipMemsetAsync(stats.get(), 0, 64, s));
     hipError_t e = launch_make_template(I.get(), Q.get(), P, rows.get(), nrows.get(), accept.get(), peaks.get(),
-                                        appended.get(), scratch.get(), tP.get(), d_template, d_noise, stats.get(),
+                                        appended.get(), scratch.get(), tP.get(), tPf.get(), noise.get(), stats.get(),
                                         refmed.get(), s);
     if (e == hipErrorInvalidValue) FAIL(c, MKID_E_STATE, "make_template: no pulse passed the first pass");
     HIPCHK(c, e);
     double st[5];
     std::vector<double> t(N);
     HIPCHK(c, hipMemcpyAsync(st, stats.get(), 40, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(t.data(), d_template, N * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(t.data(), tPf.get(), N * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    // nothing accepted in pass 2: the column means are 0 / 0
+    if (!(st[4] > 0)) FAIL(c, MKID_E_STATE, "make_template: no pulse passed the second pass");
+    HIPCHK(c, hipMemcpyAsync(d_template, tPf.get(), N * 8, hipMemcpyDeviceToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_noise, noise.get(), NN * 8, hipMemcpyDeviceToDevice, s));
     HIPCHK(c, hipStreamSynchronize(s));
     info->pm = st[0];
     info->pdev = st[1];

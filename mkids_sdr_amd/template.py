@@ -27,7 +27,8 @@ def _dev(a, dtype):
 def make_template(ch, I, Q):
     """I, Q: float32 [P][2000] (host arrays or device tensors). Returns a dict with template
     [2000], noise [800], noiseidx [800] (np.fft.fftfreq(800, d=2e-6), pulses.py:391) and the
-    scalars count, count1, pm, pdev, flag, pstart."""
+    scalars count, count1, pm, pdev, flag, pstart. I and Q are left as they are. Raises MkidError
+    with MKID_E_STATE when no pulse passes the first pass or none passes the second."""
     import torch
     dI, dQ = _dev(I, torch.float32), _dev(Q, torch.float32)
     if dI.dim() != 2 or dI.shape[1] != NPTS or dQ.shape != dI.shape:

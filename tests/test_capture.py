@@ -394,7 +394,7 @@ def test_capture_chain(gpu):
 
 
 def _filter_stream(C=64, npulse=260, gap=2200, chans=(5, 40)):
-    """Two channels carry `npulse` pulses of the fake_pulses shape (tests/test_template.py) as a
+    """Two channels carry `npulse` pulses of the fake_pulses shape (tests/template_pulses.py) as a
     negative-going phase of 0.4 rad, `gap` rows apart, noise sigma 0.01; the others are zero.
     Packets sit at the pulse peaks, up to 5 rows off."""
     rng = np.random.default_rng(74)
