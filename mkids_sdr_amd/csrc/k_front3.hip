@@ -1,23 +1,17 @@
 // Fused front end k_front3, the default at N = 512 / 1024 / 2048 (configs 2, 3/4): the PFB, the
 // in-wave 512-point sub-FFTs, the bin-select combine, DDC, low-pass and phase, with the waves of a
-// workgroup specialised into transform and select roles.
+// workgroup specialised into transform and select roles. The stages it shares with k_front and
+// k_front5 (run geometry, hop loader, ring_put, pfb_fft512, lpf_even / lpf_odd, fix16_13, the IQ-tap
+// word, FRONT_STAMP) are in front_common.h; this file keeps the geometry, the roles, the LDS twiddle
+// tables, the Y stores, the bin select and the scheduling decisions.
 #include "front_common.h"
+
+#ifndef MKID_F3_N
+#error "k_front3.hip is built once per geometry: -DMKID_F3_N=512 / 1024 / 2048 (Makefile)"
+#endif
 
 namespace mkid {
 
-namespace {
-// k_front3 ring plane layout (NW = 4, Q = 256 samples per plane): samples qoff..qoff+3 of a hop go
-// to planes 0..3 at plane index qoff / 4, paired (ring3_idx). The refill's ds_write_b32 become
-// 2-way bank conflicts, which cost no extra cycles for ds_write_b32 (MI355X_MICROARCH.md §LDS).
-[[maybe_unused]] __device__ __forceinline__ void ring3_put(uint32_t* hop, int qoff, uint4 v) {
-    constexpr int Q = 256;
-    const int a = ring3_idx(qoff / 4);
-    hop[a] = v.x;
-    hop[Q + a] = v.y;
-    hop[2 * Q + a] = v.z;
-    hop[3 * Q + a] = v.w;
-}
-}  // namespace
 // Why specialise: when every wave runs the FFT phase and then the select phase with a barrier
 // between them (the round-2 design, history in DESIGN.md Appendix A), a SIMD idles whenever all its
 // waves wait on LDS (ring reads, the select's bin-indexed reads) or on the barrier. Here waves 0-7 only transform
@@ -71,43 +65,6 @@ struct G3 {
     static_assert(lds_bytes * WG_PER_CU <= 160 * 1024, "LDS");
 };
 
-// ring plane layout for any NW (paired planes of Q = M / NW = 256 samples): samples qoff..qoff+3 of
-// a hop (qoff a multiple of 4) go to plane o mod NW at plane index o / NW
-template <int NW>
-__device__ __forceinline__ void ring3_put_nw(uint32_t* hop, int qoff, uint4 v) {
-    if constexpr (NW == 4) {
-        ring3_put(hop, qoff, v);
-    } else if constexpr (NW == 2) {
-        constexpr int Q = 256;
-        const int a = ring3_idx(qoff / 2);   // plane indices qoff / 2 and qoff / 2 + 1 (at a + 2)
-        hop[a] = v.x;
-        hop[Q + a] = v.y;
-        hop[a + 2] = v.z;
-        hop[Q + a + 2] = v.w;
-    } else {
-        static_assert(NW == 1, "ring layout");
-        const int a = ring3_idx(qoff);
-        hop[a] = v.x;
-        hop[a + 2] = v.y;
-        hop[a + 4] = v.z;
-        hop[a + 6] = v.w;
-    }
-}
-
-#ifdef MKID_XP_STAMPS
-#define STAMP3(slot_)                                                                             \
-    do {                                                                                          \
-        __builtin_amdgcn_sched_barrier(0);                                                        \
-        const uint64_t tm_ = __builtin_amdgcn_s_memtime();                                        \
-        __builtin_amdgcn_sched_barrier(0);                                                        \
-        if (blockIdx.x < 4 && t >= 8 && t < 16 && (threadIdx.x & 63) == 0)                        \
-            reinterpret_cast<uint64_t*>(a.phase)[((blockIdx.x * 16 + (threadIdx.x >> 6)) * 8 +   \
-                                                  (t - 8)) * 16 + (slot_)] = tm_;                 \
-    } while (0)
-#else
-#define STAMP3(slot_) ((void)0)
-#endif
-
 template <int N>
 __global__ __launch_bounds__(G3<N>::BT, 4) void k_front3(FrontArgs a) {   // 16 waves per CU
     using G = G3<N>;
@@ -137,12 +94,10 @@ __global__ __launch_bounds__(G3<N>::BT, 4) void k_front3(FrontArgs a) {   // 16 
         tw2[i] = make_float2((float)cs, (float)sn);
     }
 
-    const int64_t k_b = (int64_t)blockIdx.x * a.frames_per_block;
-    int64_t k_e = k_b + a.frames_per_block;
-    if (k_e > a.K) k_e = a.K;
-    if (k_b >= k_e) return;
-    const int64_t k_start = k_b - kLpfHist;
-    const int nrun = (int)(k_e - k_b);
+    const FrontRun run(a);
+    if (run.empty()) return;
+    const int64_t k_b = run.k_b, k_start = run.k_start;
+    const int nrun = run.nrun;
     const int nit = (nrun + kLpfHist + F - 1) / F;    // iterations of F frames from k_start
 
     if (xform) {
@@ -155,8 +110,7 @@ __global__ __launch_bounds__(G3<N>::BT, 4) void k_front3(FrontArgs a) {   // 16 
             for (int g = 0; g < 2 * T - 1 + F; g += 2) {
                 const int64_t hop = h0 + g + qh;
                 if (hop > h0 + 2 * T - 2 + F) continue;
-                const uint4 v = front_load4<M>(a, h0 + g, xt);
-                ring3_put_nw<NW>(ring + (int)(((hop % RS) + RS) % RS) * M, qoff, v);
+                ring_put<NW>(ring + (int)(((hop % RS) + RS) % RS) * M, qoff, front_load<M, 1>(a, h0 + g, xt));
             }
         }
         uint2 tq[8];
@@ -190,94 +144,49 @@ __global__ __launch_bounds__(G3<N>::BT, 4) void k_front3(FrontArgs a) {   // 16 
             int sb = rb + slot;
             sb -= sb >= RS ? RS : 0;
             float2 v[8];
-            uint32_t xr[8][T];
-#pragma unroll
-            for (int hi = 0; hi < 2; ++hi)
-#pragma unroll
-                for (int tau = 0; tau < T; ++tau) {
-                    int sl = sb + 2 * tau + hi;
-                    sl -= sl >= RS ? RS : 0;
-                    const uint32_t* pl = ring + sl * M + w * (M / NW) + 2 * L;
-                    const uint2 p01 = *reinterpret_cast<const uint2*>(pl);
-                    const uint2 p23 = *reinterpret_cast<const uint2*>(pl + 128);
-                    xr[4 * hi + 0][tau] = p01.x;
-                    xr[4 * hi + 1][tau] = p01.y;
-                    xr[4 * hi + 2][tau] = p23.x;
-                    xr[4 * hi + 3][tau] = p23.y;
-                }
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                uint32_t x4[T];
-#pragma unroll
-                for (int tau = 0; tau < T; ++tau) x4[tau] = xr[r][tau];
-                const uint32_t i01 = __builtin_amdgcn_perm(x4[1], x4[0], kPermI);
-                const uint32_t q01 = __builtin_amdgcn_perm(x4[1], x4[0], kPermQ);
-                const uint32_t i23 = __builtin_amdgcn_perm(x4[3], x4[2], kPermI);
-                const uint32_t q23 = __builtin_amdgcn_perm(x4[3], x4[2], kPermQ);
-                int32_t ai = dot2_first(tq[r].x, i01);
-                ai = __builtin_amdgcn_sdot2(as_s2(tq[r].y), as_s2(i23), ai, false);
-                int32_t aq = dot2_first(tq[r].x, q01);
-                aq = __builtin_amdgcn_sdot2(as_s2(tq[r].y), as_s2(q23), aq, false);
-                v[r] = make_float2((float)ai, (float)aq);
-            }
-            dft<8>(v);
-#pragma unroll
-            for (int k = 1; k < 8; ++k) v[k] = cmul_pk(v[k], w1[k - 1]);
-            t1_lds(v, reg, L);
-            dft<8>(v);
-#pragma unroll
-            for (int k = 1; k < 8; ++k) v[k] = cmul_pk(v[k], w2[k - 1]);
-            float2* t2w = reg + 72 * kl + la;
-            const float2* t2r = reg + 72 * kl + 9 * la;
-#pragma unroll
-            for (int r = 0; r < 8; ++r) t2w[9 * r] = v[r];
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int r = 0; r < 8; ++r) v[r] = t2r[r];
-            dft<8>(v);
-            __builtin_amdgcn_wave_barrier();
+            pfb_fft512<M, RS>(ring, sb, w * (M / NW), tq, w1, w2, reg, L, v);
             float2* yw = reg + ((kl + 8 * la) ^ (la << 1));
 #pragma unroll
             for (int r = 0; r < 8; ++r) yw[64 * r] = v[r];
         };
         if constexpr (!G::PF2) {
             for (int t = 0; t <= nit; ++t) {
-                STAMP3(0);
+                FRONT_STAMP(t, 8, 0);
                 if (t < nit) {
                     const int kr = -kLpfHist + F * t;
                     // the hops iteration t + 1 adds: loaded now, written after this wave's PFB
-                    const uint4 pre = front_load4<M>(a, k_b + kr + F, xt);
+                    const Hop<1> pre = front_load<M, 1>(a, k_b + kr + F, xt);
                     transform(t);
                     // ring refill: hops k+F .. k+2F-1 over hops k-2T-1 .. (no reader this iteration)
                     int ws = rb + 2 * T - 1 + F + qh;
                     ws -= ws >= RS ? RS : 0;
                     ws -= ws >= RS ? RS : 0;
-                    ring3_put_nw<NW>(ring + ws * M, qoff, pre);
+                    ring_put<NW>(ring + ws * M, qoff, pre);
                     rb += F;
                     rb -= rb >= RS ? RS : 0;
                 }
-                STAMP3(1);
+                FRONT_STAMP(t, 8, 1);
                 __syncthreads();
-                STAMP3(2);
+                FRONT_STAMP(t, 8, 2);
             }
         } else {
             // the prefetch two iterations deep, unrolled by 2 so that the two loads in flight sit in
             // fixed registers and the wait before each refill leaves the newer one outstanding
             // (vmcnt(1)); the loads are unconditional (past the run they read unused words)
             auto iter = [&](int t, const Load4& use, Load4& fill) __attribute__((always_inline)) {
-                STAMP3(0);
+                FRONT_STAMP(t, 8, 0);
                 const int kr = -kLpfHist + F * t;
                 fill = front_load4_nb<M>(a, k_b + kr + 2 * F, xt);   // the hops iteration t + 2 adds
                 transform(t);
                 int ws = rb + 2 * T - 1 + F + qh;   // the ring refill, as above
                 ws -= ws >= RS ? RS : 0;
                 ws -= ws >= RS ? RS : 0;
-                ring3_put_nw<NW>(ring + ws * M, qoff, use.past ? make_uint4(0, 0, 0, 0) : use.v);
+                ring_put<NW>(ring + ws * M, qoff, Hop<1>{{use.past ? make_uint4(0, 0, 0, 0) : use.v}});
                 rb += F;
                 rb -= rb >= RS ? RS : 0;
-                STAMP3(1);
+                FRONT_STAMP(t, 8, 1);
                 __syncthreads();
-                STAMP3(2);
+                FRONT_STAMP(t, 8, 2);
             };
             Load4 pa = front_load4_nb<M>(a, k_b - kLpfHist + F, xt), pb;
             int t = 0;
@@ -286,10 +195,10 @@ __global__ __launch_bounds__(G3<N>::BT, 4) void k_front3(FrontArgs a) {   // 16 
                 iter(t + 1, pb, pa);
             }
             if (t < nit) iter(t, pa, pb);
-            STAMP3(0);   // t = nit: the select waves' last iteration
-            STAMP3(1);
+            FRONT_STAMP(t, 8, 0);   // t = nit: the select waves' last iteration
+            FRONT_STAMP(t, 8, 1);
             __syncthreads();
-            STAMP3(2);
+            FRONT_STAMP(t, 8, 2);
         }
     } else {
         // ---------------- select waves: channels st + SPT q, one iteration behind ---------------
@@ -333,7 +242,7 @@ __global__ __launch_bounds__(G3<N>::BT, 4) void k_front3(FrontArgs a) {   // 16 
         int lrow = (int)((a.k0 + k_start) & (int64_t)(a.P - 1));
         __syncthreads();
         for (int t = 0; t <= nit; ++t) {
-            STAMP3(3);
+            FRONT_STAMP(t, 8, 3);
             if (t > 0) {
                 const int kr = -kLpfHist + F * (t - 1);
                 float2 lov[F][CPT];
@@ -357,20 +266,10 @@ __global__ __launch_bounds__(G3<N>::BT, 4) void k_front3(FrontArgs a) {   // 16 
                         z[q] = cmul_add_pk(X, lov[f][q], ncen[q]);   // z - c'
                     }
                     if ((f & 1) == 0) {
-#pragma unroll
-                        for (int m = 0; m < 13; ++m)
-#pragma unroll
-                            for (int q = 0; q < CPT; ++q) acc[q][m] = fma_tap<1>(gp[m], z[q], acc[q][m]);
+                        lpf_even<CPT>(gp, z, acc);
                     } else {
                         float2 y[CPT];
-#pragma unroll
-                        for (int q = 0; q < CPT; ++q) y[q] = fma_tap<0>(gp[0], z[q], acc[q][0]);
-#pragma unroll
-                        for (int m = 0; m < 12; ++m)
-#pragma unroll
-                            for (int q = 0; q < CPT; ++q) acc[q][m] = fma_tap<0>(gp[m + 1], z[q], acc[q][m + 1]);
-#pragma unroll
-                        for (int q = 0; q < CPT; ++q) acc[q][12] = make_float2(0.f, 0.f);
+                        lpf_odd<CPT>(gp, z, acc, y);
                         if (kf > 0 && kf < nrun) {
                             const int jr = (kf - 1) >> 1;
 #pragma unroll
@@ -379,26 +278,22 @@ __global__ __launch_bounds__(G3<N>::BT, 4) void k_front3(FrontArgs a) {   // 16 
                                 ys[q].x += y[q].x;
                                 ys[q].y += y[q].y;
                                 const float ph = phase_atan2(y[q].y + cor[q].y, y[q].x + cor[q].x);
-                                int qv = __float2int_rn(ph * 8192.0f);
-                                qv = qv < -25736 ? -25736 : (qv > 25736 ? 25736 : qv);
                                 // plain stores: with the slot order a wave's store covers its 64
                                 // channels within 2 (raw) or 4 (phase) lines, merged in L2
 #ifndef MKID_XP_STAMPS   // the timing build keeps its stamps in the phase buffer
                                 if (phase_run) (phase_run + jr * C)[c] = ph;
 #endif
-                                (raw_run + jr * C)[c] = (int16_t)qv;
-                                if (c == a.iq_ch && a.iqtap) {
-                                    a.iqtap[2 * ((k_b >> 1) + jr)] = iq16(y[q].x + a.cen.tap_off.x);
-                                    a.iqtap[2 * ((k_b >> 1) + jr) + 1] = iq16(y[q].y + a.cen.tap_off.y);
-                                }
+                                (raw_run + jr * C)[c] = fix16_13(ph);
+                                if (c == a.iq_ch && a.iqtap)
+                                    *reinterpret_cast<uint32_t*>(a.iqtap + 2 * ((k_b >> 1) + jr)) = iq_tap_word(a.cen, y[q]);
                             }
                         }
                     }
                 }
             }
-            STAMP3(4);
+            FRONT_STAMP(t, 8, 4);
             __syncthreads();
-            STAMP3(5);
+            FRONT_STAMP(t, 8, 5);
         }
         if (a.ysum)
 #pragma unroll
@@ -407,7 +302,7 @@ __global__ __launch_bounds__(G3<N>::BT, 4) void k_front3(FrontArgs a) {   // 16 
 }
 
 template <int N>
-static hipError_t launch_front3_n(const FrontArgs& a0, hipStream_t s) {
+hipError_t launch_front3(const FrontArgs& a0, hipStream_t s) {
     using G = G3<N>;
     static std::atomic<uint64_t> attr_mask{0};
     hipError_t e = ensure_lds_attr(attr_mask, (const void*)k_front3<N>, (int)G::lds_bytes);
@@ -415,45 +310,13 @@ static hipError_t launch_front3_n(const FrontArgs& a0, hipStream_t s) {
     FrontArgs a = a0;
     if (a.K <= 0) return hipSuccess;
     const int64_t ncu = a.ncu > 0 ? a.ncu : 256;
-    int64_t fpb = a.K / (ncu * G::WG_PER_CU);    // one run per resident workgroup
-    fpb = fpb < 64 ? 64 : (fpb > 4096 ? 4096 : fpb);
-    fpb = (fpb + G::F - 1) / G::F * G::F;
-    a.frames_per_block = fpb;
-    const int64_t blocks = (a.K + fpb - 1) / fpb;
+    const int64_t blocks = front_grid(a, ncu * G::WG_PER_CU, 4096, G::F);   // one run per resident workgroup
     hipLaunchKernelGGL(k_front3<N>, dim3((unsigned)blocks), dim3(G::BT), G::lds_bytes, s, a);
     return hipGetLastError();
 }
 
-#ifdef MKID_F3_N
-// One geometry per object (Makefile: k_front3_<N>.o), so that each takes scheduler flags of its
-// own (F3_FLAGS_<N>); the N = 2048 object also holds the dispatch.
-hipError_t launch_front3_512(const FrontArgs& a, hipStream_t s);
-hipError_t launch_front3_1024(const FrontArgs& a, hipStream_t s);
-hipError_t launch_front3_2048(const FrontArgs& a, hipStream_t s);
-#define MKID_F3_CAT2(a, b) a##b
-#define MKID_F3_CAT(a, b) MKID_F3_CAT2(a, b)
-hipError_t MKID_F3_CAT(launch_front3_, MKID_F3_N)(const FrontArgs& a, hipStream_t s) {
-    return launch_front3_n<MKID_F3_N>(a, s);
-}
-#if MKID_F3_N == 2048
-hipError_t launch_front3(int N, const FrontArgs& a, hipStream_t s) {
-    switch (N) {
-        case 2048: return launch_front3_2048(a, s);
-        case 1024: return launch_front3_1024(a, s);
-        case 512: return launch_front3_512(a, s);
-        default: return hipErrorInvalidValue;
-    }
-}
-#endif
-#else
-hipError_t launch_front3(int N, const FrontArgs& a, hipStream_t s) {
-    switch (N) {
-        case 2048: return launch_front3_n<2048>(a, s);
-        case 1024: return launch_front3_n<1024>(a, s);
-        case 512: return launch_front3_n<512>(a, s);
-        default: return hipErrorInvalidValue;
-    }
-}
-#endif
+// One geometry per object (Makefile: k_front3_<N>.o), so that each takes scheduler flags of its own
+// (F3_FLAGS_<N>); launch_fused (k_front.hip) calls the three instantiations
+template hipError_t launch_front3<MKID_F3_N>(const FrontArgs&, hipStream_t);
 
 }  // namespace mkid

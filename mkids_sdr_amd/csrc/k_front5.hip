@@ -27,25 +27,14 @@
 // the 4 regions of its bin's s and evaluates X[b] = (P_0 + t^2 P_2) + t (P_1 + t^2 P_3), t = W_N^b:
 // 4 instead of 8 bin-indexed LDS reads and 4 instead of 9 complex MACs per channel-frame
 // (tools/front2_layouts.py precombine_f32, same-box -6 %, profiles/r05/r05l_kbench_c5_precombine.json).
+// The stages shared with k_front3 / k_front (run geometry, hop loader, ring_put, pfb_fft512, lpf_even /
+// lpf_odd, fix16_13, the IQ-tap word, FRONT_STAMP) are in front_common.h; this file keeps the
+// geometry, the roles, the in-register twiddles, the pre-combination and the select.
 #include "front_common.h"
 
 #include <type_traits>
 
-#ifdef MKID_XP_STAMPS
-// timing-only build: lane 0 of every wave of workgroups 0-3 stamps s_memtime at points of
-// iterations (frames) 8..15 into a.phase (tools/stamps4.py ... v5); the phase output is garbage
-#define STAMP5(t_, slot_)                                                                         \
-    do {                                                                                          \
-        __builtin_amdgcn_sched_barrier(0);                                                        \
-        const uint64_t tm_ = __builtin_amdgcn_s_memtime();                                        \
-        __builtin_amdgcn_sched_barrier(0);                                                        \
-        if (blockIdx.x < 4 && (t_) >= 40 && (t_) < 48 && (threadIdx.x & 63) == 0)                 \
-            reinterpret_cast<uint64_t*>(a.phase)[((blockIdx.x * 16 + (threadIdx.x >> 6)) * 8 +   \
-                                                  ((t_) - 40)) * 16 + (slot_)] = tm_;              \
-    } while (0)
-#else
-#define STAMP5(t_, slot_) ((void)0)
-#endif
+// the timing build (MKID_XP_STAMPS, tools/stamps4.py ... v5) stamps iterations (frames) 40..47
 
 namespace mkid {
 
@@ -63,7 +52,6 @@ struct G5 {
     static constexpr int Q = M / NW;              // samples per hop plane
     static constexpr int REG = 576;               // float2 per (frame, sub-FFT) region
     static constexpr int FB = NW * REG;           // float2 per frame
-    static constexpr int HIST = (2 * T - 1 + kLpfHist) * M;
     static constexpr size_t off_fbuf = (size_t)RS * M * 4;
     // [C] float2 per-channel slot: the avgIQ partial sums while the accumulator is armed
     // (k_front5<true>), else the centring constant -c' (k_front5<false>, the streaming kernel)
@@ -73,26 +61,6 @@ struct G5 {
     static_assert(SW3 * 64 * 3 + (SW - SW3) * 64 * 2 == C, "every channel has one select slot");
     static_assert(lds_bytes <= 160 * 1024, "LDS");
 };
-
-// the 8 samples transform thread xt contributes to hop `hop` (samples 8 xt .. 8 xt + 7)
-__device__ __forceinline__ void load_hop(const FrontArgs& a, int64_t hop, int xt, uint4& v0, uint4& v1) {
-    const int64_t s0 = hop * G5::M + (int64_t)xt * G5::SPT;
-    if (s0 >= a.K * G5::M) {
-        v0 = v1 = make_uint4(0, 0, 0, 0);
-        return;
-    }
-    if (s0 >= -a.avail) {
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-        const u32x4 p = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(a.x + s0));
-        const u32x4 q = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(a.x + s0 + 4));
-        v0 = make_uint4(p.x, p.y, p.z, p.w);
-        v1 = make_uint4(q.x, q.y, q.z, q.w);
-        return;
-    }
-    const uint32_t* h = a.xhist + (s0 + a.avail + G5::HIST);
-    v0 = *reinterpret_cast<const uint4*>(h);
-    v1 = *reinterpret_cast<const uint4*>(h + 4);
-}
 
 // Pre-combination twiddles W_1024^{e + 64 r} = w0 W_16^r (w0 = W_1024^e, e = kl + 8 la), built per
 // frame from w0 with three constants: u1 = w0 W_16, vv = w0 conj(W_16) (= (-i) w0 W_16^3) and
@@ -122,16 +90,6 @@ __device__ __forceinline__ PreTw pre_twiddles(float2 w0) {
     return PreTw{float2_of(u1), float2_of(vv), float2_of(u2)};
 }
 
-// hop layout: sample o at plane o % 8, plane index o / 8 stored at ring3_idx(o / 8), the paired
-// plane layout of k_front3 (plane entries 64 apart adjacent, so a lane's PFB points
-// r, r + 1 are one ds_read_b64)
-__device__ __forceinline__ void ring_put(uint32_t* hop, int xt, uint4 v0, uint4 v1) {
-    constexpr int Q = G5::Q;
-    uint32_t* p = hop + ring3_idx(xt);
-    p[0] = v0.x; p[Q] = v0.y; p[2 * Q] = v0.z; p[3 * Q] = v0.w;
-    p[4 * Q] = v1.x; p[5 * Q] = v1.y; p[6 * Q] = v1.z; p[7 * Q] = v1.w;
-}
-
 // measured and dropped (DESIGN.md §5 k_front5): T1 in registers, LO one frame ahead, one Horner
 // chain, even/odd chains, unsplit Y reads, no barrier between channels, transform-wave priority
 
@@ -142,7 +100,7 @@ __device__ __forceinline__ void ring_put(uint32_t* hop, int xt, uint4 v0, uint4 
 // RF (waves 12-15, 256 threads like the transform waves, the lightest select work): the ring
 // refill. In the barrier interval in which the transform waves compute frame k (one ahead of the
 // select), hop k + 1 goes over hop k - 2T, a slot no wave reads in that interval; thread xt loads
-// and writes the 8 samples load_hop / ring_put give it. Off the transform waves' chain: -8.8 %
+// and writes samples 8 xt .. 8 xt + 7 of the hop (front_load / ring_put, front_common.h). Off the transform waves' chain: -8.8 %
 // same box (profiles/r05/r05u_kbench_c5_refill.json; waves 4-7 or 4-11 instead: -7 %).
 template <int CPT, bool ACC, bool RF>
 __device__ __forceinline__ void select_run(const FrontArgs& a, const float2* fbuf, float2* ysl, int c0, int cs,
@@ -175,10 +133,8 @@ __device__ __forceinline__ void select_run(const FrontArgs& a, const float2* fbu
     int lrow = (int)((a.k0 + k_start) & (int64_t)(a.P - 1));
     __syncthreads();   // prologue: ring written
     if (RF) {          // transform iteration 0 computes frame k_start: hop k_start + 1
-        uint4 v0, v1;
         const int64_t h = k_start + 1;
-        load_hop(a, h, xt, v0, v1);
-        ring_put(ring + (int)(((h % RS) + RS) % RS) * G5::M, xt, v0, v1);
+        ring_put<G5::NW>(ring + (int)(((h % RS) + RS) % RS) * G5::M, G5::SPT * xt, front_load<G5::M, 2>(a, h, xt));
     }
     __syncthreads();   // transform iteration 0 (frame k_start) wrote Y buffer 0
     // frames in pairs (even: accumulate, odd: output), one barrier after each: frame k_start + 2p
@@ -192,13 +148,13 @@ __device__ __forceinline__ void select_run(const FrontArgs& a, const float2* fbu
         const int kf = -kLpfHist + 2 * p;   // even
 #pragma unroll
         for (int f = 0; f < 2; ++f) {
-            STAMP5(2 * p + 1 + f, 8);
+            FRONT_STAMP(2 * p + 1 + f, 40, 8);
             // this interval's refill (transform iteration 2p + f + 1, frame k_start + 2p + f + 1):
             // hop k_start + 2p + f + 2, loaded first (its wait then covers nothing issued later)
             const int64_t hr = k_start + 2 * p + f + 2;
             const bool rf = RF && 2 * p + f + 1 < nit;
-            uint4 rv0, rv1;
-            if (rf) load_hop(a, hr, xt, rv0, rv1);
+            Hop<2> rv;
+            if (rf) rv = front_load<G5::M, 2>(a, hr, xt);
             // channel base re-defined every frame so per-channel addresses are rebuilt in the loop
             // (a few VALU) instead of being hoisted as 64-bit pointers that crowd the low-pass state
             int cb = c0;
@@ -240,8 +196,7 @@ __device__ __forceinline__ void select_run(const FrontArgs& a, const float2* fbu
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int q = 0; q < CPT; ++q) {
-#pragma unroll
-                    for (int m = 0; m < 13; ++m) acc[q][m] = fma_tap<1>(gp[m], zz[q], acc[q][m]);   // g_{2m+1}
+                    lpf_even(gp, zz[q], acc[q]);   // g_{2m+1}
                 }
             } else {
                 const int ko = kf + 1;   // odd: output row (ko - 1) / 2 of the run
@@ -255,10 +210,7 @@ __device__ __forceinline__ void select_run(const FrontArgs& a, const float2* fbu
 #pragma unroll
                 for (int q = 0; q < CPT; ++q) {
                     const float2 z = zq(q);
-                    const float2 y = fma_tap<0>(gp[0], z, acc[q][0]);                                // g_0
-#pragma unroll
-                    for (int m = 0; m < 12; ++m) acc[q][m] = fma_tap<0>(gp[m + 1], z, acc[q][m + 1]);  // g_{2m+2}
-                    acc[q][12] = make_float2(0.f, 0.f);
+                    const float2 y = lpf_odd(gp, z, acc[q]);   // g_{2m}
                     ph[q] = phase_atan2(y.y + corv[q].y, y.x + corv[q].x);
                     if (out) {
                         const int c = cb + cs * q;
@@ -274,9 +226,7 @@ __device__ __forceinline__ void select_run(const FrontArgs& a, const float2* fbu
                         }
                         if (a.iqtap) {               // uniform; the IQ-tap channel's sample by select
                             const bool hit = c == a.iq_ch;
-                            const float2 yt = make_float2(y.x + a.cen.tap_off.x, y.y + a.cen.tap_off.y);
-                            const uint32_t v = (uint32_t)(uint16_t)iq16(yt.x) | ((uint32_t)(uint16_t)iq16(yt.y) << 16);
-                            iqv = hit ? v : iqv;
+                            iqv = hit ? iq_tap_word(a.cen, y) : iqv;
                             iqhit = iqhit || hit;
                         }
                     }
@@ -289,20 +239,18 @@ __device__ __forceinline__ void select_run(const FrontArgs& a, const float2* fbu
 #pragma unroll
                     for (int q = 0; q < CPT; ++q) {
                         const uint32_t c = (uint32_t)(cb + cs * q);
-                        int qv = __float2int_rn(ph[q] * 8192.0f);
-                        qv = qv < -25736 ? -25736 : (qv > 25736 ? 25736 : qv);
 #ifndef MKID_XP_STAMPS
                         if (phase_run) __builtin_nontemporal_store(ph[q], reinterpret_cast<float*>(prow + c * 4u));
 #endif
-                        __builtin_nontemporal_store((int16_t)qv, reinterpret_cast<int16_t*>(rrow + c * 2u));
+                        __builtin_nontemporal_store(fix16_13(ph[q]), reinterpret_cast<int16_t*>(rrow + c * 2u));
                     }
                     if (iqhit) *reinterpret_cast<uint32_t*>(a.iqtap + 2 * ((k_b >> 1) + jr)) = iqv;
                 }
             }
-            if (rf) ring_put(ring + (int)(((hr % RS) + RS) % RS) * G5::M, xt, rv0, rv1);
-            STAMP5(2 * p + 1 + f, 9);
+            if (rf) ring_put<G5::NW>(ring + (int)(((hr % RS) + RS) % RS) * G5::M, G5::SPT * xt, rv);
+            FRONT_STAMP(2 * p + 1 + f, 40, 9);
             __syncthreads();   // Y buffer f read; the transform waves wrote the next frame into 1 - f
-            STAMP5(2 * p + 1 + f, 10);
+            FRONT_STAMP(2 * p + 1 + f, 40, 10);
         }
         lrow += 2;
     };
@@ -331,12 +279,10 @@ __global__ __launch_bounds__(G5::BT, 4) void k_front5(FrontArgs a) {
     const int L = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    const int64_t k_b = (int64_t)blockIdx.x * a.frames_per_block;
-    int64_t k_e = k_b + a.frames_per_block;
-    if (k_e > a.K) k_e = a.K;
-    if (k_b >= k_e) return;
-    const int64_t k_start = k_b - kLpfHist;
-    const int nrun = (int)(k_e - k_b);
+    const FrontRun run(a);
+    if (run.empty()) return;
+    const int64_t k_b = run.k_b, k_start = run.k_start;
+    const int nrun = run.nrun;
     const int nit = nrun + kLpfHist;                 // iterations: frames k_start .. k_e - 1 (even)
 
 #ifdef MKID_XP_STAMPS
@@ -351,11 +297,8 @@ __global__ __launch_bounds__(G5::BT, 4) void k_front5(FrontArgs a) {
         const int rw = wave, xt = tid;               // xt: thread among the transform waves
         {   // prologue: hops k_start-2T+1 .. k_start -> ring (slot = hop mod RS)
             const int64_t h0 = k_start - 2 * T + 1;
-            for (int g = 0; g < 2 * T; ++g) {
-                uint4 v0, v1;
-                load_hop(a, h0 + g, xt, v0, v1);
-                ring_put(ring + (int)((((h0 + g) % RS) + RS) % RS) * M, xt, v0, v1);
-            }
+            for (int g = 0; g < 2 * T; ++g)
+                ring_put<NW>(ring + (int)((((h0 + g) % RS) + RS) % RS) * M, G::SPT * xt, front_load<M, 2>(a, h0 + g, xt));
         }
         uint2 tq[G::SPW][8];
 #pragma unroll
@@ -383,7 +326,7 @@ __global__ __launch_bounds__(G5::BT, 4) void k_front5(FrontArgs a) {
             asm volatile("" : "+v"(w1[k - 1].x), "+v"(w1[k - 1].y), "+v"(w2[k - 1].x), "+v"(w2[k - 1].y));
         }
         for (int t = 0; t <= nit; ++t) {
-            STAMP5(t, 0);
+            FRONT_STAMP(t, 40, 0);
             if (t < nit) {
                 float2* fb = fbuf + (t & 1) * G::FB;
                 // Y_rw of sub-FFT 0, held in VGPRs for the pre-combination (16 VGPRs the transform
@@ -394,51 +337,8 @@ __global__ __launch_bounds__(G5::BT, 4) void k_front5(FrontArgs a) {
                 for (int s = 0; s < G::SPW; ++s) {
                     const int w = rw + G::FW * s;
                     float2* reg = fb + w * G::REG;
-                    uint32_t xr[8][T];
-#pragma unroll
-                    for (int hi = 0; hi < 2; ++hi)
-#pragma unroll
-                        for (int tau = 0; tau < T; ++tau) {
-                            int sl = rb + 2 * tau + hi;
-                            sl -= sl >= RS ? RS : 0;
-                            const uint32_t* pl = ring + sl * M + w * G::Q + 2 * L;
-                            const uint2 p01 = *reinterpret_cast<const uint2*>(pl);
-                            const uint2 p23 = *reinterpret_cast<const uint2*>(pl + 128);
-                            xr[4 * hi + 0][tau] = p01.x;
-                            xr[4 * hi + 1][tau] = p01.y;
-                            xr[4 * hi + 2][tau] = p23.x;
-                            xr[4 * hi + 3][tau] = p23.y;
-                        }
                     float2 v[8];
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) {
-                        const uint32_t* x4 = xr[r];
-                        const uint32_t i01 = __builtin_amdgcn_perm(x4[1], x4[0], kPermI);
-                        const uint32_t q01 = __builtin_amdgcn_perm(x4[1], x4[0], kPermQ);
-                        const uint32_t i23 = __builtin_amdgcn_perm(x4[3], x4[2], kPermI);
-                        const uint32_t q23 = __builtin_amdgcn_perm(x4[3], x4[2], kPermQ);
-                        int32_t ai = dot2_first(tq[s][r].x, i01);
-                        ai = __builtin_amdgcn_sdot2(as_s2(tq[s][r].y), as_s2(i23), ai, false);
-                        int32_t aq = dot2_first(tq[s][r].x, q01);
-                        aq = __builtin_amdgcn_sdot2(as_s2(tq[s][r].y), as_s2(q23), aq, false);
-                        v[r] = make_float2((float)ai, (float)aq);
-                    }
-                    dft<8>(v);
-#pragma unroll
-                    for (int k = 1; k < 8; ++k) v[k] = cmul_pk(v[k], w1[k - 1]);
-                    t1_lds(v, reg, L);
-                    dft<8>(v);
-#pragma unroll
-                    for (int k = 1; k < 8; ++k) v[k] = cmul_pk(v[k], w2[k - 1]);
-                    float2* t2w = reg + 72 * kl + la;
-                    const float2* t2r = reg + 72 * kl + 9 * la;
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) t2w[9 * r] = v[r];
-                    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) v[r] = t2r[r];
-                    dft<8>(v);
-                    __builtin_amdgcn_wave_barrier();
+                    pfb_fft512<M, RS>(ring, rb, w * G::Q, tq[s], w1, w2, reg, L, v);
                     float2* yw = reg + ((kl + 8 * la) ^ (la << 1));
                     if (s == 0) {
 #pragma unroll
@@ -472,15 +372,15 @@ __global__ __launch_bounds__(G5::BT, 4) void k_front5(FrontArgs a) {
                             yw[64 * r] = q;
                         }
                     }
-                    STAMP5(t, 1 + s);
+                    FRONT_STAMP(t, 40, 1 + s);
                 }
                 // the ring refill (hop k + 1 over hop k - 2T) is done by select waves 12-15
                 rb += 1;
                 rb -= rb >= RS ? RS : 0;
             }
-            STAMP5(t, 3);
+            FRONT_STAMP(t, 40, 3);
             __syncthreads();
-            STAMP5(t, 4);
+            FRONT_STAMP(t, 40, 4);
         }
 #ifdef MKID_XP_STAMPS
         if (tid == 0) bst[1] = __builtin_amdgcn_s_memtime();
@@ -505,12 +405,7 @@ hipError_t launch_front5(const FrontArgs& a0, hipStream_t s) {
     if (a.K <= 0) return hipSuccess;
     // one run per CU (a 2^30-sample chunk: 2048 frames per CU of MI355X's 256, the 24-frame
     // low-pass warm-up 1.2 % of it); runs are even so that every run starts on an output row
-    const int64_t ncu = a.ncu > 0 ? a.ncu : 256;
-    int64_t fpb = a.K / ncu;
-    fpb = fpb < 64 ? 64 : (fpb > 4096 ? 4096 : fpb);
-    fpb = (fpb + 1) / 2 * 2;
-    a.frames_per_block = fpb;
-    const int64_t blocks = (a.K + fpb - 1) / fpb;
+    const int64_t blocks = front_grid(a, a.ncu > 0 ? a.ncu : 256, 4096, 2);
     if (a.ysum)
         hipLaunchKernelGGL(k_front5<true>, dim3((unsigned)blocks), dim3(G5::BT), G5::lds_bytes, s, a);
     else

@@ -8,7 +8,7 @@
 // butterfly over the wave (deterministic). The phase rows of one packet's window are strided by
 // C floats, so each lane's read is its own cache line; the volume is small (ncoeff x 4 B per
 // packet). Windows that start before the call's first row read the context's carried history of
-// the previous call's last rows (mkid_api.hip pulse_heights), so a streamed run loses heights
+// the previous call's last rows (mkid_calib.hip pulse_heights), so a streamed run loses heights
 // only at the stream start and for windows past the call's last row.
 #include "mkid_internal.h"
 

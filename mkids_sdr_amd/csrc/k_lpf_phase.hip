@@ -3,13 +3,12 @@
 //   y_j = sum_i g_i z_{2j+1-i}                  (taps int(lpf*(2**11-1))/2^11, ROACH_Pulses.py:69,88)
 //   phi_j = atan2(Im y - qc, Re y - ic)          (pulse_triggering_IQ.py:152, conv_phase_centers)
 //   computed centred: y - c = sum_i g_i (z_i - c') + r  (mkid_internal.h Centring)
-//   raw_j = clamp(rint(phi_j * 2^13), +-25736)   (Fix16_13, ROACH_Pulses.py:274-278)
+//   raw_j = fix16_13(phi_j): clamp(rint(phi_j * 2^13), +-pi 2^13)   (front_common.h)
 // Thread = one channel x JB = 13*kLpfRounds consecutive outputs: a 26-deep register window slides
 // by 2 frames per output; slots are static inside each 13-output round, so z is read from HBM
 // once plus a 25-frame prologue per thread (25/(2 JB) re-read). Lanes = consecutive channels:
 // every z load / phase store of a wave is one contiguous 512 B / 256 B segment.
-#include "fft_common.h"
-#include "mkid_internal.h"
+#include "front_common.h"
 
 namespace mkid {
 
@@ -60,10 +59,8 @@ __global__ __launch_bounds__(kLpfThreads) void k_lpf_phase(LpfArgs a) {
                 ys.x += yr;
                 ys.y += yi;
                 const float ph = phase_atan2(yi + cor.y, yr + cor.x);
-                int q = __float2int_rn(ph * 8192.0f);
-                q = q < -25736 ? -25736 : (q > 25736 ? 25736 : q);
                 if (a.phase) a.phase[j * C + c] = ph;
-                a.raw[j * C + c] = (int16_t)q;
+                a.raw[j * C + c] = fix16_13(ph);
                 if (c == a.iq_ch && a.iqtap) {
                     a.iqtap[2 * j] = iq16(yr + a.cen.tap_off.x);
                     a.iqtap[2 * j + 1] = iq16(yi + a.cen.tap_off.y);

@@ -242,8 +242,9 @@ bool channelize_supported(int N);
 // specialised), k_front5 (4096, wave-specialised); fused_supported / launch_fused dispatch by N
 bool fused_supported(int N);
 hipError_t launch_fused(int N, const FrontArgs& a, hipStream_t s);
-hipError_t launch_front(int N, const FrontArgs& a, hipStream_t s);   // N = 128 / 256 (k_front.hip)
-hipError_t launch_front3(int N, const FrontArgs& a, hipStream_t s);  // N = 512 / 1024 / 2048 (k_front3.hip)
+// N = 512 / 1024 / 2048: k_front3.hip is built once per N and instantiates that one
+template <int N>
+hipError_t launch_front3(const FrontArgs& a, hipStream_t s);
 hipError_t launch_front5(const FrontArgs& a, hipStream_t s);         // N = 4096 (k_front5.hip)
 int64_t front_hist_samples(int N);  // ADC history the fused kernel reads before a chunk
 

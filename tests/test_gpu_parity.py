@@ -189,6 +189,21 @@ def test_chain_parity(gpu, C, S, splits, seed, front):
     compare(case, thr, splits or [0, S], front=front.replace('-noacc', ''), acc=acc)
 
 
+@pytest.mark.parametrize('acc', [True, False])
+@pytest.mark.parametrize('C,S,seed', [
+    # test_chain_parity's geometries, the ones its case cache still holds first
+    (2048, 2 ** 20, 6), (1024, 2 ** 20, 5), (512, 2 ** 19, 7), (64, 2 ** 16, 1), (128, 2 ** 17, 2), (256, 2 ** 18, 3),
+])
+def test_fused_short_calls_and_run_tails(gpu, C, S, seed, acc):
+    """The fused front ends' shared run geometry and hop loader at their smallest shapes: calls of
+    2, 6 and 66 frames, then the rest. A 2-frame call is shorter than one iteration at N = 512 / 1024
+    (4 frames per iteration) and reads everything but its own hops from the carried ADC history; a
+    66-frame call is one full 64-frame run plus a 2-frame tail run at every geometry."""
+    N = 2 * C
+    case, thr = cached_case(C, S, seed, max(1.0, S / N / 400))
+    compare(case, thr, [0, N, 4 * N, 37 * N, S], acc=acc)
+
+
 @pytest.mark.parametrize('mode', [0, 1, 2])
 def test_baseline_modes(gpu, mode):
     C, S = 256, 2 ** 18

@@ -4,7 +4,7 @@
     python tools/kbench.py [--log2-samples 28] [--rounds 5] [--baseline svf] variantA.so variantB.so[:split] ...
 Each variant gets its own context on the same synthetic 1024-channel input (bench.py's feedline,
 calibrated); per round every variant processes the input once; per-kernel HIP-event times are
-reported as median / min over rounds.
+reported as median / min / max over rounds (max - min of a duplicated library is the run's own spread).
 """
 import argparse
 import json
@@ -129,7 +129,7 @@ def main():
                 times[path].setdefault('wall', []).append((time.perf_counter() - t0) * 1e3)
     out = {}
     for path in args.libs:
-        out[os.path.basename(path).replace('.so', '')] = {k: dict(median=float(np.median(v)), min=float(np.min(v)))
+        out[os.path.basename(path).replace('.so', '')] = {k: dict(median=float(np.median(v)), min=float(np.min(v)), max=float(np.max(v)))
                                        for k, v in times[path].items()}
     print(json.dumps(dict(samples=S, channels=C, rounds=args.rounds, kernels_ms=out), indent=1))
 

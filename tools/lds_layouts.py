@@ -11,14 +11,11 @@ A layout maps float2 index i to i + (i >> SH) * MUL. Two properties are checked 
 
     python tools/lds_layouts.py          # report for the kernels' plans
 """
-import itertools
-
 PTS = 8
-FRONT_PLANS = {128: [8, 4, 4], 256: [8, 8, 4], 512: [8, 4, 4, 4], 1024: [8, 8, 4, 4], 2048: [8, 8, 8, 4]}
+FRONT_PLANS = {128: [8, 4, 4], 256: [8, 8, 4]}   # k_front runs the three-pass plans only
 CHAN_PLANS = {128: [8, 4, 4], 256: [8, 8, 4], 512: [8, 8, 8], 1024: [8, 8, 4, 4], 2048: [8, 8, 8, 4],
               4096: [8, 8, 8, 8]}
 PAD16 = (4, 1)
-PADB = (5, 4)
 
 
 def pad(i, p):
@@ -102,14 +99,7 @@ def exchange(N, Rw, NS, Rr, p):
 def front_exchanges(N):
     """Exchanges of k_front<N>: (name, write radix, NS, read radix or None, layout)."""
     R = FRONT_PLANS[N]
-    padb = PADB
-    ex = [('A', R[0], 1, R[1], PAD16)]
-    if len(R) == 4:
-        ex.append(('B', R[1], R[0], R[2], padb))
-        ex.append(('C', R[2], R[0] * R[1], None, PAD16))
-    else:
-        ex.append(('C', R[1], R[0], None, PAD16))
-    return ex
+    return [('A', R[0], 1, R[1], PAD16), ('C', R[1], R[0], None, PAD16)]
 
 
 def chan_exchanges(N):
@@ -128,13 +118,6 @@ def main():
     for N in sorted(CHAN_PLANS):
         for name, Rw, NS, Rr, p in chan_exchanges(N):
             print('k_channelize<%d> %s' % (N, name), 'linear/write/read', exchange(N, Rw, NS, Rr, p))
-    # candidate search for exchange B at N = 2048
-    best = []
-    for sh, mul in itertools.product(range(3, 8), range(1, 9)):
-        lin, wc, rc = exchange(2048, 8, 8, 8, (sh, mul))
-        if lin:
-            best.append((max(wc, 48) + rc, wc, rc, (sh, mul)))
-    print('exchange B candidates (cost, write, read, layout):', sorted(best)[:5])
 
 
 if __name__ == '__main__':
