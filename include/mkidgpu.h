@@ -338,6 +338,57 @@ int mkid_capture_pulses_counted(mkid_ctx* ctx, const float* d_phase, int64_t row
                                 const uint64_t* d_events, const int64_t* d_count, int64_t cap,
                                 float* d_records, int64_t* d_stamps, int32_t* d_info);
 
+/* Every channel's template and pulse filter from a record bank in one call: the bank that
+ * mkid_capture_pulses filled (or any bank of that layout) becomes the table that
+ * mkid_set_pulse_filter takes, and optionally every channel's template and noise PSD.
+ *   - Device pointers only; asynchronous on the context stream. Once the workspace exists the call
+ *     makes no device-to-host copy and no stream synchronisation (growing the workspace allocates,
+ *     synchronises once and moves the new buffer in). I1m/Q1m, pm/pdev, count1, count, pstart and
+ *     flag are produced and consumed on the device.
+ *   - IQ mode (d_Q != NULL): rows [0, ready_c) of d_I[c], d_Q[c] ([Cb][R][2000] float32) go through
+ *     exactly mkid_make_template and then mkid_optimal_filter(pre, ncoeff): template, noise, every
+ *     info field and coeff = (float) of the float64 weights are bit-identical to those two calls on
+ *     that channel's set, the reference's double re-reference of the first 1000 pulses and the
+ *     pass-1 cap of 1000 pulses included.
+ *   - Phase mode (d_Q == NULL): d_I holds phase records (rad); the same pipeline runs on
+ *     I = cosf(sign phi), Q = sinf(sign phi), formed as the records are loaded (no I/Q copy of the
+ *     bank is made).
+ *   - ready_c = d_ready[c * ready_stride] clamped to 0..R (ready_stride 2 reads the ready column of a
+ *     capture d_info, 1 a plain list). A channel is worked on iff ready_c >= max(min_records, 1).
+ *   - d_result[c].status: 0 used; 1 below min_records; 2 no pulse passed pass 1; 3 none passed pass
+ *     2. Where status != 0 the channel's rows of d_coeff, d_templates and d_noise keep the bits they
+ *     had (the caller pre-fills its fallback), flag = pstart = -1 and count = 0; count1, pm and pdev
+ *     are what pass 1 found (status 2, 3) or 0 (status 1).
+ *   - The bank and d_ready are never written; rows at or beyond ready_c and the other columns of
+ *     d_ready are never read.
+ *   - A channel's outputs depend on its own records and pre / ncoeff / sign only: not on its index,
+ *     its neighbours, Cb, R or group.
+ *   - The workspace is bounded by a fixed byte budget (256 MiB, unless one channel alone needs
+ *     more), not by Cb R: channels are worked on in groups of `group` (0: as many as the budget
+ *     holds; a larger request is cut to that).
+ *   - MKID_E_ARG before any launch: a null required pointer, length != 2000, Cb < 1, R < 1, pre
+ *     outside 10..2000, ncoeff outside 1..800, ready_stride < 1, group < 0, and in phase mode a
+ *     sign that is zero or not finite. Not timed (no MKID_K_ id). */
+typedef struct mkid_bank_cfg {
+    int32_t n_channels;    /* Cb: channels of the bank (need not equal the context's C)      */
+    int32_t max_per_ch;    /* R: record stride of the bank                                   */
+    int32_t length;        /* rows per record; must be 2000 (MKID_E_ARG otherwise)           */
+    int32_t min_records;   /* a channel is worked on iff ready >= max(min_records, 1)        */
+    int32_t pre, ncoeff;   /* as mkid_optimal_filter: 10 <= pre <= 2000, 1 <= ncoeff <= 800  */
+    int32_t ready_stride;  /* int32 stride of d_ready: 2 for a capture d_info, 1 for a plain list */
+    int32_t group;         /* channels worked on per pass; 0 = as many as the workspace budget holds */
+    float   sign;          /* phase mode only: I = cos(sign*phi), Q = sin(sign*phi)          */
+} mkid_bank_cfg;
+typedef struct mkid_bank_result {   /* one per channel, on the device */
+    double count, count1, pm, pdev;
+    int32_t flag, pstart;
+    int32_t status;        /* 0 used; 1 below min_records; 2 no pulse passed pass 1; 3 none passed pass 2 */
+    int32_t ready;         /* the record count used (d_ready clamped to 0..R) */
+} mkid_bank_result;
+int mkid_bank_filters(mkid_ctx* ctx, const float* d_I, const float* d_Q, const int32_t* d_ready,
+                      const mkid_bank_cfg* cfg, double* d_templates, double* d_noise, float* d_coeff,
+                      mkid_bank_result* d_result);
+
 /* Kernel timing with HIP events on the context stream (for bench roofline numbers). */
 #define MKID_K_CHANNELIZE 0
 #define MKID_K_FIR_PHASE 1

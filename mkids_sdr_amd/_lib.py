@@ -57,6 +57,21 @@ class TemplateInfo(ctypes.Structure):
                 ('pdev', ctypes.c_double), ('flag', ctypes.c_int32), ('pstart', ctypes.c_int32)]
 
 
+class BankCfg(ctypes.Structure):
+    _fields_ = [('n_channels', ctypes.c_int32), ('max_per_ch', ctypes.c_int32), ('length', ctypes.c_int32),
+                ('min_records', ctypes.c_int32), ('pre', ctypes.c_int32), ('ncoeff', ctypes.c_int32),
+                ('ready_stride', ctypes.c_int32), ('group', ctypes.c_int32), ('sign', ctypes.c_float)]
+
+
+class BankResult(ctypes.Structure):
+    _fields_ = [('count', ctypes.c_double), ('count1', ctypes.c_double), ('pm', ctypes.c_double),
+                ('pdev', ctypes.c_double), ('flag', ctypes.c_int32), ('pstart', ctypes.c_int32),
+                ('status', ctypes.c_int32), ('ready', ctypes.c_int32)]
+
+
+BANK_USED, BANK_FEW_RECORDS, BANK_NONE_PASS1, BANK_NONE_PASS2 = range(4)
+
+
 class SynthTone(ctypes.Structure):
     _fields_ = [('amp', ctypes.c_float), ('phase0', ctypes.c_float),
                 ('freq_index', ctypes.c_int32), ('pad', ctypes.c_int32)]
@@ -103,6 +118,7 @@ _SIGS = {
     'mkid_replay_trigger': [P, P, I64, I64, I32, P, P, I32, P],
     'mkid_make_template': [P, P, P, I64, P, P, P],
     'mkid_optimal_filter': [P, P, P, I32, I32, P],
+    'mkid_bank_filters': [P, P, P, P, P, P, P, P, P],
     'mkid_set_pulse_filter': [P, P, I32, I32, I32],
     'mkid_pulse_heights': [P, P, I64, I64, P, I64, P],
     'mkid_pulse_heights_counted': [P, P, I64, I64, P, P, I64, P],

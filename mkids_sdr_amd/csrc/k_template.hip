@@ -17,6 +17,12 @@
 // numpy's pairwise float64 summation. Results agree with oracle/template_ref.py to float rounding
 // (atan2f and the least-squares fit differ in the last bits), and every accept/skip decision away
 // from a threshold is identical (tests/test_template.py, tests/test_gpu_template.py).
+//
+// Every stage is a device function with two callers: the single-set kernels k_tpl_* (one
+// resonator's set, scalars through the host: mkid_make_template, mkid_optimal_filter) and the bank
+// kernels k_bank_* (mkid_bank_filters: a group of channels of a record bank per launch, scalars in
+// device tables, I/Q or phase records read where they lie). In I/Q mode the bank path gives the
+// single path's bits (tests/test_bank_filters.py); DESIGN.md §5.7 has the layout.
 #include "mkid_internal.h"
 
 namespace mkid {
@@ -146,10 +152,51 @@ struct TplArgs {
     int pass;
 };
 
-// One pulse: prep (re-reference, phase, unwrap, baseline) then the pass's selection.
-__global__ __launch_bounds__(kTB) void k_tpl_pulse(TplArgs a) {
-    const int64_t j = blockIdx.x;
-    if (j >= a.P) return;
+// One pulse as its workgroup sees it: the scalars of its set and its own slots of the set's tables.
+struct TplPulse {
+    float I1m, Q1m;
+    const double* tP;    // pass-1 template (pass 2)
+    double pm, pdev;     // pass-1 peak statistics (pass 2)
+    double* row;         // [2000]
+    double* nrow;        // [800] (pass 2)
+    int32_t* accept;
+    double* peak;        // pass 1
+    int32_t* appended;   // pass 1
+    int pass;
+    int nref;            // re-references before the phase: 1, or 2 where pass 2 meets a pulse that
+                         // pass 1 re-referenced already and whose source was left as it was
+};
+
+// Where a pulse's samples come from. The single-set kernels read a work copy and write the
+// re-referenced samples back (the reference edits its table); the bank kernels read the caller's
+// records, I/Q or phase, and write nothing back.
+struct SrcWorkCopy {
+    float* I;
+    float* Q;
+    __device__ __forceinline__ void load(int t, float& i, float& q) const { i = I[t]; q = Q[t]; }
+    __device__ __forceinline__ void store(int t, float i, float q) const { I[t] = i; Q[t] = q; }
+};
+// I = cos(sign phi), Q = sin(sign phi), float32: template.iq_from_phase on the device
+__device__ __forceinline__ void phase_iq(float sign, float phi, float& i, float& q) {
+    const float a = sign * phi;
+    i = cosf(a);
+    q = sinf(a);
+}
+struct SrcBank {
+    const float* I;      // this pulse's record: I, or phase (rad) where Q is null
+    const float* Q;
+    float sign;
+    __device__ __forceinline__ void load(int t, float& i, float& q) const {
+        if (Q) { i = I[t]; q = Q[t]; }
+        else phase_iq(sign, I[t], i, q);
+    }
+    __device__ __forceinline__ void store(int, float, float) const {}
+};
+
+// One pulse: prep (re-reference, phase, unwrap, baseline) then the pass's selection. The one
+// definition behind k_tpl_pulse (single set) and k_bank_pulse (record bank).
+template <typename Src>
+__device__ __forceinline__ void tpl_pulse(const Src src, const TplPulse a) {
     __shared__ float sI[kTN], sQ[kTN], sP2[kTN];
     __shared__ double sP3[kTN];
     __shared__ double sA[600];
@@ -157,23 +204,22 @@ __global__ __launch_bounds__(kTB) void k_tpl_pulse(TplArgs a) {
     __shared__ int redi[kTB];
     __shared__ double s_fit[2];
     __shared__ int s_bad;
-    float* gI = a.I + j * kTN;
-    float* gQ = a.Q + j * kTN;
     const int t0 = threadIdx.x;
-    for (int t = t0; t < kTN; t += kTB) { sI[t] = gI[t]; sQ[t] = gQ[t]; }
+    for (int t = t0; t < kTN; t += kTB) src.load(t, sI[t], sQ[t]);
     __syncthreads();
-    // I += I1m - median(I[1:900]) (float32), written back: the reference edits its table
-    const float mI = wg_median([&](int i) { return sI[1 + i]; }, 899);
-    const float mQ = wg_median([&](int i) { return sQ[1 + i]; }, 899);
-    const float dI = a.I1m - mI, dQ = a.Q1m - mQ;
-    for (int t = t0; t < kTN; t += kTB) {
-        sI[t] += dI;
-        sQ[t] += dQ;
-        gI[t] = sI[t];
-        gQ[t] = sQ[t];
-        sP2[t] = atan2f(sQ[t] - 0.0f, sI[t] - 0.0f);  // P1 (xc = yc = 0, pulses.py:274-275)
+    for (int r = 0; r < a.nref; ++r) {
+        // I += I1m - median(I[1:900]) (float32), written back: the reference edits its table
+        const float mI = wg_median([&](int i) { return sI[1 + i]; }, 899);
+        const float mQ = wg_median([&](int i) { return sQ[1 + i]; }, 899);
+        const float dI = a.I1m - mI, dQ = a.Q1m - mQ;
+        for (int t = t0; t < kTN; t += kTB) {
+            sI[t] += dI;
+            sQ[t] += dQ;
+            src.store(t, sI[t], sQ[t]);
+            sP2[t] = atan2f(sQ[t] - 0.0f, sI[t] - 0.0f);  // P1 (xc = yc = 0, pulses.py:274-275)
+        }
+        __syncthreads();
     }
-    __syncthreads();
     // np.unwrap (float32: period 2pi, discont pi) + rad2deg, sequential like the reference's cumsum
     if (t0 == 0) {
         const float hi = 3.14159265358979311600f, per = 6.28318530717958623200f;
@@ -239,8 +285,8 @@ __global__ __launch_bounds__(kTB) void k_tpl_pulse(TplArgs a) {
     __syncthreads();
     if (s_bad) {
         if (t0 == 0) {
-            a.accept[j] = 0;
-            if (a.pass == 1) a.appended[j] = 0;
+            *a.accept = 0;
+            if (a.pass == 1) *a.appended = 0;
         }
         return;
     }
@@ -269,7 +315,7 @@ __global__ __launch_bounds__(kTB) void k_tpl_pulse(TplArgs a) {
         __syncthreads();
         for (int o = kTB / 2; o > 0; o >>= 1) { if (t0 < o) redi[t0] = min(redi[t0], redi[t0 + o]); __syncthreads(); }
         const int ploc = redi[0];
-        if (t0 == 0) { a.peaks[j] = peak; a.appended[j] = 1; }
+        if (t0 == 0) { *a.peak = peak; *a.appended = 1; }
         ok = !(peak < 15.0 || peak > 120.0) && !(ploc < 980 || ploc > 1020);
         shift = 1000 - ploc;
     } else {
@@ -302,10 +348,10 @@ __global__ __launch_bounds__(kTB) void k_tpl_pulse(TplArgs a) {
         ok = inr && !(peak < a.pm - 4.0 * a.pdev || peak > a.pm + 4.0 * a.pdev) && !(ploc < -30 || ploc > 30);
         shift = -ploc;
     }
-    if (t0 == 0) a.accept[j] = ok ? 1 : 0;
+    if (t0 == 0) *a.accept = ok ? 1 : 0;
     if (!ok) return;
     // row = roll(P3, shift) / max(P3)
-    double* row = a.rows + j * kTN;
+    double* row = a.row;
     for (int t = t0; t < kTN; t += kTB) {
         int src = t - shift;
         src %= kTN;
@@ -332,7 +378,7 @@ __global__ __launch_bounds__(kTB) void k_tpl_pulse(TplArgs a) {
             win[t] = sP3[src] * 0.017453292519943295;
         }
         __syncthreads();
-        double* nrow = a.nrows + j * kTNoise;
+        double* nrow = a.nrow;
         for (int f = t0; f < kTNoise; f += kTB) {
             double re = 0.0, im = 0.0;
             int ph = 0;
@@ -347,10 +393,17 @@ __global__ __launch_bounds__(kTB) void k_tpl_pulse(TplArgs a) {
     }
 }
 
+__global__ __launch_bounds__(kTB) void k_tpl_pulse(TplArgs a) {
+    const int64_t j = blockIdx.x;
+    if (j >= a.P) return;
+    tpl_pulse(SrcWorkCopy{a.I + j * kTN, a.Q + j * kTN},
+              TplPulse{a.I1m, a.Q1m, a.tP, a.pm, a.pdev, a.rows + j * kTN, a.nrows + j * kTNoise, a.accept + j,
+                       a.peaks + j, a.appended + j, a.pass, 1});
+}
+
 // column sums over accepted rows in pulse order; out[t] = sum / count
-__global__ void k_tpl_colsum(const double* rows, const int32_t* accept, int64_t P, int width, double* out,
-                             double* count) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void tpl_colsum(const double* rows, const int32_t* accept, int64_t P, int width, int t,
+                                           double* out, double* count) {
     if (t >= width) return;
     double s = 0.0, n = 0.0;
     for (int64_t j = 0; j < P; ++j)
@@ -358,20 +411,30 @@ __global__ void k_tpl_colsum(const double* rows, const int32_t* accept, int64_t 
     out[t] = s / n;
     if (t == 0) *count = n;
 }
-
-// global reference medians I1m, Q1m over pulses [0, min(P,100)) x samples [0, 900)
-__global__ void k_tpl_refmed(const float* I, const float* Q, int64_t P, float* out) {
-    const int np = (int)(P < 100 ? P : 100);
-    const int n = np * 900;
-    const float mi = wg_median([&](int i) { return I[(int64_t)(i / 900) * kTN + i % 900]; }, n);
-    const float mq = wg_median([&](int i) { return Q[(int64_t)(i / 900) * kTN + i % 900]; }, n);
-    if (threadIdx.x == 0) { out[0] = mi; out[1] = mq; }
+__global__ void k_tpl_colsum(const double* rows, const int32_t* accept, int64_t P, int width, double* out,
+                             double* count) {
+    tpl_colsum(rows, accept, P, width, blockIdx.x * blockDim.x + threadIdx.x, out, count);
 }
 
-// pm, pdev: median / std of appended pass-1 peaks > 15 (pulses.py:334-336), in pulse order
-__global__ void k_tpl_peakstats(const double* peaks, const int32_t* appended, int64_t P, double* out,
-                                double* scratch) {
-    if (threadIdx.x != 0) return;
+// global reference medians I1m, Q1m over pulses [0, min(P,100)) x samples [0, 900); get(pulse,
+// sample, i, q) reads one sample of the set
+template <typename G>
+__device__ __forceinline__ void tpl_refmed(G get, int64_t P, float* out) {
+    const int np = (int)(P < 100 ? P : 100);
+    const int n = np * 900;
+    const float mi = wg_median([&](int k) { float i, q; get(k / 900, k % 900, i, q); return i; }, n);
+    const float mq = wg_median([&](int k) { float i, q; get(k / 900, k % 900, i, q); return q; }, n);
+    if (threadIdx.x == 0) { out[0] = mi; out[1] = mq; }
+}
+__global__ void k_tpl_refmed(const float* I, const float* Q, int64_t P, float* out) {
+    tpl_refmed([&](int p, int t, float& i, float& q) { i = I[(int64_t)p * kTN + t]; q = Q[(int64_t)p * kTN + t]; },
+               P, out);
+}
+
+// pm, pdev: median / std of appended pass-1 peaks > 15 (pulses.py:334-336), in pulse order; one
+// thread's work
+__device__ void tpl_peakstats(const double* peaks, const int32_t* appended, int64_t P, double* out,
+                              double* scratch) {
     int n = 0;
     for (int64_t j = 0; j < P; ++j)
         if (appended[j] && peaks[j] > 15.0) scratch[n++] = peaks[j];
@@ -388,11 +451,16 @@ __global__ void k_tpl_peakstats(const double* peaks, const int32_t* appended, in
     }
     out[0] = (n & 1) ? scratch[n / 2] : (scratch[n / 2 - 1] + scratch[n / 2]) / 2.0;
 }
+__global__ void k_tpl_peakstats(const double* peaks, const int32_t* appended, int64_t P, double* out,
+                                double* scratch) {
+    if (threadIdx.x == 0) tpl_peakstats(peaks, appended, P, out, scratch);
+}
 
 // near-optimal filter: s = deg2rad(template[pk-pre : pk-pre+800]); H = S / J, H[0] = 0;
-// g = real(ifft(H)) (correlation weights), g /= g.s; coeff = g[pre-10 : pre-10+ncoeff]
-__global__ void k_tpl_optfilt(const double* tpl, const double* noise, int pre, int ncoeff, double* coeff,
-                              double* work) {
+// g = real(ifft(H)) (correlation weights), g /= g.s; coeff = g[pre-10 : pre-10+ncoeff]. By a whole
+// workgroup of kTB threads; returns the first index of the template's maximum (every thread).
+__device__ __forceinline__ int tpl_optfilt(const double* tpl, const double* noise, int pre, int ncoeff,
+                                           double* coeff, double* work) {
     __shared__ double s[kTNoise];
     __shared__ double red[kTB];
     __shared__ int redi[kTB];
@@ -411,7 +479,8 @@ __global__ void k_tpl_optfilt(const double* tpl, const double* noise, int pre, i
         }
         __syncthreads();
     }
-    const int p0 = redi[0] - pre;
+    const int pk = redi[0];
+    const int p0 = pk - pre;
     for (int t = t0; t < kTNoise; t += kTB) {
         const int i = p0 + t;
         s[t] = (i >= 0 && i < kTN) ? tpl[i] * 0.017453292519943295 : 0.0;
@@ -464,6 +533,125 @@ __global__ void k_tpl_optfilt(const double* tpl, const double* noise, int pre, i
         const int m = k0 + i;
         coeff[i] = (m >= 0 && m < kTNoise) ? g[m] / norm : 0.0;
     }
+    return pk;
+}
+__global__ void k_tpl_optfilt(const double* tpl, const double* noise, int pre, int ncoeff, double* coeff,
+                              double* work) {
+    tpl_optfilt(tpl, noise, pre, ncoeff, coeff, work);
+}
+
+// ---- the record bank: the same stages for every channel of a group at once -----------------------
+// Channel b of the group (caller's channel c0 + b) owns slot b of every workspace table; its
+// scalars (ready count, status, I1m/Q1m, pm/pdev, counts) stay in those tables from kernel to kernel.
+
+__device__ __forceinline__ SrcBank bank_record(const BankArgs& a, int b, int64_t j) {
+    const int64_t o = (((int64_t)(a.c0 + b)) * a.R + j) * kTN;
+    return SrcBank{a.I + o, a.Q ? a.Q + o : nullptr, a.sign};
+}
+
+// ready and status of every channel, then I1m, Q1m of the channels worked on
+__global__ __launch_bounds__(1024) void k_bank_refmed(BankArgs a) {
+    const int b = blockIdx.x;
+    int32_t rd = a.ready[(int64_t)(a.c0 + b) * a.ready_stride];
+    rd = rd < 0 ? 0 : (rd > a.R ? a.R : rd);
+    const int32_t need = a.min_records > 1 ? a.min_records : 1;
+    const int32_t st = rd >= need ? 0 : 1;
+    if (threadIdx.x == 0) { a.nready[b] = rd; a.status[b] = st; }
+    if (st) return;
+    tpl_refmed([&](int p, int t, float& i, float& q) { bank_record(a, b, p).load(t, i, q); }, rd,
+               a.refmed + 2 * b);
+}
+
+__global__ __launch_bounds__(kTB) void k_bank_pulse(BankArgs a, int pass) {
+    const int b = blockIdx.y;
+    const int j = blockIdx.x;
+    if (a.status[b]) return;
+    const int P = a.nready[b];
+    if (j >= (pass == 1 && P > 1000 ? 1000 : P)) return;
+    const int64_t s = (int64_t)b * a.R + j;
+    const double* st = a.stats + 8 * b;
+    tpl_pulse(bank_record(a, b, j),
+              TplPulse{a.refmed[2 * b], a.refmed[2 * b + 1], a.tP + (int64_t)b * kTN, st[0], st[1],
+                       a.rows + s * kTN, a.nrows + s * kTNoise, a.accept + s, a.peaks + s, a.appended + s, pass,
+                       pass == 2 && j < 1000 ? 2 : 1});
+}
+
+// which: 0 pass-1 rows -> tP, count1; 1 pass-2 rows -> tPf, count; 2 noise rows -> noise, count
+__global__ void k_bank_colsum(BankArgs a, int which) {
+    const int b = blockIdx.y;
+    if (a.status[b]) return;
+    int64_t P = a.nready[b];
+    if (which == 0 && P > 1000) P = 1000;
+    const int width = which == 2 ? kTNoise : kTN;
+    const double* rows = which == 2 ? a.nrows + (int64_t)b * a.R * kTNoise : a.rows + (int64_t)b * a.R * kTN;
+    double* out = which == 0 ? a.tP + (int64_t)b * kTN
+                             : (which == 1 ? a.tPf + (int64_t)b * kTN : a.noise + (int64_t)b * kTNoise);
+    tpl_colsum(rows, a.accept + (int64_t)b * a.R, P, width, blockIdx.x * blockDim.x + threadIdx.x, out,
+               a.stats + 8 * b + (which == 0 ? 3 : 4));
+}
+
+// pm, pdev; then the first of the host's two decisions: no pulse passed pass 1
+__global__ void k_bank_peakstats(BankArgs a) {
+    const int b = blockIdx.x;
+    if (threadIdx.x != 0 || a.status[b]) return;
+    const int64_t P = a.nready[b] > 1000 ? 1000 : a.nready[b];
+    double* st = a.stats + 8 * b;
+    tpl_peakstats(a.peaks + (int64_t)b * a.R, a.appended + (int64_t)b * a.R, P, st,
+                  a.scratch + (int64_t)b * (2 * (int64_t)a.R + 8));
+    if (!(st[3] > 0)) a.status[b] = 2;
+}
+
+// the second decision (none passed pass 2), pstart and flag, the filter, and the caller's rows
+__global__ __launch_bounds__(kTB) void k_bank_finish(BankArgs a) {
+    const int b = blockIdx.x;
+    const int64_t c = a.c0 + b;
+    const int t0 = threadIdx.x;
+    const double* st = a.stats + 8 * b;
+    int status = a.status[b];
+    if (status == 0 && !(st[4] > 0)) status = 3;
+    if (status) {
+        if (t0 == 0) {
+            mkid_bank_result r{};
+            if (status >= 2) { r.count1 = st[3]; r.pm = st[0]; r.pdev = st[1]; }
+            r.flag = r.pstart = -1;
+            r.status = status;
+            r.ready = a.nready[b];
+            a.result[c] = r;
+        }
+        return;
+    }
+    const double* tpl = a.tPf + (int64_t)b * kTN;
+    const double* noise = a.noise + (int64_t)b * kTNoise;
+    double* co = a.coeff + (int64_t)b * kTNoise;
+    const int pk = tpl_optfilt(tpl, noise, a.pre, a.ncoeff, co, a.work + (int64_t)b * 3 * kTNoise);
+    for (int i = t0; i < a.ncoeff; i += kTB) a.out_coeff[c * a.ncoeff + i] = (float)co[i];  // own writes
+    if (a.out_tpl)
+        for (int t = t0; t < kTN; t += kTB) a.out_tpl[c * kTN + t] = tpl[t];
+    if (a.out_noise)
+        for (int t = t0; t < kTNoise; t += kTB) a.out_noise[c * kTNoise + t] = noise[t];
+    if (t0 == 0) {
+        mkid_bank_result r{};
+        r.count = st[4]; r.count1 = st[3]; r.pm = st[0]; r.pdev = st[1];
+        r.flag = (st[4] < 500 || st[0] < 10 || st[0] > 150) ? 1 : 0;
+        // the host's scan `if (t[i] > t[ps]) ps = i` from ps = 0: the first maximum; 0 when t[0] is NaN
+        r.pstart = (pk >= kTN || tpl[0] != tpl[0]) ? 0 : pk;
+        r.status = 0;
+        r.ready = a.nready[b];
+        a.result[c] = r;
+    }
+}
+
+hipError_t launch_bank_filters(const BankArgs& a, hipStream_t s) {
+    const unsigned g = (unsigned)a.g, R = (unsigned)a.R, R1 = R < 1000 ? R : 1000;
+    hipLaunchKernelGGL(k_bank_refmed, dim3(g), dim3(1024), 0, s, a);
+    hipLaunchKernelGGL(k_bank_pulse, dim3(R1, g), dim3(kTB), 0, s, a, 1);
+    hipLaunchKernelGGL(k_bank_colsum, dim3((kTN + 255) / 256, g), dim3(256), 0, s, a, 0);
+    hipLaunchKernelGGL(k_bank_peakstats, dim3(g), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(k_bank_pulse, dim3(R, g), dim3(kTB), 0, s, a, 2);
+    hipLaunchKernelGGL(k_bank_colsum, dim3((kTN + 255) / 256, g), dim3(256), 0, s, a, 1);
+    hipLaunchKernelGGL(k_bank_colsum, dim3((kTNoise + 255) / 256, g), dim3(256), 0, s, a, 2);
+    hipLaunchKernelGGL(k_bank_finish, dim3(g), dim3(kTB), 0, s, a);
+    return hipGetLastError();
 }
 
 hipError_t launch_make_template(float* I, float* Q, int64_t P, double* rows, double* nrows, int32_t* accept,

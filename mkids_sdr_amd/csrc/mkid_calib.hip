@@ -1,7 +1,10 @@
 // C ABI of libmkidgpu.so (include/mkidgpu.h): calibration and pulse analysis — replay trigger,
-// template, optimal filter, pulse heights, pulse capture, the synthetic ADC stream, stream copy.
+// template, optimal filter, bank filters, pulse heights, pulse capture, the synthetic ADC stream,
+// stream copy.
 // Every entry point that replaces buffers of the context allocates the new ones into locals and
 // moves them in, with the scalars that describe them, only once every allocation has succeeded.
+#include <cmath>
+
 #include "mkid_ctx.h"
 
 using namespace mkid;
@@ -98,6 +101,41 @@ int mkid_optimal_filter(mkid_ctx* c, const double* d_template, const double* d_n
     HIPCHK(c, work.alloc(3 * 800));
     HIPCHK(c, launch_optimal_filter(d_template, d_noise, pre, ncoeff, d_coeff, work.get(), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return MKID_OK;
+}
+
+int mkid_bank_filters(mkid_ctx* c, const float* d_I, const float* d_Q, const int32_t* d_ready,
+                      const mkid_bank_cfg* bc, double* d_templates, double* d_noise, float* d_coeff,
+                      mkid_bank_result* d_result) {
+    if (!c || !d_I || !d_ready || !bc || !d_coeff || !d_result) return MKID_E_ARG;
+    if (bc->length != 2000) FAIL(c, MKID_E_ARG, "bank_filters: records must be 2000 rows long");
+    if (bc->n_channels < 1 || bc->max_per_ch < 1) FAIL(c, MKID_E_ARG, "bank_filters: need channels and records");
+    if (bc->pre < 10 || bc->pre > 2000 || bc->ncoeff <= 0 || bc->ncoeff > 800)
+        FAIL(c, MKID_E_ARG, "bank_filters: bad pre/ncoeff");
+    if (bc->ready_stride < 1 || bc->group < 0) FAIL(c, MKID_E_ARG, "bank_filters: bad ready_stride/group");
+    if (!d_Q && !(std::isfinite(bc->sign) && bc->sign != 0.0f))
+        FAIL(c, MKID_E_ARG, "bank_filters: phase mode needs a finite, non-zero sign");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int32_t Cb = bc->n_channels;
+    const plan::BankWs w = plan::plan_bank(Cb, bc->max_per_ch, plan::kBankBudget, bc->group);
+    if ((size_t)w.bytes > c->bankws_n) {   // grow the workspace
+        DevBuf<char> ws;
+        HIPCHK(c, ws.alloc((size_t)w.bytes));
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // an earlier call may still use the old one
+        c->d_bankws = std::move(ws), c->bankws_n = (size_t)w.bytes;
+    }
+    char* p = c->d_bankws.get();
+    BankArgs a{d_I, d_Q, d_ready, d_templates, d_noise, d_coeff, d_result,
+               (double*)(p + w.rows), (double*)(p + w.nrows), (double*)(p + w.peaks), (double*)(p + w.scratch),
+               (double*)(p + w.tP), (double*)(p + w.tPf), (double*)(p + w.noise), (double*)(p + w.stats),
+               (double*)(p + w.work), (double*)(p + w.coeff), (float*)(p + w.refmed), (int32_t*)(p + w.accept),
+               (int32_t*)(p + w.appended), (int32_t*)(p + w.status), (int32_t*)(p + w.nready),
+               0, 0, bc->max_per_ch, bc->ready_stride, bc->min_records, bc->pre, bc->ncoeff, bc->sign};
+    for (int64_t c0 = 0; c0 < Cb; c0 += w.group) {   // the stream orders the groups' use of the tables
+        a.c0 = (int32_t)c0;
+        a.g = (int32_t)std::min<int64_t>(w.group, Cb - c0);
+        HIPCHK(c, launch_bank_filters(a, c->stream));
+    }
     return MKID_OK;
 }
 

@@ -193,6 +193,9 @@ struct mkid_ctx : CtxHandles {
     DevBuf<uint32_t> d_rflags;
     DevBuf<double> d_rmeans;
     size_t rflags_n = 0, rmeans_n = 0;
+    // mkid_bank_filters workspace (lazy, grown on demand; plan::plan_bank carves it)
+    DevBuf<char> d_bankws;
+    size_t bankws_n = 0;
     // host-API staging (lazy)
     DevBuf<uint32_t> d_in;
     DevBuf<float> d_phase_ws;

@@ -223,6 +223,36 @@ hipError_t launch_make_template(float* I, float* Q, int64_t P, double* rows, dou
 hipError_t launch_optimal_filter(const double* tpl, const double* noise, int pre, int ncoeff, double* coeff,
                                  double* work, hipStream_t s);
 
+// mkid_bank_filters (k_template.hip): one group of g channels, c0 .. c0 + g - 1, of the caller's
+// bank. The workspace tables hold one slot per channel of the group (plan::BankWs gives their sizes).
+struct BankArgs {
+    const float* I;          // [Cb][R][2000] records: I, or phase (rad) where Q is null
+    const float* Q;
+    const int32_t* ready;    // [Cb * ready_stride]
+    double* out_tpl;         // [Cb][2000], nullable
+    double* out_noise;       // [Cb][800], nullable
+    float* out_coeff;        // [Cb][ncoeff]
+    mkid_bank_result* result;  // [Cb]
+    double* rows;            // [g][R][2000]
+    double* nrows;           // [g][R][800]
+    double* peaks;           // [g][R]
+    double* scratch;         // [g][2 R + 8]
+    double* tP;              // [g][2000] pass-1 templates
+    double* tPf;             // [g][2000]
+    double* noise;           // [g][800]
+    double* stats;           // [g][8] {pm, pdev, peaks, count1, count}
+    double* work;            // [g][3][800]
+    double* coeff;           // [g][800] float64 weights
+    float* refmed;           // [g][2] I1m, Q1m
+    int32_t* accept;         // [g][R]
+    int32_t* appended;       // [g][R]
+    int32_t* status;         // [g]
+    int32_t* nready;         // [g] ready clamped to 0..R
+    int32_t c0, g, R, ready_stride, min_records, pre, ncoeff;
+    float sign;
+};
+hipError_t launch_bank_filters(const BankArgs& a, hipStream_t s);
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device), thread-safe: the
 // attribute is per device, and several contexts (devices, host threads) may launch concurrently.
 // `mask` is one static per kernel instantiation; the call is idempotent, so a race only repeats it.

@@ -284,5 +284,25 @@ int32_t rearm_level(int32_t thr, int32_t q8) {
     return (int32_t)((int64_t)thr - fl);
 }
 
+BankWs plan_bank(int64_t Cb, int64_t R, int64_t budget, int64_t want) {
+    // bytes per channel of each table, in the order of BankWs's offsets
+    const int64_t per[15] = {R * 2000 * 8, R * 800 * 8, R * 8,  (2 * R + 8) * 8, 2000 * 8, 2000 * 8, 800 * 8, 8 * 8,
+                             3 * 800 * 8,  800 * 8,     2 * 4,  R * 4,           R * 4,    4,        4};
+    BankWs w;
+    for (int64_t p : per) w.channel_bytes += p;
+    const int64_t slack = 15 * (kBankAlign - 1);   // at most this much padding, whatever the group
+    int64_t g = budget > slack ? (budget - slack) / w.channel_bytes : 0;
+    g = std::min(g, std::min(Cb, kBankMaxGroup));
+    if (want > 0) g = std::min(g, want);
+    w.group = std::max<int64_t>(g, 1);
+    int64_t* off[15] = {&w.rows, &w.nrows, &w.peaks, &w.scratch, &w.tP,       &w.tPf,    &w.noise, &w.stats,
+                        &w.work, &w.coeff, &w.refmed, &w.accept, &w.appended, &w.status, &w.nready};
+    for (int i = 0; i < 15; ++i) {
+        *off[i] = w.bytes;
+        w.bytes += (w.group * per[i] + kBankAlign - 1) / kBankAlign * kBankAlign;
+    }
+    return w;
+}
+
 }  // namespace plan
 }  // namespace mkid

@@ -2,7 +2,8 @@
 // AddressSanitizer / UndefinedBehaviorSanitizer (make -C mkids_sdr_amd/csrc asan; tools/plan_fuzz.cpp):
 // workspace sizing at context creation, the per-call trigger segmentation and its slot-table
 // geometry, the k_front3 select-slot order, the K1 tap quantisation, the merge of per-chunk packet
-// lists, the reference packet re-encode and the validity bookkeeping of a carried history. The host
+// lists, the reference packet re-encode, the validity bookkeeping of a carried history and the
+// grouping and workspace layout of mkid_bank_filters. The host
 // files mkid_api.hip, mkid_stream.hip and mkid_calib.hip are the only product callers.
 #pragma once
 #include <stdint.h>
@@ -85,6 +86,21 @@ struct Carry {
     void advance(int64_t j0, int64_t n) { rows = std::min(H, before(j0) + n), end = j0 + n; }   // n rows rolled in
     void drop() { end = -1, rows = 0; }
 };
+
+// Workspace of mkid_bank_filters: the channels of a bank are worked on `group` at a time, and the
+// group's tables (BankArgs, mkid_internal.h) are carved from one buffer of `bytes` bytes at the
+// byte offsets below, each a multiple of kBankAlign. group = max(1, min(Cb, kBankMaxGroup, the
+// channels `budget` holds, want if want > 0)): bytes <= budget whenever one channel fits, whatever
+// Cb and R are; groups c0 = 0, group, 2 group, ... of min(group, Cb - c0) channels cover the bank.
+constexpr int64_t kBankBudget = 256ll << 20;
+constexpr int64_t kBankAlign = 256;
+constexpr int64_t kBankMaxGroup = 65535;   // the group is a grid's y extent
+struct BankWs {
+    int64_t group = 0, bytes = 0, channel_bytes = 0;
+    int64_t rows = 0, nrows = 0, peaks = 0, scratch = 0, tP = 0, tPf = 0, noise = 0, stats = 0, work = 0,
+            coeff = 0, refmed = 0, accept = 0, appended = 0, status = 0, nready = 0;
+};
+BankWs plan_bank(int64_t Cb, int64_t R, int64_t budget, int64_t want = 0);
 
 // k_front3 select-slot order (mkid_api.hip / include/mkidgpu.h mkid_slot_order): out[slot] = channel
 void slot_order(const std::vector<int32_t>& bins, int C, std::vector<int16_t>& out);

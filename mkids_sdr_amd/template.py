@@ -107,6 +107,77 @@ def filters_from_bank(ch, bank, ncoeff=100, pre=100, min_records=20, fallback=No
     return out
 
 
+RESULT_DTYPE = np.dtype([('count', np.float64), ('count1', np.float64), ('pm', np.float64), ('pdev', np.float64),
+                         ('flag', np.int32), ('pstart', np.int32), ('status', np.int32), ('ready', np.int32)])
+
+
+def result_table(d_result):
+    """The device result table of `bank_filters` ([Cb][48] uint8) as a numpy record array with the
+    fields of mkid_bank_result."""
+    return d_result.cpu().numpy().view(RESULT_DTYPE).reshape(-1)
+
+
+def bank_filters(ch, I, Q, ready, *, pre=100, ncoeff=100, min_records=20, fallback=None, keep_templates=False,
+                 group=0, sign=-1.0, ready_stride=None, sync=True):
+    """mkid_bank_filters (include/mkidgpu.h) on device tensors: I, Q float32 [Cb][R][2000], or Q =
+    None and I holding phase records (rad); ready int32 [Cb] or a capture info [Cb][2]
+    (ready_stride defaults to its row length). Every channel with enough records gets its row of
+    coeff [Cb][ncoeff] float32; the others keep `fallback` ([Cb][ncoeff] or [ncoeff]; default zeros).
+    Returns dict(coeff, result) of device tensors (result: see `result_table`), plus templates
+    [Cb][2000] and noise [Cb][800] float64 with keep_templates (rows of unused channels are NaN).
+    Nothing passes through the host. sync=False leaves the call running on the context stream."""
+    import torch
+    if I.dim() != 3 or I.shape[2] != NPTS or I.dtype != torch.float32 or not I.is_contiguous():
+        raise ValueError('records must be contiguous float32 [Cb][R][2000]')
+    if Q is not None and (Q.shape != I.shape or Q.dtype != torch.float32 or not Q.is_contiguous()):
+        raise ValueError('Q must match I')
+    Cb, R = int(I.shape[0]), int(I.shape[1])
+    if ready.dtype != torch.int32 or not ready.is_contiguous() or ready.shape[0] != Cb:
+        raise ValueError('ready must be contiguous int32 [Cb] or [Cb][k]')
+    if ready_stride is None:
+        ready_stride = 1 if ready.dim() == 1 else int(ready.shape[1])
+    dev = I.device
+    coeff = torch.zeros((Cb, int(ncoeff)), dtype=torch.float32, device=dev)
+    if fallback is not None:
+        fb = fallback if hasattr(fallback, 'data_ptr') else torch.from_numpy(np.asarray(fallback, np.float32))
+        coeff[:] = fb.to(device=dev, dtype=torch.float32)
+    tpl = torch.full((Cb, NPTS), float('nan'), dtype=torch.float64, device=dev) if keep_templates else None
+    noise = torch.full((Cb, NNOISE), float('nan'), dtype=torch.float64, device=dev) if keep_templates else None
+    result = torch.zeros((Cb, ctypes.sizeof(_lib.BankResult)), dtype=torch.uint8, device=dev)
+    cfg = _lib.BankCfg(Cb, R, NPTS, int(min_records), int(pre), int(ncoeff), int(ready_stride), int(group),
+                       float(sign))
+    p = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+    torch.cuda.synchronize(dev)   # the tensors were made on torch's stream, the kernels run on the context's
+    ch._chk(ch._L.mkid_bank_filters(ch._h, p(I), p(Q), p(ready), ctypes.byref(cfg), p(tpl), p(noise), p(coeff),
+                                    p(result)))
+    if sync:
+        torch.cuda.synchronize(dev)
+    out = dict(coeff=coeff, result=result)
+    if keep_templates:
+        out.update(templates=tpl, noise=noise)
+    return out
+
+
+def filters_from_bank_device(ch, bank, ncoeff=100, pre=100, min_records=20, fallback=None, keep_templates=False):
+    """`filters_from_bank` in one device call: the bank's phase records go through
+    mkid_bank_filters in phase mode where they lie (ready read from the bank's info, no per-channel
+    host step), then the small outputs are copied once. Same arguments, same dict, plus status [C]
+    int32 (mkid_bank_result.status; used = status == 0)."""
+    records, _, info = bank
+    if records.shape[2] != NPTS:
+        raise ValueError('filters_from_bank_device needs records of %d rows (set_capture(length=%d))' % (NPTS, NPTS))
+    r = bank_filters(ch, records, None, info, pre=pre, ncoeff=ncoeff, min_records=min_records, fallback=fallback,
+                     keep_templates=keep_templates, sign=-1.0)
+    t = result_table(r['result'])
+    used = t['status'] == 0
+    out = dict(coeff=r['coeff'].cpu().numpy(), count=t['count'].copy(), flag=t['flag'].copy(),
+               pstart=t['pstart'].copy(), ready=t['ready'].copy(), used=used, status=t['status'].copy())
+    if keep_templates:
+        tp, nz = r['templates'].cpu().numpy(), r['noise'].cpu().numpy()
+        out['templates'] = {int(c): (tp[c], nz[c]) for c in np.flatnonzero(used)}
+    return out
+
+
 def matched_fir_taps(coeff, ntaps=26, sign=-1.0):
     """Firmware FIR taps from correlation weights: the ntaps-long window of largest energy,
     reversed into convolution order (f_j = sum_i a_i raw_{j-i}), scaled to max |a| = 2047/2048

@@ -350,6 +350,50 @@ static void fuzz_carry(int iters) {
     }
 }
 
+// plan_bank (mkid_bank_filters' workspace): group >= 1, the workspace within the budget whenever one
+// channel fits, the groups covering 0..Cb-1 once, and the tables' writes (one slot per channel of the
+// group, sizes of BankArgs in mkid_internal.h) replayed into a buffer of exactly the planned size
+static void fuzz_bank(int iters) {
+    for (int it = 0; it < iters; ++it) {
+        const int64_t Cb = rint_(0, 3) == 0 ? rint_(1, 4) : rint_(1, 100000);
+        const int64_t R = rint_(0, 3) == 0 ? rint_(1, 8) : (rint_(0, 5) == 0 ? rint_(1, 3000000) : rint_(1, 1200));
+        const int64_t budget = rint_(0, 4) == 0 ? rint_(0, 100000) : (rint_(0, 1) ? kBankBudget : rint_(1, 1ll << 32));
+        const int64_t want = rint_(0, 1) ? 0 : rint_(1, 2 * Cb);
+        const BankWs w = plan_bank(Cb, R, budget, want);
+        const BankWs one = plan_bank(1, R, budget, 0);
+        CHECK(w.group >= 1 && w.group <= Cb && w.group <= kBankMaxGroup, "group %lld of %lld", (long long)w.group,
+              (long long)Cb);
+        CHECK(want == 0 || w.group <= want, "group %lld above the request %lld", (long long)w.group, (long long)want);
+        CHECK(one.group == 1 && w.bytes >= one.bytes, "one channel: group %lld", (long long)one.group);
+        if (one.bytes <= budget)
+            CHECK(w.bytes <= budget, "bytes %lld over the budget %lld (Cb %lld R %lld)", (long long)w.bytes,
+                  (long long)budget, (long long)Cb, (long long)R);
+        else
+            CHECK(w.group == 1, "group %lld although one channel does not fit", (long long)w.group);
+        std::vector<int32_t> seen((size_t)Cb, 0);
+        for (int64_t c0 = 0; c0 < Cb; c0 += w.group)
+            for (int64_t b = 0; b < std::min(w.group, Cb - c0); ++b) ++seen[(size_t)(c0 + b)];
+        CHECK(std::all_of(seen.begin(), seen.end(), [](int32_t n) { return n == 1; }), "groups do not cover the bank once");
+        // table extents: offset + group * per-channel bytes, ascending, aligned, inside `bytes`
+        const int64_t off[15] = {w.rows, w.nrows, w.peaks, w.scratch, w.tP,       w.tPf,    w.noise, w.stats,
+                                 w.work, w.coeff, w.refmed, w.accept, w.appended, w.status, w.nready};
+        const int64_t per[15] = {R * 16000, R * 6400, R * 8, (2 * R + 8) * 8, 16000, 16000, 6400, 64,
+                                 19200,     6400,     8,     R * 4,           R * 4, 4,     4};
+        int64_t sum = 0;
+        for (int i = 0; i < 15; ++i) {
+            sum += per[i];
+            CHECK(off[i] % kBankAlign == 0 && off[i] + w.group * per[i] <= (i < 14 ? off[i + 1] : w.bytes),
+                  "table %d overlaps the next", i);
+        }
+        CHECK(off[0] == 0 && sum == w.channel_bytes, "channel bytes %lld, tables %lld", (long long)w.channel_bytes,
+              (long long)sum);
+        if (w.bytes <= (1 << 22)) {   // the last slot of every table, written
+            std::vector<char> buf((size_t)w.bytes);
+            for (int i = 0; i < 15; ++i) buf[(size_t)(off[i] + w.group * per[i] - 1)] = 1;
+        }
+    }
+}
+
 int main(int argc, char** argv) {
     const int iters = argc > 1 ? atoi(argv[1]) : 300;
     rng.seed(argc > 2 ? strtoull(argv[2], nullptr, 10) : 12345);
@@ -360,6 +404,7 @@ int main(int argc, char** argv) {
     fuzz_quantize(iters / 3 + 1);
     fuzz_merge_pack(iters);
     fuzz_carry(iters);
+    fuzz_bank(iters);
     if (failures) {
         fprintf(stderr, "%d failures\n", failures);
         return 1;
