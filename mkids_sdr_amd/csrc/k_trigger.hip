@@ -5,18 +5,22 @@
 //                channel's carried state (exact). Segment s>0 starts W samples early from a guessed
 //                state (re-arm pending, baseline = first filtered sample), runs the warm-up
 //                silently, records its state S_spec at the segment start, then emits packets.
-//   k_trig_fix   one wave per channel. Segment s is exact iff the true state at its start equals
-//                S_spec[s]; by induction from the exact segment 0 that is S_end[s-1] == S_spec[s],
-//                checked for all segments at once (64 per ballot). Only the failures walk
-//                serially: the true and the speculative trajectories are re-run side by side from
-//                the segment start until they coincide (the recurrence is deterministic in
-//                (state, input)) and the packet lists are spliced: true packets before the merge,
-//                speculative ones after it. A re-run that never merges hands its end state to an
-//                explicit check of the next segment.
+//   fix-up       one wave per channel. Segment s is exact iff the true state at its start equals
+//                S_spec[s]; by induction from the exact segment 0 that is S_end[s-1] == S_spec[s].
+//                Only the failures are re-run: the true and the speculative trajectories walk side
+//                by side from the segment start until they coincide (the recurrence is
+//                deterministic in (state, input)) and the packet lists are spliced: true packets
+//                before the merge, speculative ones after it. A re-run that never merges hands its
+//                end state to an explicit check of the next segment. One kernel per baseline mode:
+//     k_trig_fix      EMA / no baseline: every boundary checked at once (64 per ballot), then
+//                     lane 0 walks the failures serially.
+//     k_trig_fix_svf  SVF: the failures were already re-run in parallel by k_trig_refix (one wave
+//                     per boundary, assuming S_end[s-1] is the truth); this kernel confirms the
+//                     assumptions in segment order, splices, and re-runs only what they got wrong.
 //
 // The result is bit-identical to the sequential oracle/trigger.c for every input; the speculation
 // only decides how much sequential work the fix-up does (EMA merges within ~10^2 samples on noisy
-// phase; the slow SVF baseline needs ~10^4, so its segments warm up over kSvfW, mkid_api.hip).
+// phase; the slow SVF baseline needs ~10^4, so its segments warm up over kSvfW, mkid_plan.h).
 // The 26-tap matched filter is 13 v_dot2_i32_i16 per sample in the walk (24-bit multiply-adds in
 // the fix-up's serial re-run). In SVF mode a pre-pass (k_mf_rows) writes the filtered rows once
 // and the walk reads them: its ~10^5-sample warm-up is bound by one wave's instruction stream,
@@ -24,6 +28,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "mkid_plan.h"
 #include "trig_common.h"
 
 namespace mkid {
@@ -38,6 +43,31 @@ constexpr int32_t kFullWarm = 100;
 // segment boundaries as consecutive entries (one coalesced load per 64 boundaries); k_trig_spec
 // writes each thread's two states once
 __device__ __forceinline__ int64_t seg_state(const TrigSpecArgs& a, int c, int s) { return (int64_t)c * a.nseg + s; }
+// rows [seg_begin, seg_end) of segment s, and its entry in the call's slot and count tables
+__device__ __forceinline__ int64_t seg_begin(const TrigSpecArgs& a, int s) { return (int64_t)s * a.L; }
+__device__ __forceinline__ int64_t seg_end(const TrigSpecArgs& a, int s) {
+    return seg_begin(a, s) + a.L < a.J ? seg_begin(a, s) + a.L : a.J;
+}
+__device__ __forceinline__ int64_t slot_entry(const TrigSpecArgs& a, int c, int s) {
+    return (int64_t)c * a.seg_stride + a.seg_off + s;
+}
+__device__ __forceinline__ TrigCfg trig_cfg(const TrigSpecArgs& a, int c) {
+    return TrigCfg{a.thr[c], a.rearm[c], a.mode, a.alpha, a.kf, a.kq, a.base_thr, a.dead};
+}
+
+// Boundary invariant. A segment with a successor is a full L rows long, and L >= kSegL (EMA / no
+// baseline) or L >= kSvfLmin (SVF), both past the start-of-stream hold-off of kHoldOff samples plus
+// the sample that sets the baseline. So s_end[s - 1] has a baseline and has left the hold-off;
+// s_spec[s] comes from a hot-loop state (from_fast*, always binit = 1) or from an exact walk of at
+// least L rows; and a true state handed on by a re-run comes from from_fast_svf or from such a
+// walk. No boundary state of the fix-up is a start-of-stream state: the SVF re-runs take the
+// hot-loop form without a test, and only k_trig_spec's first segment needs the generic recurrence.
+static_assert(plan::kSegL > kHoldOff + 1 && plan::kSvfLmin > kHoldOff + 1, "segments outlast the hold-off");
+
+// raw_jj of channel c: this call's rows, the carried history before row 0, zero before that
+__device__ __forceinline__ int32_t raw_at(const TrigSpecArgs& a, int c, int64_t jj) {
+    return jj >= 0 ? a.raw[jj * a.C + c] : (jj >= -kRawHist ? a.rhist[(jj + kRawHist) * a.C + c] : 0);
+}
 
 __device__ __attribute__((noinline)) uint64_t make_packet(int32_t c, EvInfo ev, int32_t f, int64_t jg) {
     return pack_wide(c, peakfit_i(ev.y1, ev.y2, f), ev.base, jg - 1);
@@ -51,11 +81,7 @@ struct Win {
 __device__ __forceinline__ void load_window(Win& win, const TrigSpecArgs& a, int c, int64_t j) {
     win.w[0] = 0;
 #pragma unroll
-    for (int i = 1; i < kFirTaps; ++i) {
-        const int64_t jj = j - kFirTaps + i;  // slot i holds raw_{j-26+i}
-        win.w[i] = jj >= 0 ? a.raw[jj * a.C + c]
-                           : (jj >= -kRawHist ? a.rhist[(jj + kRawHist) * a.C + c] : 0);
-    }
+    for (int i = 1; i < kFirTaps; ++i) win.w[i] = raw_at(a, c, j - kFirTaps + i);  // slot i: raw_{j-26+i}
 }
 
 // filtered sample for ring position u (raw_j already stored in slot u)
@@ -81,14 +107,18 @@ __device__ __forceinline__ uint32_t pack2(int32_t lo, int32_t hi) {
 
 __device__ __forceinline__ short2_t as_s2(uint32_t v) { return __builtin_bit_cast(short2_t, v); }
 
+// channel c's tap pairs (a_2m, a_2m+1)
+__device__ __forceinline__ void load_tap_pairs(uint32_t (&tp)[kFirTaps / 2], const TrigSpecArgs& a, int c) {
+#pragma unroll
+    for (int m = 0; m < kFirTaps / 2; ++m) tp[m] = pack2(a.fir[c * kFirTaps + 2 * m], a.fir[c * kFirTaps + 2 * m + 1]);
+}
+
 // ring aligned at j: slots 2..25 hold q_{j-24..j-1} (slot (i - j + 26) % 26); last = raw_{j-1}
 __device__ __forceinline__ void load_qwin(QWin& w, const TrigSpecArgs& a, int c, int64_t j) {
     int32_t prev = 0;
 #pragma unroll
     for (int i = 0; i < kFirTaps; ++i) {
-        const int64_t jj = j - kFirTaps + i;  // raw_{j-26+i}
-        const int32_t r = jj >= 0 ? a.raw[jj * a.C + c]
-                                  : (jj >= -kRawHist ? a.rhist[(jj + kRawHist) * a.C + c] : 0);
+        const int32_t r = raw_at(a, c, j - kFirTaps + i);
         w.q[i] = pack2(r, prev);
         prev = r;
     }
@@ -103,6 +133,11 @@ __device__ __forceinline__ void load_qwin(QWin& w, const TrigSpecArgs& a, int c,
 struct Lim16 {
     int32_t lo, hi;
 };
+__device__ __forceinline__ Lim16 lim16() {
+    Lim16 lim{-32768, 32767};
+    asm volatile("" : "+v"(lim.lo), "+v"(lim.hi));
+    return lim;
+}
 __device__ __forceinline__ int32_t mf_q(QWin& w, const uint32_t (&tp)[kFirTaps / 2], int u, uint32_t r,
                                         const Lim16& lim) {
     w.q[u] = __builtin_amdgcn_perm(w.last, r, w.sel);
@@ -177,12 +212,8 @@ template <int MODE, bool FAST = true>
 struct Stepper {
     TrigState st;
     TrigCfg k;
-    __device__ Stepper(const TrigState& s, const TrigCfg& kk, int32_t) : st(s), k(kk) {}
+    __device__ Stepper(const TrigState& s, const TrigCfg& kk) : st(s), k(kk) {}
     __device__ __forceinline__ bool step(int32_t f, EvInfo& ev) { return trig_update(st, f, k, ev); }
-    __device__ __forceinline__ void step_base(int32_t f) {
-        EvInfo ev;
-        (void)trig_update(st, f, k, ev);
-    }
     __device__ __forceinline__ TrigState state() const { return st; }
 };
 
@@ -196,7 +227,6 @@ struct Stepper<MODE, true> {
         if (!s.binit) fs.B = MODE == MKID_BASE_NONE ? 0 : f0;
     }
     __device__ __forceinline__ bool step(int32_t f, EvInfo& ev) { return trig_update_fast<MODE>(fs, f, q, ev); }
-    __device__ __forceinline__ void step_base(int32_t f) { base_update_fast<MODE>(fs, f, q); }
     __device__ __forceinline__ TrigState state() const { return from_fast(fs); }
 };
 
@@ -234,11 +264,12 @@ __device__ __forceinline__ void set_progress_prio(int32_t done, int32_t ng) {
     else if (pc >= 70 * ng) __builtin_amdgcn_s_setprio(2);
 }
 
-// PRE: the rows hold the matched-filter output (a.filt, k_mf_rows) instead of the raw phase: the
-// walk takes f from the lane's half of the loaded dword (SVF mode, whose walk is bound by one
-// wave's instruction stream over a ~10^5-sample warm-up)
-template <int MODE, bool PRE = false>
+// SVF (PRE): the rows hold the matched-filter output (a.filt, k_mf_rows) instead of the raw phase:
+// the walk takes f from the lane's half of the loaded dword (the SVF walk is bound by one wave's
+// instruction stream over a ~10^5-sample warm-up)
+template <int MODE>
 __global__ __launch_bounds__(kSpecThreads, MKID_TRIG_MINW) void k_trig_spec(TrigSpecArgs a) {
+    constexpr bool PRE = MODE == MKID_BASE_SVF;
     __builtin_amdgcn_s_setprio(3);
     const int64_t g = (int64_t)blockIdx.x * kSpecThreads + threadIdx.x;
     if (g >= (int64_t)a.C * a.nseg) return;
@@ -246,20 +277,16 @@ __global__ __launch_bounds__(kSpecThreads, MKID_TRIG_MINW) void k_trig_spec(Trig
     const int c = (int)(g % C);  // lanes of a wave = consecutive channels (coalesced raw loads)
     const int s = (int)(g / C);
     uint32_t tp[kFirTaps / 2];
-    if constexpr (!PRE) {
-#pragma unroll
-        for (int m = 0; m < kFirTaps / 2; ++m)
-            tp[m] = pack2(a.fir[c * kFirTaps + 2 * m], a.fir[c * kFirTaps + 2 * m + 1]);
-    }
-    const TrigCfg k{a.thr[c], a.rearm[c], MODE, a.alpha, a.kf, a.kq, a.base_thr, a.dead};
-    const int64_t seg0 = (int64_t)s * a.L;
-    const int64_t seg1 = seg0 + a.L < a.J ? seg0 + a.L : a.J;
+    if constexpr (!PRE) load_tap_pairs(tp, a, c);
+    TrigCfg k = trig_cfg(a, c);
+    k.mode = MODE;   // a.mode, as a constant
+    const int64_t seg0 = seg_begin(a, s), seg1 = seg_end(a, s);
     // a segment closer than W to the sub-chunk start warms up from row 0 with the carried state
     // (exact); L and W are multiples of 26 whenever W > 0, so seg0 - jw is too
     const int64_t jw = (s == 0 || seg0 <= a.W) ? 0 : seg0 - a.W;
     QWin win;
     if constexpr (!PRE) load_qwin(win, a, c, jw);
-    const int64_t sc = (int64_t)c * a.seg_stride + a.seg_off + s;
+    const int64_t sc = slot_entry(a, c, s);
     uint64_t* slot = a.slots + sc * a.capseg;
     int32_t n = 0;
     // all lanes of a wave share the segment (64 | C): a scalar row base and a 32-bit per-lane
@@ -272,8 +299,7 @@ __global__ __launch_bounds__(kSpecThreads, MKID_TRIG_MINW) void k_trig_spec(Trig
     auto rload = [&](uint32_t off) {
         return (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, (int)lane, __builtin_amdgcn_readfirstlane((int)off), 0);
     };
-    Lim16 lim{-32768, 32767};
-    asm volatile("" : "+v"(lim.lo), "+v"(lim.hi));
+    const Lim16 lim = lim16();
     const uint32_t half = (uint32_t)(c & 1) * 16u;   // PRE: the lane's int16 in the loaded dword
     // filtered sample at ring position u from the loaded dword r
     auto filt = [&](QWin& w, int u, uint32_t r) -> int32_t {
@@ -299,38 +325,31 @@ __global__ __launch_bounds__(kSpecThreads, MKID_TRIG_MINW) void k_trig_spec(Trig
                        (void)sp.step(filt(win, u, r), ev);
                    });
         if (s > 0) a.s_spec[seg_state(a, c, s)] = sp.state();
+        // global row jg, at ring position u, from the loaded dword r: step, and emit into the slot
+        auto emit = [&](int64_t jg, int u, uint32_t r) {
+            const int32_t f = filt(win, u, r);
+            EvInfo ev;
+            if (sp.step(f, ev)) {
+                if (n < a.capseg) slot[n] = make_packet(c, ev, f, jg);
+                ++n;
+            }
+        };
         const int32_t len = (int32_t)(seg1 - seg0);
         const int32_t full = len - len % kFirTaps;
         const int32_t ng = __builtin_amdgcn_readfirstlane(full / kFirTaps);
         run_groups(ng, rbase, rrow, lane, (uint32_t)(2 * C),
-                   [&](int32_t gr, int u, uint32_t r) {
-                       const int32_t f = filt(win, u, r);
-                       EvInfo ev;
-                       if (sp.step(f, ev)) {
-                           if (n < a.capseg) slot[n] = make_packet(c, ev, f, a.j0 + seg0 + gr * kFirTaps + u);
-                           ++n;
-                       }
-                   },
+                   [&](int32_t gr, int u, uint32_t r) { emit(a.j0 + seg0 + gr * kFirTaps + u, u, r); },
                    [&](int32_t gr, int h) {
                        if (h == 1) set_progress_prio(gr + 1, ng);
                    });
-        const int32_t gi = full;
-        const int32_t left = len - gi;  // tail < 26 samples, predicated
+        const int32_t left = len - full;  // tail < 26 samples, predicated
 #pragma unroll
-        for (int u = 0; u < kFirTaps; ++u) {
-            if (u < left) {
-                const int32_t f = filt(win, u, rload(rrow + (uint32_t)(2 * u * C)));
-                EvInfo ev;
-                if (sp.step(f, ev)) {
-                    if (n < a.capseg) slot[n] = make_packet(c, ev, f, a.j0 + seg0 + gi + u);
-                    ++n;
-                }
-            }
-        }
+        for (int u = 0; u < kFirTaps; ++u)
+            if (u < left) emit(a.j0 + seg0 + full + u, u, rload(rrow + (uint32_t)(2 * u * C)));
         a.s_end[seg_state(a, c, s)] = sp.state();
     };
     if (in_holdoff(st0)) {  // first segment after a reset: the generic recurrence
-        Stepper<MODE, false> sp(st0, k, f0);
+        Stepper<MODE, false> sp(st0, k);
         body(sp);
     } else {
         Stepper<MODE> sp(st0, k, f0);
@@ -351,8 +370,7 @@ __global__ __launch_bounds__(kSpecThreads) void k_mf_rows(TrigSpecArgs a, int32_
     if (j0 >= a.J) return;
     const int64_t j1 = j0 + rows_per < a.J ? j0 + rows_per : a.J;
     uint32_t tp[kFirTaps / 2];
-#pragma unroll
-    for (int m = 0; m < kFirTaps / 2; ++m) tp[m] = pack2(a.fir[c * kFirTaps + 2 * m], a.fir[c * kFirTaps + 2 * m + 1]);
+    load_tap_pairs(tp, a, c);
     QWin win;
     load_qwin(win, a, c, j0);
     const int64_t jr = __builtin_amdgcn_readfirstlane((int32_t)j0);
@@ -361,27 +379,25 @@ __global__ __launch_bounds__(kSpecThreads) void k_mf_rows(TrigSpecArgs a, int32_
     const uint32_t lane = (uint32_t)(c >> 1) * 4u;
     const uint32_t lane16 = (uint32_t)c * 2u;
     const uint32_t row = (uint32_t)(2 * C);
-    Lim16 lim{-32768, 32767};
-    asm volatile("" : "+v"(lim.lo), "+v"(lim.hi));
-    auto put = [&](uint32_t roff, int32_t f) {
-        __builtin_amdgcn_raw_buffer_store_b16((unsigned short)f, out, (int)lane16,
+    const Lim16 lim = lim16();
+    // the row at byte offset roff, at ring position u, from the loaded dword r: filter and store
+    auto put = [&](uint32_t roff, int u, uint32_t r) {
+        __builtin_amdgcn_raw_buffer_store_b16((unsigned short)mf_q(win, tp, u, r, lim), out, (int)lane16,
                                               __builtin_amdgcn_readfirstlane((int)roff), 0);
     };
     uint32_t rrow = 0;
     const int32_t len = (int32_t)(j1 - j0);
     const int32_t ng = __builtin_amdgcn_readfirstlane(len / kFirTaps);
-    run_groups(ng, rbase, rrow, lane, row, [&](int32_t gr, int u, uint32_t r) {
-        put((uint32_t)(gr * kFirTaps + u) * row, mf_q(win, tp, u, r, lim));
-    });
+    run_groups(ng, rbase, rrow, lane, row,
+               [&](int32_t gr, int u, uint32_t r) { put((uint32_t)(gr * kFirTaps + u) * row, u, r); });
     const int32_t left = len - ng * kFirTaps;   // tail < 26 rows (last block only), predicated
     const __amdgpu_buffer_rsrc_t rs = raw_rsrc(rbase);
 #pragma unroll
     for (int u = 0; u < kFirTaps; ++u) {
         if (u < left) {
             const uint32_t ro = rrow + (uint32_t)u * row;
-            const uint32_t r = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, (int)lane,
-                                                                            __builtin_amdgcn_readfirstlane((int)ro), 0);
-            put(ro, mf_q(win, tp, u, r, lim));
+            put(ro, u, (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, (int)lane,
+                                                                       __builtin_amdgcn_readfirstlane((int)ro), 0));
         }
     }
 }
@@ -392,7 +408,7 @@ __global__ __launch_bounds__(kSpecThreads) void k_mf_rows(TrigSpecArgs a, int32_
 // its detection count in nt and ndrop alike, so a late detection splices the same list.
 __device__ void splice_segment(const TrigSpecArgs& a, int c, int s, int32_t nt, int32_t ndrop, bool merged,
                                const uint64_t* scratch) {
-    const int64_t sc = (int64_t)c * a.seg_stride + a.seg_off + s;
+    const int64_t sc = slot_entry(a, c, s);
     uint64_t* slot = a.slots + sc * a.capseg;
     const int32_t cnt = a.counts[sc] < a.capseg ? a.counts[sc] : a.capseg;
     int32_t total = nt;
@@ -414,8 +430,7 @@ __device__ void splice_segment(const TrigSpecArgs& a, int c, int s, int32_t nt, 
 // Returns true if they merged; T becomes the true state at the segment end when they did not.
 __device__ bool rerun_segment(const TrigSpecArgs& a, int c, int s, const int32_t (&tap)[kFirTaps],
                               const TrigCfg& k, TrigState& T, const TrigState& S0) {
-    const int64_t seg0 = (int64_t)s * a.L;
-    const int64_t seg1 = seg0 + a.L < a.J ? seg0 + a.L : a.J;
+    const int64_t seg0 = seg_begin(a, s), seg1 = seg_end(a, s);
     uint64_t* scratch = a.scratch + (int64_t)c * a.capseg;
     TrigState tru = T, spc = S0;
     int32_t nt = 0, ndrop = 0;
@@ -452,6 +467,12 @@ __device__ bool rerun_segment(const TrigSpecArgs& a, int c, int s, const int32_t
     return merged;
 }
 
+// v of lane `lane`, wave-uniform
+__device__ __forceinline__ uint64_t readlane64(uint64_t v, int lane) {
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int32_t)(v >> 32), lane) << 32) |
+           (uint32_t)__builtin_amdgcn_readlane((int32_t)v, lane);
+}
+
 // SVF re-run of segment s of channel c on one wave (the filter pre-pass, a.filt): lanes 0 and 1
 // step the true (from T) and the speculative (from S0) trajectory in lockstep (one instruction
 // stream for both, the hot-loop form trig_update_svf) over the pre-filtered rows, 64 rows per
@@ -462,8 +483,7 @@ __device__ bool rerun_segment(const TrigSpecArgs& a, int c, int s, const int32_t
 // rows) took 3.2 ms for one segment of 16384 rows at config 3; this one 0.71 ms.
 __device__ bool svf_walk(const TrigSpecArgs& a, int c, int s, const TrigCfg& k, const TrigState& T,
                          const TrigState& S0, int lane, uint64_t* out, int32_t& nt, int32_t& ndrop, TrigState& Tend) {
-    const int64_t seg0 = (int64_t)s * a.L;
-    const int64_t seg1 = seg0 + a.L < a.J ? seg0 + a.L : a.J;
+    const int64_t seg0 = seg_begin(a, s), seg1 = seg_end(a, s);
     const FastCfg q = fast_cfg(k);
     FastSvf st = to_fast_svf(lane == 0 ? T : S0);
     nt = 0;
@@ -493,10 +513,7 @@ __device__ bool svf_walk(const TrigSpecArgs& a, int c, int s, const TrigCfg& k, 
             bl[i] = ev.base;
         }
         __builtin_amdgcn_wave_barrier();
-        const uint64_t e0 = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int32_t)(em >> 32), 0) << 32) |
-                            (uint32_t)__builtin_amdgcn_readlane((int32_t)em, 0);
-        const uint64_t e1 = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int32_t)(em >> 32), 1) << 32) |
-                            (uint32_t)__builtin_amdgcn_readlane((int32_t)em, 1);
+        const uint64_t e0 = readlane64(em, 0), e1 = readlane64(em, 1);
         ndrop += __builtin_popcountll(e1);
         for (uint64_t m = e0; m; m &= m - 1) {   // lane 0's packets: row i, samples i - 2 .. i
             const int i = __builtin_ctzll(m);
@@ -513,10 +530,8 @@ __device__ bool svf_walk(const TrigSpecArgs& a, int c, int s, const TrigCfg& k, 
     }
     if (!merged) {   // lane 0's trajectory, broadcast
         FastSvf t;
-        t.low = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int32_t)(st.low >> 32), 0) << 32) |
-                          (uint32_t)__builtin_amdgcn_readlane((int32_t)st.low, 0));
-        t.band = (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int32_t)(st.band >> 32), 0) << 32) |
-                           (uint32_t)__builtin_amdgcn_readlane((int32_t)st.band, 0));
+        t.low = (int64_t)readlane64((uint64_t)st.low, 0);
+        t.band = (int64_t)readlane64((uint64_t)st.band, 0);
         t.x = __builtin_amdgcn_readlane(st.x, 0);
         t.f1 = __builtin_amdgcn_readlane(st.f1, 0);
         t.f2 = __builtin_amdgcn_readlane(st.f2, 0);
@@ -525,39 +540,10 @@ __device__ bool svf_walk(const TrigSpecArgs& a, int c, int s, const TrigCfg& k, 
     return merged;
 }
 
-// The two-lane walk usable from any state: a start-of-stream state (hold-off, no baseline) takes
-// the generic single-lane walk instead (rerun_segment). Called by every lane with T uniform; on
-// return T is uniform (the true end state when the trajectories did not merge).
-__device__ bool rerun_segment_svf(const TrigSpecArgs& a, int c, int s, const int32_t (&tap)[kFirTaps],
-                                  const TrigCfg& k, TrigState& T, const TrigState& S0, int lane) {
-    __shared__ TrigState t_sh;
-    __shared__ int32_t m_sh;
-    if (!T.binit || !S0.binit || in_holdoff(T) || in_holdoff(S0)) {   // start of stream: generic walk
-        if (lane == 0) {
-            TrigState t = T;
-            m_sh = rerun_segment(a, c, s, tap, k, t, S0) ? 1 : 0;
-            t_sh = t;
-        }
-        __syncthreads();
-        const bool merged = m_sh != 0;
-        T = t_sh;
-        __syncthreads();
-        return merged;
-    }
-    uint64_t* scratch = a.scratch + (int64_t)c * a.capseg;
-    int32_t nt, ndrop;
-    TrigState Tend = T;
-    const bool merged = svf_walk(a, c, s, k, T, S0, lane, scratch, nt, ndrop, Tend);
-    if (lane == 0) splice_segment(a, c, s, nt, ndrop, merged, scratch);
-    if (!merged) T = Tend;
-    __syncthreads();   // lane 0's slot and scratch writes before any later segment's re-run
-    return merged;
-}
-
 // Phase A of the SVF fix-up (round 6): one wave per (channel c, segment s >= 1) of the sub-chunk.
 // A segment whose speculated start state differs from its predecessor's speculative end state is
 // re-run at once, assuming that end state is the true one (it is unless the predecessor itself
-// fails and does not merge), into its own result and packet entries; k_trig_fix confirms the
+// fails and does not merge), into its own result and packet entries; k_trig_fix_svf confirms the
 // assumptions channel by channel and splices. The failed segments of all channels walk in parallel
 // instead of one after another in their channel's wave.
 __global__ __launch_bounds__(256) void k_trig_refix(TrigSpecArgs a) {
@@ -566,21 +552,16 @@ __global__ __launch_bounds__(256) void k_trig_refix(TrigSpecArgs a) {
     const int lane = threadIdx.x & 63;
     if (w >= (int64_t)C * (a.nseg - 1)) return;   // wave-uniform
     const int c = (int)(w % C), s = (int)(w / C) + 1;
-    const int64_t sc = (int64_t)c * a.seg_stride + a.seg_off + s;
+    const int64_t sc = slot_entry(a, c, s);
     RefixRes* res = a.refix + sc;
     const TrigState P = a.s_end[seg_state(a, c, s - 1)];
     const TrigState S0 = a.s_spec[seg_state(a, c, s)];
     int32_t status = RF_OK, nt = 0, ndrop = 0;
     TrigState Tend = P;
-    if (!state_eq(P, S0, a.mode)) {
-        if (!P.binit || !S0.binit || in_holdoff(P) || in_holdoff(S0)) {
-            status = RF_SERIAL;   // start of stream: k_trig_fix walks it
-        } else {
-            const TrigCfg k{a.thr[c], a.rearm[c], a.mode, a.alpha, a.kf, a.kq, a.base_thr, a.dead};
-            status = svf_walk(a, c, s, k, P, S0, lane, a.refix_pk + sc * a.capseg, nt, ndrop, Tend) ? RF_MERGED
-                                                                                                  : RF_UNMERGED;
-        }
-    }
+    if (!state_eq(P, S0, a.mode))
+        status = svf_walk(a, c, s, trig_cfg(a, c), P, S0, lane, a.refix_pk + sc * a.capseg, nt, ndrop, Tend)
+                     ? RF_MERGED
+                     : RF_UNMERGED;
     if (lane == 0) {
         res->status = status;
         res->nt = nt;
@@ -589,6 +570,8 @@ __global__ __launch_bounds__(256) void k_trig_refix(TrigSpecArgs a) {
     }
 }
 
+// The EMA / no-baseline fix-up: one wave per channel checks every boundary, then lane 0 re-runs the
+// failures in segment order with the generic recurrence (rerun_segment).
 __global__ __launch_bounds__(64) void k_trig_fix(TrigSpecArgs a) {
     extern __shared__ uint64_t okbits[];  // bit s%64 of word s/64: segment s needs no re-run
     const int c = blockIdx.x;
@@ -615,54 +598,12 @@ __global__ __launch_bounds__(64) void k_trig_fix(TrigSpecArgs a) {
         }
     }
     __syncthreads();
-    // SVF with the filter pre-pass: the whole wave runs the control below (uniform) and the
-    // re-runs use two lanes (rerun_segment_svf); otherwise lane 0 alone walks
-    const bool wave_walk = a.mode == MKID_BASE_SVF && a.filt != nullptr;
-    if (!wave_walk && lane != 0) return;
+    if (lane != 0) return;   // lane 0 alone walks
     int32_t tap[kFirTaps];
 #pragma unroll
     for (int i = 0; i < kFirTaps; ++i) tap[i] = a.fir[c * kFirTaps + i];
-    const TrigCfg k{a.thr[c], a.rearm[c], a.mode, a.alpha, a.kf, a.kq, a.base_thr, a.dead};
+    const TrigCfg k = trig_cfg(a, c);
     int32_t reruns = 0;
-    if (wave_walk && a.refix && a.refix_pk) {
-        // phase B after k_trig_refix: walk the segments in order. While the true start of segment s
-        // is s_end[s - 1] (truth), its phase-A result holds: OK keeps the speculative list, a re-run
-        // is spliced, an unmerged one hands its true end state on. Otherwise (T) the segment is
-        // checked against T and, if it differs, re-run here from T (phase A assumed the wrong start).
-        bool truth = true;
-        TrigState T{};
-        for (int s = 1; s < a.nseg; ++s) {
-            const int64_t sc = (int64_t)c * a.seg_stride + a.seg_off + s;
-            const RefixRes* r = a.refix + sc;
-            const int32_t st = r->status;
-            const TrigState S0 = a.s_spec[seg_state(a, c, s)];
-            if (truth) {
-                if (st == RF_OK) continue;
-                ++reruns;
-                if (st == RF_MERGED || st == RF_UNMERGED) {
-                    if (lane == 0) splice_segment(a, c, s, r->nt, r->ndrop, st == RF_MERGED, a.refix_pk + sc * a.capseg);
-                    if (st == RF_UNMERGED) {
-                        T = r->T;
-                        truth = false;
-                    }
-                    continue;
-                }
-                T = a.s_end[seg_state(a, c, s - 1)];   // RF_SERIAL
-                truth = rerun_segment_svf(a, c, s, tap, k, T, S0, lane);
-            } else {
-                if (state_eq(T, S0, a.mode)) {
-                    truth = true;
-                    continue;
-                }
-                ++reruns;
-                truth = rerun_segment_svf(a, c, s, tap, k, T, S0, lane);
-            }
-        }
-        if (lane != 0) return;
-        a.st_out[c] = truth ? a.s_end[seg_state(a, c, a.nseg - 1)] : T;
-        if (a.reruns) a.reruns[c] = reruns;
-        return;
-    }
     TrigState T{};
     bool override_ = false;  // T holds the true start state of segment s (from an unmerged re-run)
     int s = 1;
@@ -683,11 +624,55 @@ __global__ __launch_bounds__(64) void k_trig_fix(TrigSpecArgs a) {
         }
         ++reruns;
         const TrigState S0 = a.s_spec[seg_state(a, c, s)];
-        override_ = wave_walk ? !rerun_segment_svf(a, c, s, tap, k, T, S0, lane) : !rerun_segment(a, c, s, tap, k, T, S0);
+        override_ = !rerun_segment(a, c, s, tap, k, T, S0);
         ++s;
     }
-    if (lane != 0) return;
     a.st_out[c] = override_ ? T : a.s_end[seg_state(a, c, a.nseg - 1)];
+    if (a.reruns) a.reruns[c] = reruns;
+}
+
+// Phase B of the SVF fix-up, after k_trig_refix: one wave per channel walks the segments in order,
+// the control uniform over the wave. While the true start of segment s is s_end[s - 1] (truth),
+// its phase-A result holds: OK keeps the speculative list, a re-run is spliced, an unmerged one
+// hands its true end state T on. Otherwise the segment is checked against T and, if it differs,
+// re-run here from T on two lanes (phase A assumed the wrong start).
+__global__ __launch_bounds__(64) void k_trig_fix_svf(TrigSpecArgs a) {
+    const int c = blockIdx.x;
+    const int lane = threadIdx.x;
+    const TrigCfg k = trig_cfg(a, c);
+    uint64_t* scratch = a.scratch + (int64_t)c * a.capseg;
+    int32_t reruns = 0;
+    bool truth = true;
+    TrigState T{};
+    for (int s = 1; s < a.nseg; ++s) {
+        if (truth) {
+            const int64_t sc = slot_entry(a, c, s);
+            const RefixRes* r = a.refix + sc;
+            const int32_t st = r->status;
+            if (st == RF_OK) continue;
+            ++reruns;
+            if (lane == 0) splice_segment(a, c, s, r->nt, r->ndrop, st == RF_MERGED, a.refix_pk + sc * a.capseg);
+            if (st == RF_UNMERGED) {
+                T = r->T;
+                truth = false;
+            }
+            continue;
+        }
+        const TrigState S0 = a.s_spec[seg_state(a, c, s)];
+        if (state_eq(T, S0, a.mode)) {
+            truth = true;
+            continue;
+        }
+        ++reruns;
+        int32_t nt, ndrop;
+        TrigState Tend = T;
+        truth = svf_walk(a, c, s, k, T, S0, lane, scratch, nt, ndrop, Tend);
+        if (lane == 0) splice_segment(a, c, s, nt, ndrop, truth, scratch);
+        if (!truth) T = Tend;
+        __syncthreads();   // lane 0's slot and scratch writes before any later segment's re-run
+    }
+    if (lane != 0) return;
+    a.st_out[c] = truth ? a.s_end[seg_state(a, c, a.nseg - 1)] : T;
     if (a.reruns) a.reruns[c] = reruns;
 }
 
@@ -704,9 +689,9 @@ int64_t trigger_wave_slots(int device) {
 hipError_t launch_trigger(const TrigSpecArgs& a, hipStream_t s) {
     const int64_t threads = (int64_t)a.C * a.nseg;
     const dim3 grid((unsigned)((threads + kSpecThreads - 1) / kSpecThreads));
-    if (a.mode == MKID_BASE_EMA)
-        hipLaunchKernelGGL(k_trig_spec<MKID_BASE_EMA>, grid, dim3(kSpecThreads), 0, s, a);
-    else if (a.mode == MKID_BASE_SVF && a.filt) {
+    hipError_t e;
+    if (a.mode == MKID_BASE_SVF) {
+        if (!a.filt || !a.refix || !a.refix_pk) return hipErrorInvalidValue;   // SvfTables, mkid_ctx.h
         // filter pre-pass: row blocks of >= 520 rows (a multiple of 26), ~3 waves per SIMD
         const int64_t nt = std::max<int64_t>(1, (int64_t)3072 * 64 / a.C);
         int64_t rp = std::max<int64_t>(520, (a.J + nt - 1) / nt);
@@ -714,21 +699,22 @@ hipError_t launch_trigger(const TrigSpecArgs& a, hipStream_t s) {
         const int64_t mthreads = (int64_t)a.C * ((a.J + rp - 1) / rp);
         hipLaunchKernelGGL(k_mf_rows, dim3((unsigned)((mthreads + kSpecThreads - 1) / kSpecThreads)),
                            dim3(kSpecThreads), 0, s, a, (int32_t)rp);
-        hipError_t e0 = hipGetLastError();
-        if (e0 != hipSuccess) return e0;
-        hipLaunchKernelGGL((k_trig_spec<MKID_BASE_SVF, true>), grid, dim3(kSpecThreads), 0, s, a);
-        if (a.refix && a.refix_pk && a.nseg > 1) {
-            hipError_t e1 = hipGetLastError();
-            if (e1 != hipSuccess) return e1;
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_trig_spec<MKID_BASE_SVF>, grid, dim3(kSpecThreads), 0, s, a);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (a.nseg > 1) {
             const int64_t waves = (int64_t)a.C * (a.nseg - 1);
             hipLaunchKernelGGL(k_trig_refix, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, a);
+            if ((e = hipGetLastError()) != hipSuccess) return e;
         }
-    } else if (a.mode == MKID_BASE_SVF)
-        hipLaunchKernelGGL(k_trig_spec<MKID_BASE_SVF>, grid, dim3(kSpecThreads), 0, s, a);
+        hipLaunchKernelGGL(k_trig_fix_svf, dim3(a.C), dim3(64), 0, s, a);
+        return hipGetLastError();
+    }
+    if (a.mode == MKID_BASE_EMA)
+        hipLaunchKernelGGL(k_trig_spec<MKID_BASE_EMA>, grid, dim3(kSpecThreads), 0, s, a);
     else
         hipLaunchKernelGGL(k_trig_spec<MKID_BASE_NONE>, grid, dim3(kSpecThreads), 0, s, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
+    if ((e = hipGetLastError()) != hipSuccess) return e;
     const size_t lds = (size_t)((a.nseg + 63) / 64) * 8;
     hipLaunchKernelGGL(k_trig_fix, dim3(a.C), dim3(64), lds, s, a);
     return hipGetLastError();

@@ -427,20 +427,9 @@ int mkid_set_baseline(mkid_ctx* c, int32_t mode, int32_t alpha, int32_t kf, int3
     if (alpha < 0 || alpha > 1024) FAIL(c, MKID_E_ARG, "alpha must be Fix12_9 in 0..1024 (gain <= 2.0)");
     if (kf < 0 || kf >= (1 << 18) || kq < 0 || kq >= (1 << 18)) FAIL(c, MKID_E_ARG, "kf/kq must be Fix18_16");
     if (base_thr < 0 || base_thr > 65535) FAIL(c, MKID_E_ARG, "base_thr must be Fix16_13 (0..65535)");
-    if (mode == MKID_BASE_SVF && !(c->d_filt.get() && c->d_refix.get())) {
-        // allocated on first use; whichever is missing after a failure is tried again by the next call
+    if (mode == MKID_BASE_SVF && !c->svf.ready()) {   // allocated on first use
         HIPCHK(c, hipSetDevice(c->device));
-        if (!c->d_filt.get()) HIPCHK(c, c->d_filt.alloc((size_t)c->ws.Jmax * c->C));   // filter pre-pass rows
-        // the parallel re-run tables (k_trig_refix): one result per slot-table segment, one packet
-        // table the size of the slot table. Both or neither (without them the fix-up walks the
-        // failed segments in the channel's wave, k_trig_fix)
-        DevBuf<RefixRes> rf;
-        DevBuf<uint64_t> rp;
-        hipError_t e = rf.alloc((size_t)c->C * (size_t)c->ws.nsub_max * (size_t)std::max<int64_t>(1, c->ws.nseg_max));
-        if (e == hipSuccess) e = rp.alloc((size_t)c->ws.slot_cap);
-        if (e != hipSuccess) FAIL(c, MKID_E_HIP, "hipMalloc of the SVF re-run tables failed");
-        c->d_refix = std::move(rf);
-        c->d_refix_pk = std::move(rp);
+        if (c->svf.alloc(c->ws, c->C) != hipSuccess) FAIL(c, MKID_E_HIP, "hipMalloc of the SVF tables failed");
     }
     c->mode = mode; c->alpha = alpha; c->kf = kf; c->kq = kq; c->base_thr = base_thr;
     return MKID_OK;

@@ -77,6 +77,23 @@ struct RollBuf {
     }
 };
 
+// The SVF trigger path's device tables (TrigSpecArgs filt / refix / refix_pk), allocated on the
+// first mkid_set_baseline(SVF): all three or none, and a failed alloc() is tried again by the next.
+struct SvfTables {
+    DevBuf<int16_t> filt;            // [Jmax][C] filter pre-pass output (k_mf_rows)
+    DevBuf<mkid::RefixRes> refix;    // [C][nsub_max * nseg_max] parallel re-run results (k_trig_refix)
+    DevBuf<uint64_t> refix_pk;       // [slot_cap] their true packets (the slot table's geometry)
+    bool ready() const { return filt.get() != nullptr; }
+    hipError_t alloc(const mkid::plan::Workspace& ws, int C) {
+        SvfTables t;
+        hipError_t e = t.filt.alloc((size_t)ws.Jmax * C);
+        if (e == hipSuccess) e = t.refix.alloc((size_t)C * (size_t)ws.nsub_max * (size_t)std::max<int64_t>(1, ws.nseg_max));
+        if (e == hipSuccess) e = t.refix_pk.alloc((size_t)ws.slot_cap);
+        if (e == hipSuccess) *this = std::move(t);
+        return e;
+    }
+};
+
 struct KTime { int k; hipEvent_t a, b; };
 
 // Streams and events of a context. A base of mkid_ctx, so that it is destroyed after the members:
@@ -147,9 +164,7 @@ struct mkid_ctx : CtxHandles {
     // workspace
     DevBuf<float2> d_zb[2];
     DevBuf<int16_t> d_raw;
-    DevBuf<int16_t> d_filt;          // [Jmax][C] SVF filter pre-pass output (k_mf_rows)
-    DevBuf<mkid::RefixRes> d_refix;  // [C][nsub_max * nseg_max] SVF parallel re-run results (k_trig_refix)
-    DevBuf<uint64_t> d_refix_pk;     // [slot_cap] their true packets (the slot table's geometry)
+    SvfTables svf;                   // none until the SVF baseline is first selected
     DevBuf<long long> d_ysum;        // [C][2] fixed point 2^-kYsumFrac: sums of y' while armed
     // avgIQ accumulator (K9; startAccumulator / avgIQ_ctrl, ROACH_Setup.py:654-659): armed by
     // mkid_set_accumulator; rows accumulated since arming and the host-side sums of G c' over them

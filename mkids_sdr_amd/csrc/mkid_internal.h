@@ -113,7 +113,7 @@ struct FrontArgs {
 // Result of one segment's parallel SVF re-run (k_trig_refix, round 6): status and, for a re-run,
 // the true packets before the merge detection (in TrigSpecArgs::refix_pk at the segment's slot
 // entry), the speculative packets the re-run dropped, and the true end state when it did not merge.
-enum { RF_OK = 0, RF_MERGED = 1, RF_UNMERGED = 2, RF_SERIAL = 3 };
+enum { RF_OK = 0, RF_MERGED = 1, RF_UNMERGED = 2 };
 struct RefixRes {
     int32_t status, nt, ndrop, pad;
     TrigState T;
@@ -141,12 +141,13 @@ struct TrigSpecArgs {
     // the segments of one call's sub-chunks share one [C][seg_stride] slot table, so that a single
     // compaction at the end of the call orders packets channel-major over the whole call
     int32_t seg_stride, seg_off;
-    // [J][C] matched-filter output (int16) of the SVF path's filter pre-pass (k_mf_rows), so
-    // that the SVF walk, bound by one wave's instruction stream, skips the 26-tap filter
+    // The SVF path's tables (mkid_ctx.h SvfTables; an SVF launch needs all three, other modes none).
+    // filt: [J][C] matched-filter output (int16) of the filter pre-pass (k_mf_rows), so that the SVF
+    // walk, bound by one wave's instruction stream, skips the 26-tap filter. refix / refix_pk: every
+    // failed segment is re-run in parallel (k_trig_refix) assuming its predecessor's speculative end
+    // state, into [C][seg_stride] results and a [C][seg_stride][capseg] packet table; k_trig_fix_svf
+    // then confirms the assumptions channel by channel
     int16_t* filt = nullptr;
-    // SVF with the pre-pass: every failed segment is re-run in parallel (k_trig_refix) assuming its
-    // predecessor's speculative end state, into [C][seg_stride] results and a [C][seg_stride][capseg]
-    // packet table; k_trig_fix then confirms the assumptions channel by channel
     RefixRes* refix = nullptr;
     uint64_t* refix_pk = nullptr;
 };

@@ -46,7 +46,7 @@ static int run_trigger(mkid_ctx* c, const int16_t* raw, const CallPlan& p, const
                     c->d_scratch.get(), c->d_reruns.get(),
                     sp.J,       c->j0,      c->C,       sp.nseg,       sp.L,         sp.W,
                     p.capseg,   c->mode,    c->alpha,   c->kf,         c->kq,        c->base_thr,
-                    c->cfg.dead_time, p.stride, sp.seg_off, c->d_filt.get(), c->d_refix.get(), c->d_refix_pk.get()};
+                    c->cfg.dead_time, p.stride, sp.seg_off, c->svf.filt.get(), c->svf.refix.get(), c->svf.refix_pk.get()};
     tstart(c, MKID_K_TRIGGER, &kt, s);
     HIPCHK(c, launch_trigger(ta, s));
     tstop(c, &kt, s);

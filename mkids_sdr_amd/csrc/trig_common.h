@@ -1,5 +1,5 @@
-// One sample of the K7/K8 trigger recurrence, shared by the serial, speculative and fix-up
-// kernels. Integer semantics bit-identical to oracle/trigger.c (reference anchors listed there).
+// One sample of the K7/K8 trigger recurrence, shared by the speculative and fix-up kernels of
+// k_trigger.hip. Integer semantics bit-identical to oracle/trigger.c (reference anchors listed there).
 #pragma once
 #include "mkid_internal.h"
 
@@ -117,6 +117,17 @@ __device__ __forceinline__ TrigState from_fast(const FastState& f) {
     return TrigState{f.B, 1, st, f.x > 0 ? f.x : 0, f.f1, f.f2, 0, 0, 0, 0};
 }
 
+// One step of the code-state machine on sample f (e = f - baseline, f1 the previous sample).
+// Returns true when a packet is due.
+__device__ __forceinline__ bool code_step(int32_t& x, int32_t e, int32_t f, int32_t f1, const FastCfg& k) {
+    const bool emit = (x == -2) & (f > f1);
+    int32_t xn = e < (x == 0 ? k.rearm : k.thr) ? 2 * x : -1;
+    xn = x == -2 ? (f > f1 ? k.dx : -2) : xn;
+    xn = x > 0 ? x - 1 : xn;
+    x = xn;
+    return emit;
+}
+
 template <int MODE>
 __device__ __forceinline__ bool trig_update_fast(FastState& s, int32_t f, const FastCfg& k, EvInfo& ev) {
     const int32_t e = f - s.B;
@@ -127,12 +138,7 @@ __device__ __forceinline__ bool trig_update_fast(FastState& s, int32_t f, const 
         const int32_t gate = -(int32_t)((uint32_t)e + k.goff < k.glim);
         s.B += (__mul24(k.alpha, e) >> 9) & gate;
     }
-    const int32_t x = s.x;
-    const bool emit = (x == -2) & (f > s.f1);
-    int32_t xn = e < (x == 0 ? k.rearm : k.thr) ? 2 * x : -1;
-    xn = x == -2 ? (f > s.f1 ? k.dx : -2) : xn;
-    xn = x > 0 ? x - 1 : xn;
-    s.x = xn;
+    const bool emit = code_step(s.x, e, f, s.f1, k);
     s.f2 = s.f1;
     s.f1 = f;
     return emit;
@@ -166,14 +172,24 @@ __device__ __forceinline__ int64_t mul_u32_i64(uint32_t a, int64_t b) {
     return (int64_t)(lo + ((uint64_t)hi << 32));
 }
 
-__device__ __forceinline__ void base_update_svf(FastSvf& s, int32_t f, const FastCfg& k, int32_t kf, int32_t kq) {
-    const int32_t e = f - (int32_t)(s.low >> 16);
+// Gated Chamberlin update on sample f (e = f - (low >> 16)), computed unconditionally and selected
+// (a branch per sample splits the unrolled groups into blocks the register allocator spills
+// across). kf, kq are Fix18_16 in 0..2^18-1 (mkid_set_baseline checks)
+__device__ __forceinline__ void svf_update(FastSvf& s, int32_t f, int32_t e, const FastCfg& k, int32_t kf, int32_t kq) {
     const bool gate = (uint32_t)e + k.goff < k.glim;
     const int64_t high = ((int64_t)f * 65536) - s.low - (mul_u32_i64((uint32_t)kq, s.band) >> 16);
     const int64_t band = s.band + (mul_u32_i64((uint32_t)kf, high) >> 16);
     const int64_t low = s.low + (mul_u32_i64((uint32_t)kf, band) >> 16);
     s.band = gate ? band : s.band;
     s.low = gate ? low : s.low;
+}
+
+// Baseline-only form for the early part of a long speculative warm-up: the baseline (low, band)
+// and the last two samples advance, the code-state machine does not. Whatever code results is
+// re-converged by the full steps of the warm-up's last part and, like every speculated start
+// state, verified exactly by the fix-up.
+__device__ __forceinline__ void base_update_svf(FastSvf& s, int32_t f, const FastCfg& k, int32_t kf, int32_t kq) {
+    svf_update(s, f, f - (int32_t)(s.low >> 16), k, kf, kq);
     s.f2 = s.f1;
     s.f1 = f;
 }
@@ -183,40 +199,11 @@ __device__ __forceinline__ bool trig_update_svf(FastSvf& s, int32_t f, const Fas
     const int32_t base = (int32_t)(s.low >> 16);
     const int32_t e = f - base;
     ev = EvInfo{s.f2, s.f1, base};
-    {   // computed unconditionally and selected (a branch per sample splits the unrolled groups
-        // into blocks the register allocator spills across)
-        const bool gate = (uint32_t)e + k.goff < k.glim;
-        // kf, kq are Fix18_16 in 0..2^18-1 (mkid_set_baseline checks)
-        const int64_t high = ((int64_t)f * 65536) - s.low - (mul_u32_i64((uint32_t)kq, s.band) >> 16);
-        const int64_t band = s.band + (mul_u32_i64((uint32_t)kf, high) >> 16);
-        const int64_t low = s.low + (mul_u32_i64((uint32_t)kf, band) >> 16);
-        s.band = gate ? band : s.band;
-        s.low = gate ? low : s.low;
-    }
-    const int32_t x = s.x;
-    const bool emit = (x == -2) & (f > s.f1);
-    int32_t xn = e < (x == 0 ? k.rearm : k.thr) ? 2 * x : -1;
-    xn = x == -2 ? (f > s.f1 ? k.dx : -2) : xn;
-    xn = x > 0 ? x - 1 : xn;
-    s.x = xn;
+    svf_update(s, f, e, k, kf, kq);
+    const bool emit = code_step(s.x, e, f, s.f1, k);
     s.f2 = s.f1;
     s.f1 = f;
     return emit;
-}
-
-// Baseline-only forms for the early part of a long speculative warm-up: the baseline (EMA B /
-// SVF low, band) and the last two samples advance, the trigger state machine does not. Whatever
-// state machine code results is re-converged by the full steps of the warm-up's last part and,
-// like every speculated start state, verified exactly by k_trig_fix.
-template <int MODE>
-__device__ __forceinline__ void base_update_fast(FastState& s, int32_t f, const FastCfg& k) {
-    if (MODE == MKID_BASE_EMA) {
-        const int32_t e = f - s.B;
-        const int32_t gate = -(int32_t)((uint32_t)e + k.goff < k.glim);
-        s.B += (__mul24(k.alpha, e) >> 9) & gate;
-    }
-    s.f2 = s.f1;
-    s.f1 = f;
 }
 
 // Advance state s by one filtered sample f taken at global phase index jg. Returns true and fills
