@@ -253,7 +253,12 @@ int mkid_replay_trigger(mkid_ctx* ctx, const int16_t* d_raw, int64_t n, int64_t 
  * Outputs the PulseAnalysis fields (pulses.py:44-51): template [2000] f64 (deg-normalised,
  * peak at pstart), noise PSD [800] f64, and the scalars below. Fails with MKID_E_STATE when no
  * pulse survives the first pass or none survives the second; d_template, d_noise and info are
- * then left as they were. */
+ * then left as they were. 1 <= npulses <= 2^31 - 1 (MKID_E_ARG otherwise). Device pointers for
+ * the pulses, template and noise, a host pointer for info; complete on return.
+ * The call is mkid_bank_filters' pipeline on one channel whose npulses records are all ready,
+ * without the filter, and shares that call's workspace: the context keeps it after the call,
+ * sized by the largest call of either kind so far (for this call 22 432 B per pulse plus 64.1 KB
+ * of fixed tables; mkid_destroy frees it). */
 typedef struct mkid_template_info {
     double count;   /* pulses in the final template (pass 2)                         */
     double count1;  /* pulses in the preliminary template (pass 1, first 1000 pulses) */
@@ -349,7 +354,9 @@ int mkid_capture_pulses_counted(mkid_ctx* ctx, const float* d_phase, int64_t row
  *     exactly mkid_make_template and then mkid_optimal_filter(pre, ncoeff): template, noise, every
  *     info field and coeff = (float) of the float64 weights are bit-identical to those two calls on
  *     that channel's set, the reference's double re-reference of the first 1000 pulses and the
- *     pass-1 cap of 1000 pulses included.
+ *     pass-1 cap of 1000 pulses included. This holds because mkid_make_template launches the same
+ *     kernels on a one-channel bank (R = ready = npulses) and the filter stage is one device function
+ *     for both calls; a channel's result does not depend on its slot, R or the group (below).
  *   - Phase mode (d_Q == NULL): d_I holds phase records (rad); the same pipeline runs on
  *     I = cosf(sign phi), Q = sinf(sign phi), formed as the records are loaded (no I/Q copy of the
  *     bank is made).

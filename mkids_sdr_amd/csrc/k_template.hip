@@ -18,11 +18,13 @@
 // (atan2f and the least-squares fit differ in the last bits), and every accept/skip decision away
 // from a threshold is identical (tests/test_template.py, tests/test_gpu_template.py).
 //
-// Every stage is a device function with two callers: the single-set kernels k_tpl_* (one
-// resonator's set, scalars through the host: mkid_make_template, mkid_optimal_filter) and the bank
-// kernels k_bank_* (mkid_bank_filters: a group of channels of a record bank per launch, scalars in
-// device tables, I/Q or phase records read where they lie). In I/Q mode the bank path gives the
-// single path's bits (tests/test_bank_filters.py); DESIGN.md §5.7 has the layout.
+// Every stage is one device function and runs in one set of kernels, k_bank_*: a group of channels of
+// a record bank per launch, every scalar (I1m/Q1m, pm/pdev, the counts, both status decisions) in
+// device tables, I/Q or phase records read where they lie and never written. mkid_bank_filters
+// launches them over a caller's bank; mkid_make_template is the same launch on one channel whose
+// records are all ready (g = 1, R = ready = P, no filter), so a channel of a bank and the same
+// records run alone give the same bits by construction. mkid_optimal_filter (k_tpl_optfilt) is the
+// filter stage alone. DESIGN.md §5.7 has the launches and the workspace layout.
 #include "mkid_internal.h"
 
 namespace mkid {
@@ -137,20 +139,74 @@ __device__ __forceinline__ float np_modf(float a, float b) {
     return m;
 }
 
-struct TplArgs {
-    float* I;            // [P][2000] work copy, re-referenced in place
-    float* Q;
-    int64_t P;
-    float I1m, Q1m;
-    const double* tP;    // pass-1 template (pass 2)
-    double pm, pdev;     // pass-1 peak statistics (pass 2)
-    double* rows;        // [P][2000] normalised aligned pulses
-    double* nrows;       // [P][800] noise periodograms (pass 2)
-    int32_t* accept;     // [P]
-    double* peaks;       // [P] pass-1 peak (appended iff not bad)
-    int32_t* appended;   // [P]
-    int pass;
+// Workgroup reductions of kTB threads through one scratch pair per kernel. Each returns its result
+// to every thread, with the scratch free for the next one.
+struct WgRed {
+    double v[kTB];
+    int i[kTB];
 };
+__device__ __forceinline__ WgRed& wg_red() {
+    __shared__ WgRed r;
+    return r;
+}
+template <typename T, typename Op>
+__device__ __forceinline__ T wg_reduce(T* red, T v, Op op) {
+    const int t0 = threadIdx.x;
+    red[t0] = v;
+    __syncthreads();
+    for (int o = kTB / 2; o > 0; o >>= 1) { if (t0 < o) red[t0] = op(red[t0], red[t0 + o]); __syncthreads(); }
+    const T r = red[0];
+    __syncthreads();
+    return r;
+}
+__device__ __forceinline__ double wg_sum(double v) {
+    return wg_reduce(wg_red().v, v, [](double a, double b) { return a + b; });
+}
+__device__ __forceinline__ double wg_max(double v) {
+    return wg_reduce(wg_red().v, v, [](double a, double b) { return fmax(a, b); });
+}
+__device__ __forceinline__ int wg_argmin(int i) {
+    return wg_reduce(wg_red().i, i, [](int a, int b) { return min(a, b); });
+}
+// index of the largest v, the smallest index among equals
+__device__ __forceinline__ int wg_argmax_first(double v, int i) {
+    double* red = wg_red().v;
+    int* redi = wg_red().i;
+    const int t0 = threadIdx.x;
+    red[t0] = v;
+    redi[t0] = i;
+    __syncthreads();
+    for (int o = kTB / 2; o > 0; o >>= 1) {
+        if (t0 < o && (red[t0 + o] > red[t0] || (red[t0 + o] == red[t0] && redi[t0 + o] < redi[t0]))) {
+            red[t0] = red[t0 + o];
+            redi[t0] = redi[t0 + o];
+        }
+        __syncthreads();
+    }
+    const int r = redi[0];
+    __syncthreads();
+    return r;
+}
+
+// The direct 800-point DFT in float64: tw[k] = exp(-2 pi i k / 800) by the whole workgroup (the
+// caller synchronises), and one row's walk, term(n, tw[n f mod 800]) for n = 0..799 in that order.
+__device__ __forceinline__ void dft_twiddles(double* twr, double* twi) {
+    for (int k = threadIdx.x; k < kTNoise; k += kTB) {
+        double sn, cs;
+        sincospi(-2.0 * k / kTNoise, &sn, &cs);
+        twr[k] = cs;
+        twi[k] = sn;
+    }
+}
+template <typename F>
+__device__ __forceinline__ void dft_row(int f, const double* twr, const double* twi, F term) {
+    int ph = 0;
+    for (int n = 0; n < kTNoise; ++n) {
+        term(n, twr[ph], twi[ph]);
+        ph += f;
+        if (ph >= kTNoise) ph -= kTNoise;
+    }
+}
 
 // One pulse as its workgroup sees it: the scalars of its set and its own slots of the set's tables.
 struct TplPulse {
@@ -167,21 +223,13 @@ struct TplPulse {
                          // pass 1 re-referenced already and whose source was left as it was
 };
 
-// Where a pulse's samples come from. The single-set kernels read a work copy and write the
-// re-referenced samples back (the reference edits its table); the bank kernels read the caller's
-// records, I/Q or phase, and write nothing back.
-struct SrcWorkCopy {
-    float* I;
-    float* Q;
-    __device__ __forceinline__ void load(int t, float& i, float& q) const { i = I[t]; q = Q[t]; }
-    __device__ __forceinline__ void store(int t, float i, float q) const { I[t] = i; Q[t] = q; }
-};
 // I = cos(sign phi), Q = sin(sign phi), float32: template.iq_from_phase on the device
 __device__ __forceinline__ void phase_iq(float sign, float phi, float& i, float& q) {
     const float a = sign * phi;
     i = cosf(a);
     q = sinf(a);
 }
+// Where a pulse's samples come from: the caller's record, I/Q or phase, read only.
 struct SrcBank {
     const float* I;      // this pulse's record: I, or phase (rad) where Q is null
     const float* Q;
@@ -190,32 +238,26 @@ struct SrcBank {
         if (Q) { i = I[t]; q = Q[t]; }
         else phase_iq(sign, I[t], i, q);
     }
-    __device__ __forceinline__ void store(int, float, float) const {}
 };
 
-// One pulse: prep (re-reference, phase, unwrap, baseline) then the pass's selection. The one
-// definition behind k_tpl_pulse (single set) and k_bank_pulse (record bank).
-template <typename Src>
-__device__ __forceinline__ void tpl_pulse(const Src src, const TplPulse a) {
+// One pulse: prep (re-reference, phase, unwrap, baseline) then the pass's selection.
+__device__ __forceinline__ void tpl_pulse(const SrcBank src, const TplPulse a) {
     __shared__ float sI[kTN], sQ[kTN], sP2[kTN];
     __shared__ double sP3[kTN];
     __shared__ double sA[600];
-    __shared__ double red[kTB];
-    __shared__ int redi[kTB];
     __shared__ double s_fit[2];
     __shared__ int s_bad;
     const int t0 = threadIdx.x;
     for (int t = t0; t < kTN; t += kTB) src.load(t, sI[t], sQ[t]);
     __syncthreads();
     for (int r = 0; r < a.nref; ++r) {
-        // I += I1m - median(I[1:900]) (float32), written back: the reference edits its table
+        // I += I1m - median(I[1:900]) (float32)
         const float mI = wg_median([&](int i) { return sI[1 + i]; }, 899);
         const float mQ = wg_median([&](int i) { return sQ[1 + i]; }, 899);
         const float dI = a.I1m - mI, dQ = a.Q1m - mQ;
         for (int t = t0; t < kTN; t += kTB) {
             sI[t] += dI;
             sQ[t] += dQ;
-            src.store(t, sI[t], sQ[t]);
             sP2[t] = atan2f(sQ[t] - 0.0f, sI[t] - 0.0f);  // P1 (xc = yc = 0, pulses.py:274-275)
         }
         __syncthreads();
@@ -244,16 +286,8 @@ __device__ __forceinline__ void tpl_pulse(const Src src, const TplPulse a) {
         double sx = 0, sy = 0;
         for (int t = t0; t < kTN; t += kTB)
             if (t < 900 || t >= 1800) { sx += 2.0 * t; sy += (double)sP2[t]; }
-        red[t0] = sx;
-        __syncthreads();
-        for (int o = kTB / 2; o > 0; o >>= 1) { if (t0 < o) red[t0] += red[t0 + o]; __syncthreads(); }
-        const double xm = red[0] / 1100.0;
-        __syncthreads();
-        red[t0] = sy;
-        __syncthreads();
-        for (int o = kTB / 2; o > 0; o >>= 1) { if (t0 < o) red[t0] += red[t0 + o]; __syncthreads(); }
-        const double ym = red[0] / 1100.0;
-        __syncthreads();
+        const double xm = wg_sum(sx) / 1100.0;
+        const double ym = wg_sum(sy) / 1100.0;
         double sxy = 0, sxx = 0;
         for (int t = t0; t < kTN; t += kTB)
             if (t < 900 || t >= 1800) {
@@ -261,16 +295,10 @@ __device__ __forceinline__ void tpl_pulse(const Src src, const TplPulse a) {
                 sxy += dx * ((double)sP2[t] - ym);
                 sxx += dx * dx;
             }
-        red[t0] = sxy;
-        __syncthreads();
-        for (int o = kTB / 2; o > 0; o >>= 1) { if (t0 < o) red[t0] += red[t0 + o]; __syncthreads(); }
-        const double cxy = red[0];
-        __syncthreads();
-        red[t0] = sxx;
-        __syncthreads();
-        for (int o = kTB / 2; o > 0; o >>= 1) { if (t0 < o) red[t0] += red[t0 + o]; __syncthreads(); }
+        const double cxy = wg_sum(sxy);
+        const double cxx = wg_sum(sxx);
         if (t0 == 0) {
-            s_fit[0] = cxy / red[0];
+            s_fit[0] = cxy / cxx;
             s_fit[1] = ym - s_fit[0] * xm;
         }
         __syncthreads();
@@ -293,28 +321,17 @@ __device__ __forceinline__ void tpl_pulse(const Src src, const TplPulse a) {
     // max over all of P3 (normalisation) and the pass's peak search
     double mx = -INFINITY;
     for (int t = t0; t < kTN; t += kTB) mx = fmax(mx, sP3[t]);
-    red[t0] = mx;
-    __syncthreads();
-    for (int o = kTB / 2; o > 0; o >>= 1) { if (t0 < o) red[t0] = fmax(red[t0], red[t0 + o]); __syncthreads(); }
-    const double pmax = red[0];
-    __syncthreads();
+    const double pmax = wg_max(mx);
     int shift = 0;
     bool ok = true;
     if (a.pass == 1) {
         double pk = -INFINITY;
         for (int t = 980 + t0; t < 1050; t += kTB) pk = fmax(pk, sP3[t]);
-        red[t0] = pk;
-        __syncthreads();
-        for (int o = kTB / 2; o > 0; o >>= 1) { if (t0 < o) red[t0] = fmax(red[t0], red[t0 + o]); __syncthreads(); }
-        const double peak = red[0];
-        __syncthreads();
+        const double peak = wg_max(pk);
         int first = kTN;
         for (int t = t0; t < kTN; t += kTB)
             if (sP3[t] == peak && t < first) first = t;
-        redi[t0] = first;
-        __syncthreads();
-        for (int o = kTB / 2; o > 0; o >>= 1) { if (t0 < o) redi[t0] = min(redi[t0], redi[t0 + o]); __syncthreads(); }
-        const int ploc = redi[0];
+        const int ploc = wg_argmin(first);
         if (t0 == 0) { *a.peak = peak; *a.appended = 1; }
         ok = !(peak < 15.0 || peak > 120.0) && !(ploc < 980 || ploc > 1020);
         shift = 1000 - ploc;
@@ -330,17 +347,7 @@ __device__ __forceinline__ void tpl_pulse(const Src src, const TplPulse a) {
             for (int k = klo; k <= khi; ++k) s += sA[k] * sP3[n - k];
             if (s > best) { best = s; bi = n; }
         }
-        red[t0] = best;
-        redi[t0] = bi;
-        __syncthreads();
-        for (int o = kTB / 2; o > 0; o >>= 1) {
-            if (t0 < o && (red[t0 + o] > red[t0] || (red[t0 + o] == red[t0] && redi[t0 + o] < redi[t0]))) {
-                red[t0] = red[t0 + o];
-                redi[t0] = redi[t0 + o];
-            }
-            __syncthreads();
-        }
-        const int ploc = redi[0] - 1160;
+        const int ploc = wg_argmax_first(best, bi) - 1160;
         int pi = 1000 + ploc;
         if (pi < 0) pi += kTN;  // numpy negative index
         const bool inr = pi >= 0 && pi < kTN;  // out of range: the reference raises; skipped here
@@ -365,12 +372,7 @@ __device__ __forceinline__ void tpl_pulse(const Src src, const TplPulse a) {
         __shared__ double win[kTNoise];
         double* twr = reinterpret_cast<double*>(sI);  // 800 doubles = 6400 B <= 8000 B
         double* twi = reinterpret_cast<double*>(sQ);
-        for (int k = t0; k < kTNoise; k += kTB) {
-            double sn, cs;
-            sincospi(-2.0 * k / kTNoise, &sn, &cs);
-            twr[k] = cs;
-            twi[k] = sn;
-        }
+        dft_twiddles(twr, twi);
         for (int t = t0; t < kTNoise; t += kTB) {
             int src = 50 + t - shift;
             src %= kTN;
@@ -381,24 +383,13 @@ __device__ __forceinline__ void tpl_pulse(const Src src, const TplPulse a) {
         double* nrow = a.nrow;
         for (int f = t0; f < kTNoise; f += kTB) {
             double re = 0.0, im = 0.0;
-            int ph = 0;
-            for (int n = 0; n < kTNoise; ++n) {
-                re += win[n] * twr[ph];
-                im += win[n] * twi[ph];
-                ph += f;
-                if (ph >= kTNoise) ph -= kTNoise;
-            }
+            dft_row(f, twr, twi, [&](int n, double c, double s) {
+                re += win[n] * c;
+                im += win[n] * s;
+            });
             nrow[f] = re * re + im * im;
         }
     }
-}
-
-__global__ __launch_bounds__(kTB) void k_tpl_pulse(TplArgs a) {
-    const int64_t j = blockIdx.x;
-    if (j >= a.P) return;
-    tpl_pulse(SrcWorkCopy{a.I + j * kTN, a.Q + j * kTN},
-              TplPulse{a.I1m, a.Q1m, a.tP, a.pm, a.pdev, a.rows + j * kTN, a.nrows + j * kTNoise, a.accept + j,
-                       a.peaks + j, a.appended + j, a.pass, 1});
 }
 
 // column sums over accepted rows in pulse order; out[t] = sum / count
@@ -411,10 +402,6 @@ __device__ __forceinline__ void tpl_colsum(const double* rows, const int32_t* ac
     out[t] = s / n;
     if (t == 0) *count = n;
 }
-__global__ void k_tpl_colsum(const double* rows, const int32_t* accept, int64_t P, int width, double* out,
-                             double* count) {
-    tpl_colsum(rows, accept, P, width, blockIdx.x * blockDim.x + threadIdx.x, out, count);
-}
 
 // global reference medians I1m, Q1m over pulses [0, min(P,100)) x samples [0, 900); get(pulse,
 // sample, i, q) reads one sample of the set
@@ -425,10 +412,6 @@ __device__ __forceinline__ void tpl_refmed(G get, int64_t P, float* out) {
     const float mi = wg_median([&](int k) { float i, q; get(k / 900, k % 900, i, q); return i; }, n);
     const float mq = wg_median([&](int k) { float i, q; get(k / 900, k % 900, i, q); return q; }, n);
     if (threadIdx.x == 0) { out[0] = mi; out[1] = mq; }
-}
-__global__ void k_tpl_refmed(const float* I, const float* Q, int64_t P, float* out) {
-    tpl_refmed([&](int p, int t, float& i, float& q) { i = I[(int64_t)p * kTN + t]; q = Q[(int64_t)p * kTN + t]; },
-               P, out);
 }
 
 // pm, pdev: median / std of appended pass-1 peaks > 15 (pulses.py:334-336), in pulse order; one
@@ -451,35 +434,24 @@ __device__ void tpl_peakstats(const double* peaks, const int32_t* appended, int6
     }
     out[0] = (n & 1) ? scratch[n / 2] : (scratch[n / 2 - 1] + scratch[n / 2]) / 2.0;
 }
-__global__ void k_tpl_peakstats(const double* peaks, const int32_t* appended, int64_t P, double* out,
-                                double* scratch) {
-    if (threadIdx.x == 0) tpl_peakstats(peaks, appended, P, out, scratch);
+
+// first index of the template's maximum (kTN when every sample is NaN), by a whole workgroup
+__device__ __forceinline__ int tpl_peak(const double* tpl) {
+    double best = -INFINITY;
+    int bi = kTN;
+    for (int t = threadIdx.x; t < kTN; t += kTB)
+        if (tpl[t] > best || (tpl[t] == best && t < bi)) { best = tpl[t]; bi = t; }
+    return wg_argmax_first(best, bi);
 }
 
 // near-optimal filter: s = deg2rad(template[pk-pre : pk-pre+800]); H = S / J, H[0] = 0;
 // g = real(ifft(H)) (correlation weights), g /= g.s; coeff = g[pre-10 : pre-10+ncoeff]. By a whole
-// workgroup of kTB threads; returns the first index of the template's maximum (every thread).
+// workgroup of kTB threads; returns pk = tpl_peak(tpl) (every thread).
 __device__ __forceinline__ int tpl_optfilt(const double* tpl, const double* noise, int pre, int ncoeff,
                                            double* coeff, double* work) {
     __shared__ double s[kTNoise];
-    __shared__ double red[kTB];
-    __shared__ int redi[kTB];
     const int t0 = threadIdx.x;
-    double best = -INFINITY;
-    int bi = kTN;
-    for (int t = t0; t < kTN; t += kTB)
-        if (tpl[t] > best || (tpl[t] == best && t < bi)) { best = tpl[t]; bi = t; }
-    red[t0] = best;
-    redi[t0] = bi;
-    __syncthreads();
-    for (int o = kTB / 2; o > 0; o >>= 1) {
-        if (t0 < o && (red[t0 + o] > red[t0] || (red[t0 + o] == red[t0] && redi[t0 + o] < redi[t0]))) {
-            red[t0] = red[t0 + o];
-            redi[t0] = redi[t0 + o];
-        }
-        __syncthreads();
-    }
-    const int pk = redi[0];
+    const int pk = tpl_peak(tpl);
     const int p0 = pk - pre;
     for (int t = t0; t < kTNoise; t += kTB) {
         const int i = p0 + t;
@@ -490,22 +462,14 @@ __device__ __forceinline__ int tpl_optfilt(const double* tpl, const double* nois
     double* Hi = work + kTNoise;
     double* g = work + 2 * kTNoise;
     __shared__ double twr[kTNoise], twi[kTNoise];
-    for (int k = t0; k < kTNoise; k += kTB) {
-        double sn, cs;
-        sincospi(-2.0 * k / kTNoise, &sn, &cs);
-        twr[k] = cs;
-        twi[k] = sn;
-    }
+    dft_twiddles(twr, twi);
     __syncthreads();
     for (int f = t0; f < kTNoise; f += kTB) {
         double re = 0.0, im = 0.0;
-        int ph = 0;
-        for (int n = 0; n < kTNoise; ++n) {
-            re += s[n] * twr[ph];
-            im += s[n] * twi[ph];
-            ph += f;
-            if (ph >= kTNoise) ph -= kTNoise;
-        }
+        dft_row(f, twr, twi, [&](int n, double c, double sn) {
+            re += s[n] * c;
+            im += s[n] * sn;
+        });
         const double J = noise[f];
         Hr[f] = f == 0 ? 0.0 : re / J;
         Hi[f] = f == 0 ? 0.0 : im / J;
@@ -513,21 +477,15 @@ __device__ __forceinline__ int tpl_optfilt(const double* tpl, const double* nois
     __syncthreads();
     for (int m = t0; m < kTNoise; m += kTB) {
         double re = 0.0;
-        int ph = 0;
-        for (int f = 0; f < kTNoise; ++f) {
-            re += Hr[f] * twr[ph] + Hi[f] * twi[ph];  // exp(+i theta) = conj(tw)
-            ph += m;
-            if (ph >= kTNoise) ph -= kTNoise;
-        }
+        dft_row(m, twr, twi, [&](int f, double c, double sn) {
+            re += Hr[f] * c + Hi[f] * sn;  // exp(+i theta) = conj(tw)
+        });
         g[m] = re / kTNoise;
     }
     __syncthreads();
     double d = 0.0;
     for (int m = t0; m < kTNoise; m += kTB) d += g[m] * s[m];
-    red[t0] = d;
-    __syncthreads();
-    for (int o = kTB / 2; o > 0; o >>= 1) { if (t0 < o) red[t0] += red[t0 + o]; __syncthreads(); }
-    const double norm = red[0];
+    const double norm = wg_sum(d);
     const int k0 = pre - 10;
     for (int i = t0; i < ncoeff; i += kTB) {
         const int m = k0 + i;
@@ -590,7 +548,7 @@ __global__ void k_bank_colsum(BankArgs a, int which) {
                a.stats + 8 * b + (which == 0 ? 3 : 4));
 }
 
-// pm, pdev; then the first of the host's two decisions: no pulse passed pass 1
+// pm, pdev; then the first of the two status decisions: no pulse passed pass 1
 __global__ void k_bank_peakstats(BankArgs a) {
     const int b = blockIdx.x;
     if (threadIdx.x != 0 || a.status[b]) return;
@@ -601,7 +559,8 @@ __global__ void k_bank_peakstats(BankArgs a) {
     if (!(st[3] > 0)) a.status[b] = 2;
 }
 
-// the second decision (none passed pass 2), pstart and flag, the filter, and the caller's rows
+// the second decision (none passed pass 2), pstart and flag, the filter (where out_coeff is given),
+// and the caller's rows: written at status 0 only
 __global__ __launch_bounds__(kTB) void k_bank_finish(BankArgs a) {
     const int b = blockIdx.x;
     const int64_t c = a.c0 + b;
@@ -622,9 +581,14 @@ __global__ __launch_bounds__(kTB) void k_bank_finish(BankArgs a) {
     }
     const double* tpl = a.tPf + (int64_t)b * kTN;
     const double* noise = a.noise + (int64_t)b * kTNoise;
-    double* co = a.coeff + (int64_t)b * kTNoise;
-    const int pk = tpl_optfilt(tpl, noise, a.pre, a.ncoeff, co, a.work + (int64_t)b * 3 * kTNoise);
-    for (int i = t0; i < a.ncoeff; i += kTB) a.out_coeff[c * a.ncoeff + i] = (float)co[i];  // own writes
+    int pk;
+    if (a.out_coeff) {
+        double* co = a.coeff + (int64_t)b * kTNoise;
+        pk = tpl_optfilt(tpl, noise, a.pre, a.ncoeff, co, a.work + (int64_t)b * 3 * kTNoise);
+        for (int i = t0; i < a.ncoeff; i += kTB) a.out_coeff[c * a.ncoeff + i] = (float)co[i];  // own writes
+    } else {
+        pk = tpl_peak(tpl);   // mkid_make_template: no filter, pstart alone
+    }
     if (a.out_tpl)
         for (int t = t0; t < kTN; t += kTB) a.out_tpl[c * kTN + t] = tpl[t];
     if (a.out_noise)
@@ -633,7 +597,7 @@ __global__ __launch_bounds__(kTB) void k_bank_finish(BankArgs a) {
         mkid_bank_result r{};
         r.count = st[4]; r.count1 = st[3]; r.pm = st[0]; r.pdev = st[1];
         r.flag = (st[4] < 500 || st[0] < 10 || st[0] > 150) ? 1 : 0;
-        // the host's scan `if (t[i] > t[ps]) ps = i` from ps = 0: the first maximum; 0 when t[0] is NaN
+        // the scan `if (t[i] > t[ps]) ps = i` from ps = 0: the first maximum; 0 when t[0] is NaN
         r.pstart = (pk >= kTN || tpl[0] != tpl[0]) ? 0 : pk;
         r.status = 0;
         r.ready = a.nready[b];
@@ -651,40 +615,6 @@ hipError_t launch_bank_filters(const BankArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(k_bank_colsum, dim3((kTN + 255) / 256, g), dim3(256), 0, s, a, 1);
     hipLaunchKernelGGL(k_bank_colsum, dim3((kTNoise + 255) / 256, g), dim3(256), 0, s, a, 2);
     hipLaunchKernelGGL(k_bank_finish, dim3(g), dim3(kTB), 0, s, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_make_template(float* I, float* Q, int64_t P, double* rows, double* nrows, int32_t* accept,
-                                double* peaks, int32_t* appended, double* scratch, double* tP, double* tPf,
-                                double* noise, double* stats, float* refmed, hipStream_t s) {
-    // stats: [pm, pdev, npk, count1, count2]
-    hipLaunchKernelGGL(k_tpl_refmed, dim3(1), dim3(1024), 0, s, I, Q, P, refmed);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    float rm[2];
-    if ((e = hipMemcpyAsync(rm, refmed, 8, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
-    if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
-    TplArgs a{I, Q, P < 1000 ? P : 1000, rm[0], rm[1], nullptr, 0, 0, rows, nrows, accept, peaks, appended, 1};
-    hipLaunchKernelGGL(k_tpl_pulse, dim3((unsigned)a.P), dim3(kTB), 0, s, a);
-    hipLaunchKernelGGL(k_tpl_colsum, dim3((kTN + 255) / 256), dim3(256), 0, s, rows, accept, a.P, kTN, tP,
-                       stats + 3);
-    hipLaunchKernelGGL(k_tpl_peakstats, dim3(1), dim3(64), 0, s, peaks, appended, a.P, stats, scratch);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    double st[4];
-    if ((e = hipMemcpyAsync(st, stats, 32, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
-    if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
-    if (!(st[3] > 0)) return hipErrorInvalidValue;  // no pulse passed the first pass
-    TplArgs b = a;
-    b.P = P;
-    b.tP = tP;
-    b.pm = st[0];
-    b.pdev = st[1];
-    b.pass = 2;
-    hipLaunchKernelGGL(k_tpl_pulse, dim3((unsigned)P), dim3(kTB), 0, s, b);
-    hipLaunchKernelGGL(k_tpl_colsum, dim3((kTN + 255) / 256), dim3(256), 0, s, rows, accept, P, kTN, tPf,
-                       stats + 4);
-    hipLaunchKernelGGL(k_tpl_colsum, dim3((kTNoise + 255) / 256), dim3(256), 0, s, nrows, accept, P, kTNoise,
-                       noise, stats + 4);
     return hipGetLastError();
 }
 

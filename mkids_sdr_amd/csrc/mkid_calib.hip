@@ -38,57 +38,61 @@ int mkid_replay_trigger(mkid_ctx* c, const int16_t* d_raw, int64_t n, int64_t ld
     return MKID_OK;
 }
 
+// The workspace tables of `a` for one group of the plan `w`, in the context's bank workspace; a
+// smaller workspace is grown first (allocate, synchronise once, move in).
+static int bank_tables(mkid_ctx* c, const plan::BankWs& w, BankArgs& a) {
+    if ((size_t)w.bytes > c->bankws_n) {
+        DevBuf<char> ws;
+        HIPCHK(c, ws.alloc((size_t)w.bytes));
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // an earlier call may still use the old one
+        c->d_bankws = std::move(ws), c->bankws_n = (size_t)w.bytes;
+    }
+    char* p = c->d_bankws.get();
+    a.rows = (double*)(p + w.rows), a.nrows = (double*)(p + w.nrows), a.peaks = (double*)(p + w.peaks);
+    a.scratch = (double*)(p + w.scratch), a.tP = (double*)(p + w.tP), a.tPf = (double*)(p + w.tPf);
+    a.noise = (double*)(p + w.noise), a.stats = (double*)(p + w.stats), a.work = (double*)(p + w.work);
+    a.coeff = (double*)(p + w.coeff), a.refmed = (float*)(p + w.refmed), a.accept = (int32_t*)(p + w.accept);
+    a.appended = (int32_t*)(p + w.appended), a.status = (int32_t*)(p + w.status);
+    a.nready = (int32_t*)(p + w.nready);
+    return MKID_OK;
+}
+
+// The bank kernels on one channel whose P records are all ready, without the filter; the finish
+// kernel writes the caller's template and noise at status 0 only.
 int mkid_make_template(mkid_ctx* c, const float* d_I, const float* d_Q, int64_t P, double* d_template,
                        double* d_noise, mkid_template_info* info) {
     if (!c || !d_I || !d_Q || !d_template || !d_noise || !info) return MKID_E_ARG;
     if (P <= 0) FAIL(c, MKID_E_ARG, "make_template: need pulses");
+    if (P > INT32_MAX) FAIL(c, MKID_E_ARG, "make_template: more than 2^31 - 1 pulses");
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t N = 2000, NN = 800;
-    DevBuf<float> I, Q, refmed;
-    DevBuf<double> rows, nrows, peaks, scratch, tP, tPf, noise, stats;
-    DevBuf<int32_t> accept, appended;
-    HIPCHK(c, I.alloc((size_t)P * N));
-    HIPCHK(c, Q.alloc((size_t)P * N));
-    HIPCHK(c, rows.alloc((size_t)P * N));
-    HIPCHK(c, nrows.alloc((size_t)P * NN));
-    HIPCHK(c, peaks.alloc((size_t)P));
-    HIPCHK(c, scratch.alloc((size_t)2 * P + 8));
-    HIPCHK(c, tP.alloc(N));
-    HIPCHK(c, tPf.alloc(N));     // the caller's template and noise are written only on success
-    HIPCHK(c, noise.alloc(NN));
-    HIPCHK(c, stats.alloc(8));
-    HIPCHK(c, refmed.alloc(2));
-    HIPCHK(c, accept.alloc((size_t)P));
-    HIPCHK(c, appended.alloc((size_t)P));
+    BankArgs a{};
+    if (int rc = bank_tables(c, plan::plan_bank(1, P, plan::kBankBudget), a)) return rc;
+    if (!c->d_tplslot.get()) HIPCHK(c, c->d_tplslot.alloc(1));
+    mkid_ctx::TplSlot* slot = c->d_tplslot.get();
+    a.I = d_I, a.Q = d_Q, a.ready = &slot->ready;
+    a.out_tpl = d_template, a.out_noise = d_noise, a.result = &slot->result;
+    a.g = 1, a.R = (int32_t)P, a.ready_stride = 1;
+    const int32_t ready = (int32_t)P;
+    mkid_bank_result r{};
     hipStream_t s = c->stream;
-    HIPCHK(c, hipMemcpyAsync(I.get(), d_I, (size_t)P * N * 4, hipMemcpyDeviceToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(Q.get(), d_Q, (size_t)P * N * 4, hipMemcpyDeviceToDevice, s));
-    HIPCHK(c, hipMemsetAsync(appended.get(), 0, (size_t)P * 4, s));
-    HIPCHK(c, hipMemsetAsync(stats.get(), 0, 64, s));
-    hipError_t e = launch_make_template(I.get(), Q.get(), P, rows.get(), nrows.get(), accept.get(), peaks.get(),
-                                        appended.get(), scratch.get(), tP.get(), tPf.get(), noise.get(), stats.get(),
-                                        refmed.get(), s);
-    if (e == hipErrorInvalidValue) FAIL(c, MKID_E_STATE, "make_template: no pulse passed the first pass");
-    HIPCHK(c, e);
-    double st[5];
-    std::vector<double> t(N);
-    HIPCHK(c, hipMemcpyAsync(st, stats.get(), 40, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(t.data(), tPf.get(), N * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
+    hipError_t e = hipMemcpyAsync(&slot->ready, &ready, sizeof ready, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = launch_bank_filters(a, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&r, &slot->result, sizeof r, hipMemcpyDeviceToHost, s);
+    const hipError_t es = hipStreamSynchronize(s);   // whatever was enqueued: both copies use this frame
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) {
+        c->err = std::string("make_template: ") + hipGetErrorString(e);
+        return MKID_E_HIP;
+    }
+    if (r.status == 2) FAIL(c, MKID_E_STATE, "make_template: no pulse passed the first pass");
     // nothing accepted in pass 2: the column means are 0 / 0
-    if (!(st[4] > 0)) FAIL(c, MKID_E_STATE, "make_template: no pulse passed the second pass");
-    HIPCHK(c, hipMemcpyAsync(d_template, tPf.get(), N * 8, hipMemcpyDeviceToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_noise, noise.get(), NN * 8, hipMemcpyDeviceToDevice, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    info->pm = st[0];
-    info->pdev = st[1];
-    info->count1 = st[3];
-    info->count = st[4];
-    info->flag = (st[4] < 500 || st[0] < 10 || st[0] > 150) ? 1 : 0;
-    int ps = 0;
-    for (size_t i = 1; i < N; ++i)
-        if (t[i] > t[ps]) ps = (int)i;
-    info->pstart = ps;
+    if (r.status != 0) FAIL(c, MKID_E_STATE, "make_template: no pulse passed the second pass");
+    info->count = r.count;
+    info->count1 = r.count1;
+    info->pm = r.pm;
+    info->pdev = r.pdev;
+    info->flag = r.flag;
+    info->pstart = r.pstart;
     return MKID_OK;
 }
 
@@ -118,19 +122,12 @@ int mkid_bank_filters(mkid_ctx* c, const float* d_I, const float* d_Q, const int
     HIPCHK(c, hipSetDevice(c->device));
     const int32_t Cb = bc->n_channels;
     const plan::BankWs w = plan::plan_bank(Cb, bc->max_per_ch, plan::kBankBudget, bc->group);
-    if ((size_t)w.bytes > c->bankws_n) {   // grow the workspace
-        DevBuf<char> ws;
-        HIPCHK(c, ws.alloc((size_t)w.bytes));
-        HIPCHK(c, hipStreamSynchronize(c->stream));   // an earlier call may still use the old one
-        c->d_bankws = std::move(ws), c->bankws_n = (size_t)w.bytes;
-    }
-    char* p = c->d_bankws.get();
-    BankArgs a{d_I, d_Q, d_ready, d_templates, d_noise, d_coeff, d_result,
-               (double*)(p + w.rows), (double*)(p + w.nrows), (double*)(p + w.peaks), (double*)(p + w.scratch),
-               (double*)(p + w.tP), (double*)(p + w.tPf), (double*)(p + w.noise), (double*)(p + w.stats),
-               (double*)(p + w.work), (double*)(p + w.coeff), (float*)(p + w.refmed), (int32_t*)(p + w.accept),
-               (int32_t*)(p + w.appended), (int32_t*)(p + w.status), (int32_t*)(p + w.nready),
-               0, 0, bc->max_per_ch, bc->ready_stride, bc->min_records, bc->pre, bc->ncoeff, bc->sign};
+    BankArgs a{};
+    if (int rc = bank_tables(c, w, a)) return rc;
+    a.I = d_I, a.Q = d_Q, a.ready = d_ready;
+    a.out_tpl = d_templates, a.out_noise = d_noise, a.out_coeff = d_coeff, a.result = d_result;
+    a.R = bc->max_per_ch, a.ready_stride = bc->ready_stride, a.min_records = bc->min_records;
+    a.pre = bc->pre, a.ncoeff = bc->ncoeff, a.sign = bc->sign;
     for (int64_t c0 = 0; c0 < Cb; c0 += w.group) {   // the stream orders the groups' use of the tables
         a.c0 = (int32_t)c0;
         a.g = (int32_t)std::min<int64_t>(w.group, Cb - c0);

@@ -208,9 +208,12 @@ struct mkid_ctx : CtxHandles {
     DevBuf<uint32_t> d_rflags;
     DevBuf<double> d_rmeans;
     size_t rflags_n = 0, rmeans_n = 0;
-    // mkid_bank_filters workspace (lazy, grown on demand; plan::plan_bank carves it)
+    // workspace of mkid_bank_filters and mkid_make_template (lazy, grown on demand; plan::plan_bank
+    // carves it), and what mkid_make_template's one channel reads and writes besides (lazy)
     DevBuf<char> d_bankws;
     size_t bankws_n = 0;
+    struct TplSlot { mkid_bank_result result; int32_t ready; };
+    DevBuf<TplSlot> d_tplslot;
     // host-API staging (lazy)
     DevBuf<uint32_t> d_in;
     DevBuf<float> d_phase_ws;

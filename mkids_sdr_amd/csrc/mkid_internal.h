@@ -218,21 +218,19 @@ hipError_t launch_replay(const int16_t* raw, int64_t n, int64_t ld, int32_t nch,
                          int64_t start, int64_t need, int64_t skip, int32_t wrap, double thr, uint32_t* flags,
                          double* means, int32_t* hits, int32_t cap, int32_t* counts, hipStream_t s);
 
-hipError_t launch_make_template(float* I, float* Q, int64_t P, double* rows, double* nrows, int32_t* accept,
-                                double* peaks, int32_t* appended, double* scratch, double* tP, double* tPf,
-                                double* noise, double* stats, float* refmed, hipStream_t s);
 hipError_t launch_optimal_filter(const double* tpl, const double* noise, int pre, int ncoeff, double* coeff,
                                  double* work, hipStream_t s);
 
-// mkid_bank_filters (k_template.hip): one group of g channels, c0 .. c0 + g - 1, of the caller's
-// bank. The workspace tables hold one slot per channel of the group (plan::BankWs gives their sizes).
+// mkid_bank_filters and mkid_make_template (k_template.hip): one group of g channels, c0 .. c0 + g - 1,
+// of the caller's bank. The workspace tables hold one slot per channel of the group (plan::BankWs
+// gives their sizes).
 struct BankArgs {
     const float* I;          // [Cb][R][2000] records: I, or phase (rad) where Q is null
     const float* Q;
     const int32_t* ready;    // [Cb * ready_stride]
     double* out_tpl;         // [Cb][2000], nullable
     double* out_noise;       // [Cb][800], nullable
-    float* out_coeff;        // [Cb][ncoeff]
+    float* out_coeff;        // [Cb][ncoeff]; null: no filter is made (pre, ncoeff unused)
     mkid_bank_result* result;  // [Cb]
     double* rows;            // [g][R][2000]
     double* nrows;           // [g][R][800]

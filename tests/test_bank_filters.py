@@ -1,10 +1,13 @@
 """mkid_bank_filters (k_template.hip, mkid_calib.hip): every channel's template and pulse filter
 from a record bank in one device call.
 
-IQ mode must equal mkid_make_template + mkid_optimal_filter on each channel's set bit for bit, so
-the single path is the reference there and the oracle check of tests/test_gpu_template.py rides on
-top. Phase mode forms I = cosf(sign phi), Q = sinf(sign phi) on the device, where the loop path
-takes numpy's float32 cos / sin: the CPU test below shows that moving I, Q and the arctan2 by
+mkid_make_template runs the same kernels on one channel whose records are all ready, so in IQ mode
+a channel at any slot of a grouped bank must equal mkid_make_template + mkid_optimal_filter on the
+same records run alone (R = P) bit for bit; that pins the indexing by (channel, pulse), the stop at
+ready_c and the grouping, not the arithmetic. The independent reference for the arithmetic is the
+oracle: its check of tests/test_gpu_template.py runs on the single call there and on every used
+channel here. Phase mode forms I = cosf(sign phi), Q = sinf(sign phi) on the device, where the
+loop path takes numpy's float32 cos / sin: the CPU test below shows that moving I, Q and the arctan2 by
 +-2 ulp leaves every decision of the oracle on these sets alone and stays inside the bars that the
 GPU test then uses, which is what makes exact counts and those bars a fair demand.
 """
@@ -209,7 +212,7 @@ def iq_bank(ch):
 
 @pytest.fixture(scope='module')
 def single(ch):
-    """mkid_make_template + mkid_optimal_filter on each used set of the IQ bank: the single path."""
+    """mkid_make_template + mkid_optimal_filter on each used set of the IQ bank, run alone (R = P)."""
     from mkids_sdr_amd import template
     out = {}
     for c, (I, Q, ready, status, _) in enumerate(iq_sets()):
@@ -230,9 +233,10 @@ def _equals_single(got, c, want):
 
 @on_gpu
 def test_iq_mode_equals_single_path_bit_for_bit(iq_bank, single):
-    """Every used channel of an 11-channel bank (R = 257) equals the two single-set calls on its set
-    bit for bit and passes the oracle check of tests/test_gpu_template.py; the channels with one pulse
-    among flat rows, flat rows only, 5 records and none say status 3, 2, 1, 1."""
+    """Every used channel of an 11-channel bank (R = 257), at slots b = 0..6 of its group with 24 to
+    257 of the 257 records ready, equals the same records run alone (mkid_make_template at R = P, then
+    mkid_optimal_filter) bit for bit and passes the oracle check of tests/test_gpu_template.py; the
+    channels with one pulse among flat rows, flat rows only, 5 records and none say status 3, 2, 1, 1."""
     from test_gpu_template import _check
     got = iq_bank[3]
     sets = iq_sets()
@@ -251,8 +255,10 @@ def test_iq_mode_equals_single_path_bit_for_bit(iq_bank, single):
 
 @on_gpu
 def test_iq_mode_first_pass_cap(ch):
-    """1003 pulses in a bank of R = 1003: pass 1 stops at 1000 pulses, pass 2 re-references those
-    1000 a second time and the last three once, as the single path does."""
+    """1003 pulses per channel in a two-channel bank of R = 1003: pass 1 stops at 1000 pulses, pass 2
+    re-references those 1000 a second time and the last three once. The channel at slot 1 and the one
+    at slot 0 equal the same records run alone at R = P = 1003 bit for bit, and both pass the oracle
+    check."""
     from mkids_sdr_amd import template
     from test_gpu_template import _check
     sets = [tp.case('cat', 1003, 0)[:2] + (1003,), tp.case('cat', 1003, 168)[:2] + (1003,)]
@@ -431,3 +437,64 @@ def test_bad_requests_are_refused_before_any_launch(ch):
         assert _raw_call(ch, *args) == _lib.MKID_E_ARG
     for o, k in zip(outs, keep):
         assert torch.equal(o, k)
+
+
+# ---- mkid_make_template: the same launch on one channel --------------------------------------------
+
+FIRST = b'make_template: no pulse passed the first pass'
+SECOND = b'make_template: no pulse passed the second pass'
+
+
+@on_gpu
+@pytest.mark.parametrize('rows,P,message', [('flat', 24, FIRST), ('one_good', 24, SECOND), ('flat', 1, FIRST),
+                                            ('one_good', 1, SECOND)])
+def test_make_template_failure_leaves_outputs_alone(ch, rows, P, message):
+    """Flat rows only (no pulse passes pass 1) and one good pulse among flat rows or alone (none
+    passes pass 2), through the raw entry point with the template and noise pre-filled with the NaN
+    pattern and info with a byte pattern: MKID_E_STATE with the pass's message, and every output
+    byte as it was."""
+    import torch
+    from mkids_sdr_amd import _lib
+    I, Q = _flat_rows(P) if rows == 'flat' else tp.one_good_among_flat(P)
+    dI, dQ = torch.from_numpy(I).cuda(), torch.from_numpy(Q).cuda()
+    tpl = torch.full((2000,), F64_SENTINEL, dtype=torch.int64, device='cuda')
+    noise = torch.full((800,), F64_SENTINEL, dtype=torch.int64, device='cuda')
+    info = _lib.TemplateInfo()
+    ctypes.memset(ctypes.byref(info), 0x5A, ctypes.sizeof(info))
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    torch.cuda.synchronize()
+    rc = ch._L.mkid_make_template(ch._h, p(dI), p(dQ), P, p(tpl), p(noise), ctypes.byref(info))
+    torch.cuda.synchronize()
+    assert rc == _lib.MKID_E_STATE and ch._L.mkid_last_error(ch._h) == message
+    assert (tpl.cpu().numpy() == F64_SENTINEL).all() and (noise.cpu().numpy() == F64_SENTINEL).all()
+    assert bytes(info) == b'\x5a' * ctypes.sizeof(info)
+
+
+def _template_bits(r):
+    return (r['template'].tobytes() + r['noise'].tobytes()
+            + np.array([r[k] for k in ('count', 'count1', 'pm', 'pdev')], np.float64).tobytes()
+            + np.array([r['flag'], r['pstart']], np.int32).tobytes())
+
+
+@on_gpu
+def test_make_template_and_bank_filters_share_one_workspace(gpu, iq_bank):
+    """On a context of its own, so that the first call finds no workspace: make_template at P = 24
+    (allocates), bank_filters on the 11-channel IQ bank (grows it), make_template at P = 257 and at
+    24 again (the bank's larger workspace, reused), bank_filters again. The two P = 24 results are
+    the same bits, and so are the two bank results, which are also those of the module's context."""
+    from mkids_sdr_amd import template
+    from mkids_sdr_amd.channelizer import Channelizer
+    I, Q, info, plain = iq_bank
+    c = Channelizer(64, max_chunk=1 << 14)
+    try:
+        one = lambda P: template.make_template(c, *(a.copy() for a in tp.case('cat', P, 0)[:2]))
+        first24 = one(24)
+        bank1 = _run(c, I, Q, info)
+        big = one(257)
+        again24 = one(24)
+        bank2 = _run(c, I, Q, info)
+    finally:
+        c.close()
+    assert _template_bits(first24) == _template_bits(again24) != _template_bits(big)
+    _same_bits(bank1, bank2)
+    _same_bits(bank1, plain)

@@ -90,8 +90,10 @@ def test_device_filters_from_bank_takes_the_fallback(ch):
 
 
 def test_device_template_leaves_inputs_alone_and_repeats(ch):
-    """include/mkidgpu.h: the pulses are "not modified" (the kernel re-references a work copy), and
-    k_template.hip accumulates in pulse order: two runs give the same bits."""
+    """include/mkidgpu.h: the pulses are "not modified" (the kernels read them where they lie and
+    write nothing back), and k_template.hip accumulates in pulse order: two runs give the same bits.
+    Nothing beyond npulses rows is read: the same 24 pulses at the head of [27][2000] tensors whose
+    last three rows are NaN give the same bits again and leave all 27 rows as they were."""
     import torch
     from mkids_sdr_amd import template
     I, Q, _ = tp.case('cat', 24, 180)
@@ -101,6 +103,16 @@ def test_device_template_leaves_inputs_alone_and_repeats(ch):
     b = template.make_template(ch, dI, dQ)
     assert np.array_equal(a['template'], b['template']) and np.array_equal(a['noise'], b['noise'])
     assert (a['count1'], a['count'], a['pm'], a['pdev']) == (b['count1'], b['count'], b['pm'], b['pdev'])
+    nan3 = np.full((3, 2000), np.nan, np.float32)
+    wI, wQ = (torch.from_numpy(np.concatenate((x, nan3))).cuda() for x in (I, Q))
+    before = [w.view(dtype=torch.int32).clone() for w in (wI, wQ)]
+    assert wI[:24].is_contiguous() and wI[:24].data_ptr() == wI.data_ptr()   # npulses = 24 of the 27 rows
+    c = template.make_template(ch, wI[:24], wQ[:24])
+    for k in ('template', 'noise'):
+        assert np.array_equal(a[k].view(np.uint64), c[k].view(np.uint64)), k
+    for k in ('count', 'count1', 'pm', 'pdev', 'flag', 'pstart'):
+        assert a[k] == c[k], k
+    assert torch.equal(wI.view(dtype=torch.int32), before[0]) and torch.equal(wQ.view(dtype=torch.int32), before[1])
 
 
 @pytest.mark.parametrize('peak,pre,ncoeff', tp.FILTER_WINDOW_CASES)

@@ -350,10 +350,33 @@ static void fuzz_carry(int iters) {
     }
 }
 
-// plan_bank (mkid_bank_filters' workspace): group >= 1, the workspace within the budget whenever one
-// channel fits, the groups covering 0..Cb-1 once, and the tables' writes (one slot per channel of the
-// group, sizes of BankArgs in mkid_internal.h) replayed into a buffer of exactly the planned size
+// table extents of a plan for R records per channel: offset + group * per-channel bytes (sizes of
+// BankArgs in mkid_internal.h), ascending, aligned, inside `bytes`; the last slot of every table is
+// written into a buffer of exactly the planned size when that is small
+static void check_bank_tables(const BankWs& w, int64_t R) {
+    const int64_t off[15] = {w.rows, w.nrows, w.peaks, w.scratch, w.tP,       w.tPf,    w.noise, w.stats,
+                             w.work, w.coeff, w.refmed, w.accept, w.appended, w.status, w.nready};
+    const int64_t per[15] = {R * 16000, R * 6400, R * 8, (2 * R + 8) * 8, 16000, 16000, 6400, 64,
+                             19200,     6400,     8,     R * 4,           R * 4, 4,     4};
+    int64_t sum = 0;
+    for (int i = 0; i < 15; ++i) {
+        sum += per[i];
+        CHECK(off[i] % kBankAlign == 0 && off[i] + w.group * per[i] <= (i < 14 ? off[i + 1] : w.bytes),
+              "table %d overlaps the next", i);
+    }
+    CHECK(off[0] == 0 && sum == w.channel_bytes, "channel bytes %lld, tables %lld", (long long)w.channel_bytes,
+          (long long)sum);
+    if (w.bytes <= (1 << 22)) {
+        std::vector<char> buf((size_t)w.bytes);
+        for (int i = 0; i < 15; ++i) buf[(size_t)(off[i] + w.group * per[i] - 1)] = 1;
+    }
+}
+
+// plan_bank (the workspace of mkid_bank_filters and mkid_make_template): group >= 1, the workspace
+// within the budget whenever one channel fits, the groups covering 0..Cb-1 once, and the tables of
+// the bank's plan and of the one-channel plan that mkid_make_template asks for
 static void fuzz_bank(int iters) {
+    int over = 0;
     for (int it = 0; it < iters; ++it) {
         const int64_t Cb = rint_(0, 3) == 0 ? rint_(1, 4) : rint_(1, 100000);
         const int64_t R = rint_(0, 3) == 0 ? rint_(1, 8) : (rint_(0, 5) == 0 ? rint_(1, 3000000) : rint_(1, 1200));
@@ -374,24 +397,18 @@ static void fuzz_bank(int iters) {
         for (int64_t c0 = 0; c0 < Cb; c0 += w.group)
             for (int64_t b = 0; b < std::min(w.group, Cb - c0); ++b) ++seen[(size_t)(c0 + b)];
         CHECK(std::all_of(seen.begin(), seen.end(), [](int32_t n) { return n == 1; }), "groups do not cover the bank once");
-        // table extents: offset + group * per-channel bytes, ascending, aligned, inside `bytes`
-        const int64_t off[15] = {w.rows, w.nrows, w.peaks, w.scratch, w.tP,       w.tPf,    w.noise, w.stats,
-                                 w.work, w.coeff, w.refmed, w.accept, w.appended, w.status, w.nready};
-        const int64_t per[15] = {R * 16000, R * 6400, R * 8, (2 * R + 8) * 8, 16000, 16000, 6400, 64,
-                                 19200,     6400,     8,     R * 4,           R * 4, 4,     4};
-        int64_t sum = 0;
-        for (int i = 0; i < 15; ++i) {
-            sum += per[i];
-            CHECK(off[i] % kBankAlign == 0 && off[i] + w.group * per[i] <= (i < 14 ? off[i + 1] : w.bytes),
-                  "table %d overlaps the next", i);
-        }
-        CHECK(off[0] == 0 && sum == w.channel_bytes, "channel bytes %lld, tables %lld", (long long)w.channel_bytes,
-              (long long)sum);
-        if (w.bytes <= (1 << 22)) {   // the last slot of every table, written
-            std::vector<char> buf((size_t)w.bytes);
-            for (int i = 0; i < 15; ++i) buf[(size_t)(off[i] + w.group * per[i] - 1)] = 1;
-        }
+        check_bank_tables(w, R);
+        // mkid_make_template's request: one channel of R = P pulses at the product's budget, which
+        // one channel alone exceeds from R = 11 964 on
+        const BankWs tpl = plan_bank(1, R, kBankBudget);
+        CHECK(tpl.group == 1 && tpl.bytes >= tpl.channel_bytes &&
+                  tpl.bytes <= tpl.channel_bytes + 15 * (kBankAlign - 1),
+              "make_template: group %lld, %lld bytes for R %lld", (long long)tpl.group, (long long)tpl.bytes,
+              (long long)R);
+        over += tpl.bytes > kBankBudget;
+        check_bank_tables(tpl, R);
     }
+    CHECK(iters < 100 || over > 0, "no one-channel plan above the budget in %d iterations", iters);
 }
 
 int main(int argc, char** argv) {
