@@ -69,7 +69,9 @@ typedef struct mkid_cfg {
     int32_t dead_time;         /* trigger dead time in phase samples (build decision)         */
     int32_t max_events_per_ch; /* per-call event capacity per channel (0 = derive from chunk) */
     int32_t front;             /* MKID_FRONT_AUTO (fused K1-K6 kernel, N = 128..4096) or
-                                  MKID_FRONT_SPLIT (channeliser + low-pass kernels, z in HBM)  */
+                                  MKID_FRONT_SPLIT (channeliser + low-pass kernels one after the
+                                  other, the call's z in HBM: the reference for the fused kernels,
+                                  which every supported N has; it is not built for speed)        */
     int64_t max_chunk;         /* largest nsamples per process call (workspace sizing)        */
     double sample_rate;        /* fs, complex S/s; ROACH_Setup.py:82                           */
 } mkid_cfg;
@@ -87,7 +89,8 @@ const char* mkid_global_error(void);
 int mkid_get_cfg(const mkid_ctx* ctx, mkid_cfg* out);
 
 /* Run the context's kernels on an external hipStream_t (e.g. torch's current stream). NULL
- * restores the context's own stream. */
+ * restores the context's own stream. All device work of either front end runs on that one stream,
+ * in call order: work enqueued on it after a call sees the call's results. */
 int mkid_set_stream(mkid_ctx* ctx, void* hip_stream);
 
 /* PFB prototype filter, T*N float coefficients (build decision: the firmware's taps are not in
@@ -200,7 +203,7 @@ int mkid_read_raw_phase(mkid_ctx* ctx, int16_t* host_out, int64_t cap_rows, int6
 int mkid_set_iq_tap(mkid_ctx* ctx, int32_t channel);
 int mkid_read_iq_tap(mkid_ctx* ctx, int16_t* host_iq, int64_t cap_rows, int64_t* rows);
 
-/* Diagnostic: trigger segments of the last sub-chunk whose speculative start state had to be
+/* Diagnostic: trigger segments of the last call whose speculative start state had to be
  * re-run by the exact fix-up pass (0 = all speculation was right; results are exact either way). */
 int mkid_trigger_reruns(mkid_ctx* ctx, int64_t* total);
 

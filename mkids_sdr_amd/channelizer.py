@@ -167,7 +167,7 @@ class Channelizer:
         return p.value, n.value
 
     def raw_phase(self):
-        """Host copy of the last sub-chunk's Fix16_13 phase rows, int16 [rows][C]."""
+        """Host copy of the last call's Fix16_13 phase rows, int16 [rows][C]."""
         p, rows = self.raw_phase_ptr()
         out = np.empty((rows, self.C), np.int16)
         n = ctypes.c_int64()

@@ -7,21 +7,14 @@
 //          latency hides behind the FFT; each sample is read from HBM once (+ (2T-1)/run warm-up).
 //   PFB    u[p] = sum_tau h[tau N + p] x[(k+1)M - TN + tau N + p]  (h in registers, x from LDS)
 //   FFT    Stockham radix-8/4 passes, butterflies in registers, one twiddle base per butterfly
-//          (powers rebuilt in registers), exchanges through padded LDS. With MKID_CHAN_DBUF the
-//          passes ping-pong between two LDS buffers: one barrier per pass instead of two.
+//          (powers rebuilt in registers), exchanges through padded LDS. The passes ping-pong
+//          between two LDS buffers: one barrier per pass instead of two.
 //   K3/4   z[k][c] = X[bin_c] (-1)^(bin_c (k+1)) conj(LUT_c[k mod P]) / 2^15; LO table [P][C] so
 //          both the LO row and the z row of a frame are contiguous (coalesced)
 // Reference geometry: fft_len/channels ROACH_Setup.py:507,515; bins ROACH_Setup.py:534-550; DDS
 // LUT at 2 fs/N ROACH_Setup.py:525. Taps/window of the PFB: build decision (firmware absent).
 #include "fft_common.h"
 #include "mkid_internal.h"
-
-#ifndef MKID_CHAN_MINWAVES
-#define MKID_CHAN_MINWAVES 1
-#endif
-#ifndef MKID_CHAN_DBUF
-#define MKID_CHAN_DBUF 1
-#endif
 
 namespace mkid {
 
@@ -35,7 +28,7 @@ struct Geo {
     static constexpr int M = N / 2, C = N / 2, T = kPfbTaps;
     static constexpr int RS = 2 * T - 1 + FPB;          // ring slots (hops)
     static constexpr int LDSF = lds_frame_elems<N>();
-    static constexpr int NBUF = MKID_CHAN_DBUF ? 2 : 1;  // FFT exchange buffers per frame
+    static constexpr int NBUF = 2;                      // FFT exchange buffers per frame
     static constexpr int CPT = C / NT;                  // channels per thread in select
     static constexpr int NEW = FPB * M;                 // new samples per iteration
     static constexpr int SPT = NEW / BT;                // new samples per thread (4)
@@ -50,13 +43,12 @@ __device__ __forceinline__ uint4 load_new(const ChanArgs& a, int64_t first_hop, 
     using G = Geo<N>;
     const int64_t s0 = first_hop * G::M + (int64_t)tid * G::SPT;  // sample index in chunk
     if (s0 >= (int64_t)a.K * G::M) return make_uint4(0, 0, 0, 0);
-    if (s0 >= -a.avail) return *reinterpret_cast<const uint4*>(a.x + s0);
-    const int64_t hs = s0 + a.avail + (G::T * N - G::M);  // into xhist (H = TN - M samples)
-    return *reinterpret_cast<const uint4*>(a.xhist + hs);
+    if (s0 >= 0) return *reinterpret_cast<const uint4*>(a.x + s0);
+    return *reinterpret_cast<const uint4*>(a.xhist + s0 + (G::T * N - G::M));  // H = TN - M samples
 }
 
 template <int N>
-__global__ __launch_bounds__(Geo<N>::BT, MKID_CHAN_MINWAVES) void k_channelize(ChanArgs a) {
+__global__ __launch_bounds__(Geo<N>::BT, 1) void k_channelize(ChanArgs a) {
     using G = Geo<N>;
     using PL = Plan8<N>;
     constexpr int PTS = G::PTS, NT = G::NT, M = G::M, C = G::C, T = G::T, RS = G::RS;
@@ -68,7 +60,7 @@ __global__ __launch_bounds__(Geo<N>::BT, MKID_CHAN_MINWAVES) void k_channelize(C
     const int slot = tid / NT;
     const int t = tid % NT;
     float2* bufA = fbuf + slot * G::NBUF * G::LDSF;
-    [[maybe_unused]] float2* bufB = bufA + (G::NBUF - 1) * G::LDSF;  // == bufA without double buffering
+    float2* bufB = bufA + G::LDSF;
 
     // PFB taps for this thread's points (constant over frames)
     float h[T][PTS];
@@ -129,7 +121,6 @@ __global__ __launch_bounds__(Geo<N>::BT, MKID_CHAN_MINWAVES) void k_channelize(C
             v[r] = make_float2(ur, ui);
         }
         st_dft<PTS, PL::R[0]>(v);
-#if MKID_CHAN_DBUF
         // pass 1 -> A. The barrier publishes A and retires every ring read of this iteration.
         st_write<N, PTS, PL::R[0], 1>(bufA, v, t);
         __syncthreads();
@@ -157,37 +148,6 @@ __global__ __launch_bounds__(Geo<N>::BT, MKID_CHAN_MINWAVES) void k_channelize(C
             __syncthreads();
             fin = bufB;
         }
-#else
-        __syncthreads();  // all PFB reads of the oldest FPB hops are done
-        {
-            const int64_t hop = kb + G::FPB + (tid * G::SPT) / M;
-            *reinterpret_cast<uint4*>(ring + (int)(hop % RS) * M + (tid * G::SPT) % M) = pre;
-            pre = load_new<N>(a, kb + 2 * G::FPB, tid);
-        }
-        st_write<N, PTS, PL::R[0], 1>(bufA, v, t);
-        __syncthreads();
-        st_read<N, PTS, PL::R[1]>(bufA, v, t);
-        __syncthreads();
-        tw2.apply(v);
-        st_dft<PTS, PL::R[1]>(v);
-        st_write<N, PTS, PL::R[1], G::NS2>(bufA, v, t);
-        __syncthreads();
-        st_read<N, PTS, PL::R[2]>(bufA, v, t);
-        __syncthreads();
-        tw3.apply(v);
-        st_dft<PTS, PL::R[2]>(v);
-        st_write<N, PTS, PL::R[2], G::NS3>(bufA, v, t);
-        __syncthreads();
-        if constexpr (PL::NP == 4) {
-            st_read<N, PTS, PL::R[3]>(bufA, v, t);
-            __syncthreads();
-            tw4.apply(v);
-            st_dft<PTS, PL::R[3]>(v);
-            st_write<N, PTS, PL::R[3], G::NS4>(bufA, v, t);
-            __syncthreads();
-        }
-        const float2* fin = bufA;
-#endif
         // ---- bin select + DDC ----
         if (k < k_end) {
             const int64_t kg = a.k0 + k;
@@ -200,10 +160,9 @@ __global__ __launch_bounds__(Geo<N>::BT, MKID_CHAN_MINWAVES) void k_channelize(C
                 a.z[k * C + c] = cmul(X, lo);
             }
         }
-        // Double-buffered: the next iteration's first LDS write goes to A before any barrier.
-        // With 4 passes the select above read B (safe); with 3 it read A: barrier first. (Single
-        // buffer: the next write follows the post-PFB barrier.)
-        if constexpr (MKID_CHAN_DBUF && PL::NP != 4) __syncthreads();
+        // The next iteration's first LDS write goes to A before any barrier. With 4 passes the
+        // select above read B (safe); with 3 it read A: barrier first.
+        if constexpr (PL::NP != 4) __syncthreads();
     }
 }
 

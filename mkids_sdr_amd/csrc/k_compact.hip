@@ -82,8 +82,7 @@ __global__ __launch_bounds__(kCmpThreads) void k_tile_sums(const int32_t* counts
 }
 
 // d_counts[0] = packets produced, d_counts[1] = packets stored in `out` (<= cap): written here,
-// once per process call (the call's single compaction covers all of its sub-chunks), so the
-// caller needs no zeroing launch.
+// once per process call, so the caller needs no zeroing launch.
 __global__ __launch_bounds__(kScanThreads) void k_tile_scan(const int64_t* tile_kept, const int64_t* tile_raw,
                                                             int64_t ntiles, int64_t cap, int64_t* tile_off,
                                                             int64_t* d_counts) {

@@ -49,7 +49,7 @@ __device__ __forceinline__ int64_t seg_end(const TrigSpecArgs& a, int s) {
     return seg_begin(a, s) + a.L < a.J ? seg_begin(a, s) + a.L : a.J;
 }
 __device__ __forceinline__ int64_t slot_entry(const TrigSpecArgs& a, int c, int s) {
-    return (int64_t)c * a.seg_stride + a.seg_off + s;
+    return (int64_t)c * a.seg_stride + a.seg_base + s;   // = c * nseg + s (mkid_internal.h)
 }
 __device__ __forceinline__ TrigCfg trig_cfg(const TrigSpecArgs& a, int c) {
     return TrigCfg{a.thr[c], a.rearm[c], a.mode, a.alpha, a.kf, a.kq, a.base_thr, a.dead};
@@ -281,7 +281,7 @@ __global__ __launch_bounds__(kSpecThreads, MKID_TRIG_MINW) void k_trig_spec(Trig
     TrigCfg k = trig_cfg(a, c);
     k.mode = MODE;   // a.mode, as a constant
     const int64_t seg0 = seg_begin(a, s), seg1 = seg_end(a, s);
-    // a segment closer than W to the sub-chunk start warms up from row 0 with the carried state
+    // a segment closer than W to the call's start warms up from row 0 with the carried state
     // (exact); L and W are multiples of 26 whenever W > 0, so seg0 - jw is too
     const int64_t jw = (s == 0 || seg0 <= a.W) ? 0 : seg0 - a.W;
     QWin win;
@@ -540,7 +540,7 @@ __device__ bool svf_walk(const TrigSpecArgs& a, int c, int s, const TrigCfg& k, 
     return merged;
 }
 
-// Phase A of the SVF fix-up (round 6): one wave per (channel c, segment s >= 1) of the sub-chunk.
+// Phase A of the SVF fix-up (round 6): one wave per (channel c, segment s >= 1) of the call.
 // A segment whose speculated start state differs from its predecessor's speculative end state is
 // re-run at once, assuming that end state is the true one (it is unless the predecessor itself
 // fails and does not merge), into its own result and packet entries; k_trig_fix_svf confirms the

@@ -148,7 +148,7 @@ int mkid_create(const mkid_cfg* cfg, int32_t device, mkid_ctx** out) {
         if (const char* ev = getenv("MKID_SVF_WARMUP"))
             svf_w = std::max<int64_t>(1, atoll(ev) / kFirTaps) * kFirTaps;
     }
-    if (const char* msg = plan::size_workspace(*cfg, c->fused, trig_slots, svf_lanes, svf_w, c->ws)) {
+    if (const char* msg = plan::size_workspace(*cfg, trig_slots, svf_lanes, svf_w, c->ws)) {
         g_err = msg;
         delete c;
         return MKID_E_ARG;
@@ -164,11 +164,6 @@ int mkid_create(const mkid_cfg* cfg, int32_t device, mkid_ctx** out) {
     if ((e = hipSetDevice(device)) != hipSuccess) return fail(e, "hipSetDevice");
     if ((e = hipStreamCreateWithFlags(&c->own, hipStreamNonBlocking)) != hipSuccess) return fail(e, "hipStreamCreate");
     c->stream = c->own;
-    if ((e = hipStreamCreateWithFlags(&c->sB, hipStreamNonBlocking)) != hipSuccess) return fail(e, "hipStreamCreate B");
-    for (hipEvent_t* ev : {&c->ev_zready[0], &c->ev_zready[1], &c->ev_zfree[0], &c->ev_zfree[1], &c->ev_start, &c->ev_done})
-        if ((e = hipEventCreateWithFlags(ev, hipEventDisableTiming)) != hipSuccess) return fail(e, "hipEventCreate");
-    for (int b = 0; b < 2; ++b)
-        if ((e = hipEventRecord(c->ev_zfree[b], c->sB)) != hipSuccess) return fail(e, "hipEventRecord");
     AL(d_pfb, (size_t)c->T * N);
     AL(d_pfbq, (size_t)N);
     AL(d_bins, C);
@@ -182,16 +177,13 @@ int mkid_create(const mkid_cfg* cfg, int32_t device, mkid_ctx** out) {
     AL(zhist, kLpfHist, (int64_t)C * 8);
     AL(rhist, kRawHist, (int64_t)C * 2);
     AL(d_tstate, C);
-    if (!c->fused) {
-        AL(d_zb[0], (size_t)ws.Kmax * C);
-        AL(d_zb[1], (size_t)ws.Kmax * C);
-    }
+    if (!c->fused) AL(d_z, (size_t)ws.Kmax * C);
     AL(d_raw, (size_t)ws.Jmax * C);
-    AL(d_iqtap, (size_t)(cfg->max_chunk / N) * 2);
+    AL(d_iqtap, (size_t)ws.Jmax * 2);
     AL(d_ysum, (size_t)2 * C);
     AL(d_slots, (size_t)ws.slot_cap);
-    AL(d_chcounts, (size_t)C * ws.nsub_max * ws.nseg_max);
-    AL(d_scan, (size_t)C * ws.nsub_max * ws.nseg_max + 64);  // >= 3 int64 per compaction tile
+    AL(d_chcounts, (size_t)C * ws.nseg_max);
+    AL(d_scan, (size_t)C * ws.nseg_max + 64);  // >= 3 int64 per compaction tile
     AL(d_sspec, (size_t)C * ws.nseg_max);
     AL(d_send, (size_t)C * ws.nseg_max);
     AL(d_scratch, (size_t)C * ws.scratch_cap);
@@ -438,7 +430,6 @@ int mkid_set_baseline(mkid_ctx* c, int32_t mode, int32_t alpha, int32_t kf, int3
 int mkid_reset_stream(mkid_ctx* c) {
     if (!c) return MKID_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->sB));
     HIPCHK(c, hipMemsetAsync(c->xhist.get(), 0, c->xhist.bytes(), c->stream));
     HIPCHK(c, hipMemsetAsync(c->zhist.get(), 0, c->zhist.bytes(), c->stream));
     HIPCHK(c, hipMemsetAsync(c->rhist.get(), 0, c->rhist.bytes(), c->stream));
@@ -456,8 +447,6 @@ int mkid_reset_stream(mkid_ctx* c) {
     c->j0 = 0;
     c->stream_kind = 0;
     c->last_J = 0;
-    c->last_subJ = 0;
-    c->last_raw_row = 0;
     c->pcarry.drop();   // pulse-height phase history: a reset starts a new stream
     c->ccarry.drop();   // pulse capture: the next call starts a segment (rows and pending list forgotten)
     return MKID_OK;

@@ -63,13 +63,13 @@ struct RollBuf {
     }
     T* get() const { return cur.get(); }
     size_t bytes() const { return (size_t)(rows * row_bytes); }
-    // the roll of `fresh_rows` rows at `fresh` behind the history at `old` (default: cur) into spare
-    mkid::RollJob job(const void* fresh, int64_t fresh_rows, const void* old = nullptr) const {
-        return mkid::RollJob{spare.get(), old ? old : cur.get(), fresh, rows, fresh_rows, row_bytes};
+    // the roll of `fresh_rows` rows at `fresh` behind the history into spare
+    mkid::RollJob job(const void* fresh, int64_t fresh_rows) const {
+        return mkid::RollJob{spare.get(), cur.get(), fresh, rows, fresh_rows, row_bytes};
     }
     void swap() { std::swap(cur, spare); }
-    hipError_t roll(const void* fresh, int64_t fresh_rows, hipStream_t s, const void* old = nullptr) {
-        const mkid::RollJob j = job(fresh, fresh_rows, old);
+    hipError_t roll(const void* fresh, int64_t fresh_rows, hipStream_t s) {
+        const mkid::RollJob j = job(fresh, fresh_rows);
         const hipError_t e =
             mkid::launch_hist_roll(j.dst, j.old_hist, j.fresh, j.hist_rows, j.fresh_rows, j.row_bytes, s);
         if (e == hipSuccess) swap();
@@ -81,13 +81,13 @@ struct RollBuf {
 // first mkid_set_baseline(SVF): all three or none, and a failed alloc() is tried again by the next.
 struct SvfTables {
     DevBuf<int16_t> filt;            // [Jmax][C] filter pre-pass output (k_mf_rows)
-    DevBuf<mkid::RefixRes> refix;    // [C][nsub_max * nseg_max] parallel re-run results (k_trig_refix)
+    DevBuf<mkid::RefixRes> refix;    // [C][nseg_max] parallel re-run results (k_trig_refix)
     DevBuf<uint64_t> refix_pk;       // [slot_cap] their true packets (the slot table's geometry)
     bool ready() const { return filt.get() != nullptr; }
     hipError_t alloc(const mkid::plan::Workspace& ws, int C) {
         SvfTables t;
         hipError_t e = t.filt.alloc((size_t)ws.Jmax * C);
-        if (e == hipSuccess) e = t.refix.alloc((size_t)C * (size_t)ws.nsub_max * (size_t)std::max<int64_t>(1, ws.nseg_max));
+        if (e == hipSuccess) e = t.refix.alloc((size_t)C * (size_t)ws.nseg_max);
         if (e == hipSuccess) e = t.refix_pk.alloc((size_t)ws.slot_cap);
         if (e == hipSuccess) *this = std::move(t);
         return e;
@@ -96,15 +96,10 @@ struct SvfTables {
 
 struct KTime { int k; hipEvent_t a, b; };
 
-// Streams and events of a context. A base of mkid_ctx, so that it is destroyed after the members:
-// buffers first, then events, then streams.
+// The stream and the timing events of a context. A base of mkid_ctx, so that it is destroyed after
+// the members: buffers first, then events, then the stream.
 struct CtxHandles {
     hipStream_t own = nullptr;
-    // two-stream pipeline: stream A (= `stream`) runs the channeliser, stream B the low-pass,
-    // trigger and compaction of the previous sub-chunk; z is double-buffered between them.
-    hipStream_t sB = nullptr;
-    hipEvent_t ev_zready[2] = {nullptr, nullptr}, ev_zfree[2] = {nullptr, nullptr};
-    hipEvent_t ev_start = nullptr, ev_done = nullptr;
     std::vector<KTime> pending;     // timing
     std::vector<hipEvent_t> pool;
     ~CtxHandles() {
@@ -113,9 +108,6 @@ struct CtxHandles {
             (void)hipEventDestroy(kt.b);
         }
         for (auto e : pool) (void)hipEventDestroy(e);
-        for (auto e : {ev_zready[0], ev_zready[1], ev_zfree[0], ev_zfree[1], ev_start, ev_done})
-            if (e) (void)hipEventDestroy(e);
-        if (sB) (void)hipStreamDestroy(sB);
         if (own) (void)hipStreamDestroy(own);
     }
 };
@@ -123,7 +115,7 @@ struct CtxHandles {
 struct mkid_ctx : CtxHandles {
     mkid_cfg cfg{};
     int device = 0;
-    hipStream_t stream = nullptr;   // the caller's (mkid_set_stream) or `own`
+    hipStream_t stream = nullptr;   // the caller's (mkid_set_stream) or `own`: all work runs on it
     std::string err;
     int C = 0, N = 0, M = 0, T = 0, P = 0;
     int ncu = 256;  // compute units of the device (launch grids are per-CU multiples)
@@ -155,15 +147,14 @@ struct mkid_ctx : CtxHandles {
     RollBuf<int16_t> rhist;     // [kRawHist][C]
     DevBuf<mkid::TrigState> d_tstate;
     int64_t k0 = 0, j0 = 0;
-    int zi = 0;
-    // test hook (MKID_FAULT_LAUNCH=n at mkid_create): the n-th front-end launch of the context
-    // reports a HIP failure after it was enqueued, to test the state a partly enqueued call leaves
+    // test hook (MKID_FAULT_LAUNCH=n at mkid_create): the n-th front-end launch of the context (one
+    // per process call; the split front end's three count as one) reports a HIP failure after it
+    // was enqueued, to test the state a partly enqueued call leaves
     int64_t fault_launch = 0, launch_count = 0;
-    int64_t last_raw_row = 0;       // first row of the last sub-chunk's raw phase in d_raw
-    bool fused = false;  // K1-K6 in one kernel (k_front / k_front3 / k_front5: no z buffers, no stream B work)
+    bool fused = false;  // K1-K6 in one kernel (k_front / k_front3 / k_front5: no z buffer)
     // workspace
-    DevBuf<float2> d_zb[2];
-    DevBuf<int16_t> d_raw;
+    DevBuf<float2> d_z;              // [Kmax][C] baseband of the call (split front end only)
+    DevBuf<int16_t> d_raw;           // [Jmax][C] Fix16_13 phase of the call
     SvfTables svf;                   // none until the SVF baseline is first selected
     DevBuf<long long> d_ysum;        // [C][2] fixed point 2^-kYsumFrac: sums of y' while armed
     // avgIQ accumulator (K9; startAccumulator / avgIQ_ctrl, ROACH_Setup.py:654-659): armed by
@@ -178,8 +169,7 @@ struct mkid_ctx : CtxHandles {
     DevBuf<uint64_t> d_scratch;      // [C][capseg]
     DevBuf<int32_t> d_reruns;        // [C]
     DevBuf<int64_t> d_counts;        // [2] used by the host-pointer API
-    int64_t last_J = 0;     // phase rows of the last call
-    int64_t last_subJ = 0;  // rows of its last sub-chunk (held in d_raw)
+    int64_t last_J = 0;     // phase rows of the last call (held in d_raw from row 0)
     // IQ snapshot tap: low-pass output of one channel for the rows of the last call
     int32_t iq_ch = -1;
     DevBuf<int16_t> d_iqtap;        // [max_chunk/N][2]

@@ -45,10 +45,7 @@ struct ChanArgs {
     int64_t K;              // frames in this chunk
     int64_t k0;             // global index of the chunk's first frame
     int32_t P;              // LO period (power of two)
-    int32_t pad;
     int64_t frames_per_block;  // set by the launcher
-    int64_t avail;          // samples readable before x (earlier sub-chunks of the same call);
-                            // older samples come from xhist
 };
 
 // Centred low-pass (K5-K6 with the IQ-loop centre c subtracted BEFORE the accumulation, DESIGN.md
@@ -100,9 +97,10 @@ struct FrontArgs {
     int64_t K;              // frames in this chunk (even)
     int64_t k0;             // global index of the chunk's first frame
     int64_t frames_per_block;  // set by the launcher
-    int64_t avail;          // samples readable before x (earlier sub-chunks of the same call)
+    int64_t avail;          // samples readable before x; the host always passes 0 (a call is one
+                            // launch: everything before x comes from xhist)
     int32_t P;              // LO period (power of two)
-    int32_t ncu;            // compute units of the device (grid sizing: per-CU multipliers)
+    int32_t ncu;           // compute units of the device (grid sizing: per-CU multipliers)
     LpfTaps taps;
     int16_t* iqtap;         // [K/2][2] int16 low-pass output of channel iq_ch (IQ snapshot) or nullptr
     int32_t iq_ch;
@@ -130,22 +128,24 @@ struct TrigSpecArgs {
     TrigState* st_out;      // [C] carried state after this call (may alias st_in)
     TrigState* s_spec;      // [C][nseg] speculative state at each segment start (k_trigger.hip seg_state)
     TrigState* s_end;       // [C][nseg] state at each segment end
-    uint64_t* slots;        // [C][seg_stride][capseg] packets (entry c*seg_stride + seg_off + s)
-    int32_t* counts;        // [C][seg_stride]
+    uint64_t* slots;        // [C][nseg][capseg] packets (entry c*nseg + s)
+    int32_t* counts;        // [C][nseg]
     uint64_t* scratch;      // [C][capseg] fix-up scratch
     int32_t* reruns;        // [C] segments re-run by the fix-up (diagnostic, nullable)
     int64_t J;
     int64_t j0;             // global index of the chunk's first phase sample
     int32_t C, nseg, L, W, capseg;
     int32_t mode, alpha, kf, kq, base_thr, dead;
-    // the segments of one call's sub-chunks share one [C][seg_stride] slot table, so that a single
-    // compaction at the end of the call orders packets channel-major over the whole call
-    int32_t seg_stride, seg_off;
+    // Always (nseg, 0): the slot entry is seg_stride c + seg_base + s. They date from calls cut into
+    // pieces that shared one table; reading nseg instead changes the register allocation of
+    // k_trig_spec (VGPRs 85 -> 86 and 126 -> 128, scratch 48 -> 64 bytes), so removing them waits
+    // for an A/B of its own
+    int32_t seg_stride, seg_base;
     // The SVF path's tables (mkid_ctx.h SvfTables; an SVF launch needs all three, other modes none).
     // filt: [J][C] matched-filter output (int16) of the filter pre-pass (k_mf_rows), so that the SVF
     // walk, bound by one wave's instruction stream, skips the 26-tap filter. refix / refix_pk: every
     // failed segment is re-run in parallel (k_trig_refix) assuming its predecessor's speculative end
-    // state, into [C][seg_stride] results and a [C][seg_stride][capseg] packet table; k_trig_fix_svf
+    // state, into [C][nseg] results and a [C][nseg][capseg] packet table; k_trig_fix_svf
     // then confirms the assumptions channel by channel
     int16_t* filt = nullptr;
     RefixRes* refix = nullptr;

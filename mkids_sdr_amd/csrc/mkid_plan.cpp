@@ -17,35 +17,26 @@ int64_t seg_length(int64_t J, int C, int64_t wave_slots) {
     return std::max<int64_t>(kSegL, (J + nt - 1) / nt);
 }
 
-const char* size_workspace(const mkid_cfg& cfg, bool fused, int64_t trig_slots, int64_t svf_lanes,
-                           int64_t svf_w, Workspace& ws) {
+const char* size_workspace(const mkid_cfg& cfg, int64_t trig_slots, int64_t svf_lanes, int64_t svf_w,
+                           Workspace& ws) {
     const int C = cfg.n_channels, N = cfg.fft_len;
     if (C <= 0 || N != 2 * C || cfg.max_chunk < N || cfg.max_chunk % N != 0 || cfg.dead_time < 0)
         return "unsupported geometry";
     if (trig_slots < 1 || svf_lanes < 1 || svf_w < kFirTaps || svf_w % kFirTaps != 0) return "bad tuning values";
     ws = Workspace{};
-    // split front end: a large call is cut into 4 sub-chunks so the channeliser (stream A) of
-    // sub-chunk i+1 overlaps the low-pass/trigger (stream B) of sub-chunk i
-    int64_t G = cfg.max_chunk;
-    if (!fused && G >= (int64_t)512 * N) {
-        G = cfg.max_chunk / 4;
-        G -= G % N;
-    }
     ws.max_chunk = cfg.max_chunk;
-    ws.G = G;
-    ws.Kmax = G / (N / 2);
-    ws.Jmax = G / N;
-    ws.nsub_max = (cfg.max_chunk + G - 1) / G;
+    ws.Kmax = cfg.max_chunk / (N / 2);
+    ws.Jmax = cfg.max_chunk / N;
     ws.trig_slots = trig_slots;
     ws.svf_lanes = svf_lanes;
     ws.svf_w = svf_w;
     // packet capacities are hard bounds (seg_capacity): no per-channel/segment overflow can occur
-    const int64_t cap_bound = seg_capacity(ws.Jmax, cfg.dead_time);   // whole sub-chunk, one segment
+    const int64_t cap_bound = seg_capacity(ws.Jmax, cfg.dead_time);   // whole call, one segment
     ws.capc = std::min<int64_t>(cfg.max_events_per_ch > 0 ? cfg.max_events_per_ch : cap_bound, INT_MAX / 2);
-    // plan_sub rounds segment lengths UP to the 26-sample ring: every segment of a sub-chunk of
+    // plan_trigger rounds segment lengths UP to the 26-sample ring: every segment of a call of
     // J <= Jmax rows is at most round26(Jmax) long (EMA: round26(max(kSegL, ceil(J / nt))), and a
     // multi-segment plan needs J > kSegL; SVF: round26(ceil(J / nseg)) or J), and the EMA segments of
-    // a full sub-chunk at most Lmax = round26(seg_length(Jmax)) (found by tools/plan_fuzz.cpp: sizing
+    // a full call at most Lmax = round26(seg_length(Jmax)) (found by tools/plan_fuzz.cpp: sizing
     // from the unrounded lengths left some legal calls one packet short of the scratch)
     auto round26 = [](int64_t L) { return (L + kFirTaps - 1) / kFirTaps * kFirTaps; };
     const int64_t Lmax = round26(seg_length(ws.Jmax, C, trig_slots));
@@ -53,21 +44,20 @@ const char* size_workspace(const mkid_cfg& cfg, bool fused, int64_t trig_slots, 
     ws.nseg_max = std::max<int64_t>(std::max<int64_t>(1, trig_slots * 64 / C), (ws.Jmax + kSegL - 1) / kSegL);
     const int64_t capseg = seg_capacity(Lmax, cfg.dead_time);
     const int64_t capseg_any = seg_capacity(round26(ws.Jmax), cfg.dead_time);   // any one segment
-    // one [C][sum of the sub-chunks' segments][capseg] table per call (single compaction)
-    ws.slot_cap = (int64_t)C * ws.nsub_max * std::max<int64_t>(std::max<int64_t>(ws.nseg_max * capseg, ws.capc), capseg_any);
+    // one [C][nseg][capseg] table per call
+    ws.slot_cap = (int64_t)C * std::max<int64_t>(std::max<int64_t>(ws.nseg_max * capseg, ws.capc), capseg_any);
     // the fix-up re-runs one segment per channel into [C][capseg]: any plan's capseg, including an
-    // SVF segment as long as the whole sub-chunk (plan_sub), whatever max_events_per_ch says
+    // SVF segment as long as the whole call (plan_trigger), whatever max_events_per_ch says
     ws.scratch_cap = std::max<int64_t>(std::max<int64_t>(capseg, ws.capc), capseg_any);
     return nullptr;
 }
 
-SubPlan plan_sub(const Workspace& ws, int C, int mode, int dead, int64_t J) {
-    SubPlan p;
+static TrigPlan plan_trigger(const Workspace& ws, int C, int mode, int dead, int64_t J) {
+    TrigPlan p;
     p.J = J;
-    p.seg_off = 0;
     if (mode == MKID_BASE_SVF) {
         // svf_lanes segments over all channels (the per-lane walk is latency bound), each
-        // >= kSvfLmin rows; short sub-chunks run as one exact segment
+        // >= kSvfLmin rows; short calls run as one exact segment
         const int64_t want = std::max<int64_t>(1, ws.svf_lanes / C);
         const int64_t nseg = std::min<int64_t>(std::min<int64_t>(want, J / kSvfLmin), ws.nseg_max);
         p.W = 0;
@@ -93,22 +83,13 @@ SubPlan plan_sub(const Workspace& ws, int C, int mode, int dead, int64_t J) {
     return p;
 }
 
-const char* plan_call(const Workspace& ws, int C, int N, int mode, int dead, int64_t n,
-                      std::vector<SubPlan>& subs, int32_t& stride, int32_t& capseg) {
-    subs.clear();
-    stride = 0;
-    capseg = 1;
+const char* plan_call(const Workspace& ws, int C, int N, int mode, int dead, int64_t n, TrigPlan& p) {
     // the per-call buffers (raw rows, IQ tap, slot table) hold max_chunk samples
     if (n <= 0 || n % N != 0 || n > ws.max_chunk) return "call size outside the workspace";
-    for (int64_t off = 0; off < n; off += ws.G) {
-        subs.push_back(plan_sub(ws, C, mode, dead, std::min<int64_t>(ws.G, n - off) / N));
-        subs.back().seg_off = stride;
-        stride += subs.back().nseg;
-        capseg = std::max(capseg, subs.back().capseg);
-        if (subs.back().nseg > ws.nseg_max) return "trigger plan exceeds the segment tables";
-    }
-    if ((int64_t)C * stride * capseg > ws.slot_cap) return "trigger plan exceeds the packet slot table";
-    if (capseg > ws.scratch_cap) return "trigger plan exceeds the fix-up scratch";
+    p = plan_trigger(ws, C, mode, dead, n / N);
+    if (p.nseg > ws.nseg_max) return "trigger plan exceeds the segment tables";
+    if ((int64_t)C * p.nseg * p.capseg > ws.slot_cap) return "trigger plan exceeds the packet slot table";
+    if (p.capseg > ws.scratch_cap) return "trigger plan exceeds the fix-up scratch";
     return nullptr;
 }
 

@@ -52,30 +52,26 @@ int64_t seg_length(int64_t J, int C, int64_t wave_slots);
 // What a context was sized for (mkid_create): every later call is planned within it.
 struct Workspace {
     int64_t max_chunk = 0;    // samples per call (cfg.max_chunk)
-    int64_t G = 0;            // samples per sub-chunk (max_chunk, or max_chunk/4 on the split path)
-    int64_t Kmax = 0, Jmax = 0, nsub_max = 0;
-    int64_t capc = 0;         // per-channel packet capacity of a whole sub-chunk
+    int64_t Kmax = 0, Jmax = 0;   // FFT frames and phase rows of a call of max_chunk samples
+    int64_t capc = 0;         // per-channel packet capacity of a whole call
     int64_t trig_slots = 0, svf_lanes = 0, svf_w = kSvfW;
-    int64_t nseg_max = 0;     // segments per sub-chunk
-    int64_t slot_cap = 0;     // packet slots of the [C][stride][capseg] table
+    int64_t nseg_max = 0;     // segments per call
+    int64_t slot_cap = 0;     // packet slots of the [C][nseg][capseg] table
     int64_t scratch_cap = 0;  // per-channel fix-up scratch
 };
-// cfg already validated (N = 2C, max_chunk a multiple of N, dead_time >= 0); ncu = compute units
-const char* size_workspace(const mkid_cfg& cfg, bool fused, int64_t trig_slots, int64_t svf_lanes,
-                           int64_t svf_w, Workspace& ws);
+// cfg already validated (N = 2C, max_chunk a multiple of N, dead_time >= 0)
+const char* size_workspace(const mkid_cfg& cfg, int64_t trig_slots, int64_t svf_lanes, int64_t svf_w,
+                           Workspace& ws);
 
-// Trigger geometry of one sub-chunk of J phase rows: segment length L, warm-up W, nseg segments and
-// the per-segment packet capacity; seg_off (plan_call): its first segment in the call's slot table.
-struct SubPlan {
+// Trigger geometry of one call of J phase rows: nseg segments of L rows (the last one shorter), each
+// speculating from W rows of warm-up into capseg packet slots of the call's [C][nseg][capseg] table.
+struct TrigPlan {
     int64_t J;
-    int32_t L, W, nseg, capseg, seg_off;
+    int32_t L, W, nseg, capseg;
 };
-SubPlan plan_sub(const Workspace& ws, int C, int mode, int dead, int64_t J);
-// The sub-chunk plans of a call of n samples (n a positive multiple of N, n <= max_chunk) and the
-// call's slot-table geometry: stride = total segments per channel, capseg = the largest per-segment
-// capacity. Returns nullptr, or the error text when the plan exceeds the workspace.
-const char* plan_call(const Workspace& ws, int C, int N, int mode, int dead, int64_t n,
-                      std::vector<SubPlan>& subs, int32_t& stride, int32_t& capseg);
+// The plan of a call of n samples (n a positive multiple of N, n <= max_chunk). Returns nullptr, or
+// the error text when the call or its plan exceeds the workspace.
+const char* plan_call(const Workspace& ws, int C, int N, int mode, int dead, int64_t n, TrigPlan& p);
 
 // Which rows of a history buffer of H rows are valid: the last `rows`, and they precede a call that
 // starts at global row j0 only if they end there (pulse heights and capture, mkid_calib.hip).

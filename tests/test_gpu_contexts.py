@@ -72,11 +72,12 @@ def test_device_call_larger_than_workspace_is_rejected(gpu):
 
 @pytest.mark.parametrize('front', ['auto', 'split'])
 def test_packets_channel_major_over_whole_call(gpu, front):
-    """The split front end cuts a call into sub-chunks; packets still come out channel-major and
-    time-ascending over the whole call (one compaction per call)."""
+    """Packets come out channel-major and time-ascending over the whole call, on either front end
+    (one trigger plan and one compaction per call), at a call size the split front end once cut
+    into four pieces."""
     from mkids_sdr_amd.channelizer import Channelizer
     C = 256
-    S = 600 * 2 * C          # >= 512 N: four pipeline sub-chunks on the split path
+    S = 600 * 2 * C          # >= 512 N
     case = signals.make_case(C, S, seed=41, pulses_per_ch=4.0, noise=100.0)
     thr = quiet_thresholds(C, S // 4, 41)
     ch = Channelizer(C, max_chunk=S, front=front)
@@ -87,6 +88,75 @@ def test_packets_channel_major_over_whole_call(gpu, front):
         ch.close()
     assert len(ev) > 100
     assert np.array_equal(ev, sort_events(ev))
+
+
+@pytest.mark.parametrize('front', ['auto', 'split'])
+def test_raw_phase_is_the_whole_call(gpu, front):
+    """mkid_last_raw_phase / mkid_read_raw_phase hold the Fix16_13 phase of the whole last call, from
+    row 0: J = 512 rows at C = 64 is the smallest call the split front end once cut into pieces
+    (it then reported the last piece only). Element for element the rows are the Fix16_13 of the
+    float32 phase the same call returned; so are the 3 rows of a ragged second call."""
+    from mkids_sdr_amd.channelizer import Channelizer
+    C = 64
+    N = 2 * C
+    S = 512 * N
+    case = signals.make_case(C, 2 * S, seed=47, pulses_per_ch=2.0)
+    ch = Channelizer(C, max_chunk=S, front=front)
+    try:
+        configure(ch, case, np.full(C, -(1 << 30)))
+        for a, b in ((0, S), (S, S + 3 * N)):
+            ph, _ = ch.process(case.iq[a:b])
+            raw = ch.raw_phase()
+            assert ph.shape == ((b - a) // N, C) and raw.shape == ph.shape
+            want = np.clip(np.rint(ph * np.float32(8192)), -25736, 25736).astype(np.int16)
+            assert np.array_equal(raw, want)
+            assert int(raw.max()) - int(raw.min()) > 8192   # live phases, not a cleared buffer
+    finally:
+        ch.close()
+
+
+def test_split_follows_the_callers_stream(gpu):
+    """All work of a split context runs on the stream handed to mkid_set_stream, in call order: two
+    process_device calls back to back, then copies of their counts and packets enqueued on that
+    same stream and ONE synchronisation of it (no device-wide one) give the packets the same two
+    calls give through the synchronous host entry point."""
+    import torch
+    from mkids_sdr_amd.channelizer import Channelizer
+    C, S = 64, 1 << 15
+    J = S // (2 * C)
+    case = signals.make_case(C, 2 * S, seed=48, pulses_per_ch=6.0)
+    thr = quiet_thresholds(C, 2 * S, 48)
+    ref = Channelizer(C, max_chunk=S, front='split')
+    try:
+        configure(ref, case, thr)
+        want = [ref.process(case.iq[i * S:(i + 1) * S], want_phase=False)[1] for i in range(2)]
+    finally:
+        ref.close()
+    assert min(len(w) for w in want) > 10
+    cap = J * C
+    st = torch.cuda.Stream()
+    ch = Channelizer(C, max_chunk=S, front='split')
+    try:
+        configure(ch, case, thr)
+        ch.set_stream(st.cuda_stream)
+        with torch.cuda.stream(st):
+            x = [torch.from_numpy(case.iq[i * S:(i + 1) * S].reshape(-1)).to('cuda') for i in range(2)]
+            ev = [torch.empty(cap, dtype=torch.int64, device='cuda') for _ in range(2)]
+            cnt = [torch.empty(2, dtype=torch.int64, device='cuda') for _ in range(2)]
+            h_ev = [torch.empty(cap, dtype=torch.int64, pin_memory=True) for _ in range(2)]
+            h_cnt = [torch.empty(2, dtype=torch.int64, pin_memory=True) for _ in range(2)]
+            for i in range(2):
+                ch.process_device(x[i], S, None, ev[i], cap, cnt[i])
+            for i in range(2):
+                h_cnt[i].copy_(cnt[i], non_blocking=True)
+                h_ev[i].copy_(ev[i], non_blocking=True)
+        st.synchronize()
+        for i in range(2):
+            n = h_cnt[i].numpy()
+            assert n[0] == n[1] == len(want[i])
+            assert np.array_equal(h_ev[i].numpy()[:n[1]].view(np.uint64), want[i])
+    finally:
+        ch.close()
 
 
 def test_host_call_longer_than_max_chunk_is_channel_major(gpu):

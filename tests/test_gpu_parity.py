@@ -229,9 +229,11 @@ def test_internal_subchunks_and_tiny_calls(gpu):
 
 
 def test_pipelined_subchunks(gpu):
-    """max_chunk >= 512 N: calls are split into max_chunk/4 sub-chunks whose channeliser runs on
-    a second stream ahead of the low-pass/trigger (double-buffered z). Ragged calls leave short
-    last sub-chunks (down to one FFT frame pair)."""
+    """max_chunk >= 512 N, the size from which the split front end once cut a call into four
+    pipelined pieces (the test's name dates from then): a call is one piece on either front end,
+    with z staged for the whole call on the split one. Ragged calls: one that ends five rows past
+    an old piece boundary, a one-row call, one just short of a piece and one a row short of
+    max_chunk; then the SVF baseline on two calls of max_chunk samples."""
     C = 64
     N = 2 * C
     S = 2 ** 19
@@ -241,7 +243,7 @@ def test_pipelined_subchunks(gpu):
     splits = [0, 3 * G + 5 * N, 3 * G + 6 * N, 2 ** 18 + N, S]
     compare(case, thr, splits, max_chunk=2 ** 18, front='split')
     compare(case, thr, [0, S], mode=2, max_chunk=2 ** 18, front='split')
-    compare(case, thr, splits, max_chunk=2 ** 18)  # fused: plain max_chunk sub-chunks
+    compare(case, thr, splits, max_chunk=2 ** 18)  # fused
 
 
 def test_deleted_channels_and_dead_time(gpu):

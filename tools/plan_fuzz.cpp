@@ -44,7 +44,7 @@ static std::mt19937_64 rng;
 static int64_t rint_(int64_t lo, int64_t hi) { return std::uniform_int_distribution<int64_t>(lo, hi)(rng); }
 
 // workspace sizing + call plans for random geometries and ragged calls; the kernels' slot-table
-// writes ([C][stride][capseg], per (channel, segment) at most seg_capacity(L) packets; fix-up scratch
+// writes ([C][nseg][capseg], per (channel, segment) at most seg_capacity(L) packets; fix-up scratch
 // [C][capseg]) are replayed into exactly-sized buffers
 static void fuzz_plans(int iters) {
     const int Cs[] = {64, 128, 256, 512, 1024, 2048};
@@ -63,15 +63,13 @@ static void fuzz_plans(int iters) {
         // max_chunk: small (a few rows) to large (2^27 samples), sized so the replay stays small
         const int64_t rows_max = rint_(0, 3) == 0 ? rint_(1, 64) : rint_(1, std::max<int64_t>(1, (1 << 26) / N));
         cfg.max_chunk = rows_max * N;
-        const bool fused = rint_(0, 1) == 1;
         const int64_t trig_slots = rint_(0, 2) == 0 ? rint_(1, 64) : rint_(1, 40000);
         const int64_t svf_lanes = rint_(0, 2) == 0 ? rint_(1, 100) : (rint_(0, 1) ? 256 * 256 : 256 * 128);
         const int64_t svf_w = 26 * rint_(1, 4000);
         Workspace ws;
-        const char* e = size_workspace(cfg, fused, trig_slots, svf_lanes, svf_w, ws);
+        const char* e = size_workspace(cfg, trig_slots, svf_lanes, svf_w, ws);
         CHECK(e == nullptr, "size_workspace failed: %s", e);
         if (e) continue;
-        CHECK(ws.G > 0 && ws.G % N == 0 && ws.G * ws.nsub_max >= cfg.max_chunk, "sub-chunk geometry");
         CHECK(ws.nseg_max >= 1 && ws.slot_cap > 0 && ws.scratch_cap > 0, "table sizes");
         for (int call = 0; call < 6; ++call) {
             const int mode = (int)rint_(0, 2);
@@ -84,46 +82,35 @@ static void fuzz_plans(int iters) {
                 default: rows = rint_(1, rows_max);
             }
             const int64_t n = rows * N;
-            std::vector<SubPlan> subs;
-            int32_t stride = 0, capseg = 0;
-            const char* pe = plan_call(ws, C, N, mode, cfg.dead_time, n, subs, stride, capseg);
+            TrigPlan p{};
+            const char* pe = plan_call(ws, C, N, mode, cfg.dead_time, n, p);
             if (n > cfg.max_chunk) {
                 CHECK(pe != nullptr, "a call longer than max_chunk was planned");
                 continue;
             }
             CHECK(pe == nullptr, "plan_call failed: %s (C %d rows %lld mode %d)", pe, C, (long long)rows, mode);
             if (pe) continue;
-            int64_t Jsum = 0, segs = 0;
-            for (const SubPlan& sp : subs) {
-                CHECK(sp.seg_off == segs, "seg_off %d of %lld", sp.seg_off, (long long)segs);
-                Jsum += sp.J;
-                segs += sp.nseg;
-                CHECK(sp.J >= 1 && sp.J <= ws.Jmax, "sub-chunk rows %lld", (long long)sp.J);
-                CHECK(sp.nseg >= 1 && sp.nseg <= ws.nseg_max, "nseg %d of %lld", sp.nseg, (long long)ws.nseg_max);
-                CHECK(sp.L >= 1 && (int64_t)(sp.nseg - 1) * sp.L < sp.J && (int64_t)sp.nseg * sp.L >= sp.J,
-                      "segments do not tile J: J %lld L %d nseg %d", (long long)sp.J, sp.L, sp.nseg);
-                CHECK(sp.W >= 0 && sp.W % 26 == 0, "warm-up %d", sp.W);
-                CHECK(sp.nseg == 1 || sp.L % 26 == 0, "segment starts off the 26-sample ring");
-                CHECK(sp.capseg >= seg_capacity(sp.L, cfg.dead_time) && sp.capseg <= capseg, "capseg");
-            }
-            CHECK(Jsum == rows, "sub-chunks cover %lld of %lld rows", (long long)Jsum, (long long)rows);
-            CHECK(segs == stride, "stride");
-            CHECK((int64_t)C * stride * capseg <= ws.slot_cap, "slot table");
-            CHECK(capseg <= ws.scratch_cap, "scratch");
+            CHECK(p.J == rows && p.J <= ws.Jmax, "the plan covers %lld of %lld rows", (long long)p.J, (long long)rows);
+            CHECK(p.nseg >= 1 && p.nseg <= ws.nseg_max, "nseg %d of %lld", p.nseg, (long long)ws.nseg_max);
+            CHECK(p.L >= 1 && (int64_t)(p.nseg - 1) * p.L < p.J && (int64_t)p.nseg * p.L >= p.J,
+                  "segments do not tile J: J %lld L %d nseg %d", (long long)p.J, p.L, p.nseg);
+            CHECK(p.W >= 0 && p.W % 26 == 0, "warm-up %d", p.W);
+            CHECK(p.nseg == 1 || p.L % 26 == 0, "segment starts off the 26-sample ring");
+            CHECK(p.capseg >= seg_capacity(p.L, cfg.dead_time), "capseg");
+            CHECK((int64_t)C * p.nseg * p.capseg <= ws.slot_cap, "slot table");
+            CHECK(p.capseg <= ws.scratch_cap, "scratch");
             // replay the writes into exactly-sized tables (ASan catches any overrun)
             if (ws.slot_cap <= (int64_t)1 << 22 && (int64_t)C * ws.scratch_cap <= (int64_t)1 << 22) {
                 std::vector<uint8_t> slots((size_t)ws.slot_cap), scratch((size_t)(C * ws.scratch_cap));
                 const int64_t ch[] = {0, C - 1, rint_(0, C - 1)};
-                for (const SubPlan& sp : subs) {
-                    for (int64_t c : ch)
-                        for (int32_t s = 0; s < sp.nseg; s += std::max<int32_t>(1, sp.nseg - 1)) {
-                            const int64_t base = (c * stride + sp.seg_off + s) * (int64_t)capseg;
-                            for (int32_t k = 0; k < sp.capseg; k += std::max<int32_t>(1, sp.capseg - 1))
-                                slots[(size_t)(base + k)] = 1;
-                            for (int32_t k = 0; k < sp.capseg; k += std::max<int32_t>(1, sp.capseg - 1))
-                                scratch[(size_t)(c * capseg + k)] = 1;
-                        }
-                }
+                for (int64_t c : ch)
+                    for (int32_t s = 0; s < p.nseg; s += std::max<int32_t>(1, p.nseg - 1)) {
+                        const int64_t base = (c * p.nseg + s) * (int64_t)p.capseg;
+                        for (int32_t k = 0; k < p.capseg; k += std::max<int32_t>(1, p.capseg - 1))
+                            slots[(size_t)(base + k)] = 1;
+                        for (int32_t k = 0; k < p.capseg; k += std::max<int32_t>(1, p.capseg - 1))
+                            scratch[(size_t)(c * p.capseg + k)] = 1;
+                    }
             }
         }
     }
@@ -150,21 +137,19 @@ static void fuzz_sizing(int iters) {
         cfg.max_events_per_ch = rint_(0, 1) ? 0 : (int)rint_(1, 5000);
         const int64_t rows_max = rint_(1, ((int64_t)1 << rint_(20, 31)) / N);
         cfg.max_chunk = rows_max * N;
-        const bool fused = rint_(0, 1) == 1;
         Workspace ws;
-        const char* e = size_workspace(cfg, fused, trig_slots, svf_lanes, kSvfW, ws);
+        const char* e = size_workspace(cfg, trig_slots, svf_lanes, kSvfW, ws);
         CHECK(e == nullptr, "size_workspace failed at max_chunk %lld: %s", (long long)cfg.max_chunk, e);
         if (e) continue;
         for (int call = 0; call < 8; ++call) {
             const int mode = call % 3;
             const int64_t rows = call < 3 ? rows_max : rint_(1, rows_max);
-            std::vector<SubPlan> subs;
-            int32_t stride = 0, capseg = 0;
-            const char* pe = plan_call(ws, C, N, mode, cfg.dead_time, rows * N, subs, stride, capseg);
+            TrigPlan p{};
+            const char* pe = plan_call(ws, C, N, mode, cfg.dead_time, rows * N, p);
             CHECK(pe == nullptr, "legal call refused: %s (C %d rows %lld of %lld, mode %d, dead %d)", pe, C,
                   (long long)rows, (long long)rows_max, mode, cfg.dead_time);
             if (pe) continue;
-            CHECK((int64_t)C * stride * capseg <= ws.slot_cap && capseg <= ws.scratch_cap, "tables");
+            CHECK((int64_t)C * p.nseg * p.capseg <= ws.slot_cap && p.capseg <= ws.scratch_cap, "tables");
         }
     }
 }

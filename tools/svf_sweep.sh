@@ -1,6 +1,6 @@
 #!/bin/bash
 # SVF trigger geometry sweep on the GPU box: bench.py --baseline svf under MKID_SVF_WARMUP /
-# MKID_SVF_LANES (mkid_api.hip mkid_create; mkid_plan.cpp plan_sub), one short run each; prints ms/step, kernel times, re-runs.
+# MKID_SVF_LANES (mkid_api.hip mkid_create; mkid_plan.cpp plan_trigger), one short run each; prints ms/step, kernel times, re-runs.
 #   bash tools/svf_sweep.sh "W1 W2 ..." "LANES1 LANES2 ..."
 set -e
 cd "${GRAFT_REPO_ROOT:-.}"
