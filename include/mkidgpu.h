@@ -399,6 +399,46 @@ int mkid_bank_filters(mkid_ctx* ctx, const float* d_I, const float* d_Q, const i
                       const mkid_bank_cfg* cfg, double* d_templates, double* d_noise, float* d_coeff,
                       mkid_bank_result* d_result);
 
+/* Every channel's trigger threshold from a Fix16_13 phase block in one call: the reference's rule
+ * (loadThresholds / loadSingleThreshold, ROACH_Pulses.py:211-299; mkids_sdr_amd.codecs.
+ * threshold_from_phase under numpy 2) for columns 0..nch-1 of d_raw [rows][ld] int16 (the layout of
+ * mkid_replay_trigger; e.g. mkid_last_raw_phase of a quiet call). The result goes to
+ * mkid_set_thresholds. Per channel, over its rows samples x:
+ *   range      lo = min x, hi = max x as doubles; lo == hi: lo -= 0.5, hi += 0.5
+ *   edges      step = (hi - lo) / 100; e[i] = i step + lo (i = 0..99; product and sum each rounded,
+ *              never fused), e[100] = hi: np.histogram(x, bins=100)'s np.linspace
+ *   bin        of x: the largest i <= 99 with e[i] <= x; count[i] samples, exact integers
+ *   fractions  n[i] = (double)(float)count[i] / (double)rows  (np.array(n, dtype='float32') /
+ *              np.sum(n): float32 over an int64 scalar is a float64 division)
+ *   sums       tot[i] = np.sum(n[:i]), i = 0..100, in numpy's pairwise order below 128 elements:
+ *              sequential from 0 below 8 elements, else 8 accumulators over the multiple-of-8
+ *              prefix, combined ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the remainder in order
+ *   threshold  med = e[first argmin |tot - 0.5|], p05 = e[first argmin |tot - 0.05|],
+ *              thr = max((int)(-nsigma |med - p05|), -25736), the cast truncating toward zero
+ * Counts are integers and every float64 step is one IEEE operation in a fixed order, so d_thr, med
+ * and p05 are bit-identical to the host rule, to mkid_phase_thresholds_host, and from run to run.
+ *   - mkid_phase_thresholds: device pointers only, asynchronous on the context stream; nch need not
+ *     equal the context's C; the block is never written; d_thr [nch] and d_stats [nch] (nullable)
+ *     are written for channels 0..nch-1 only. Once the workspace exists (min/max [nch] and counts
+ *     [nch][100], owned by the context, grown on demand: allocate, synchronise once, move in) the
+ *     call makes no device-to-host copy and no synchronisation. MKID_E_ARG before any launch: a null
+ *     required pointer, rows < 1 or > 2^31 - 1, nch < 1 or > ld, nsigma negative or not finite.
+ *     Not timed (no MKID_K_ id).
+ *   - mkid_phase_thresholds_host: the same rule on host memory, through the same definitions
+ *     (csrc/thr_common.h); needs no device and no context. The same MKID_E_ARG cases.
+ *   - mkid_phase_thresholds_block_rows: the rows per workgroup row block the device call uses for a
+ *     block of that shape on the context's device; aligned16 says whether d_raw is 16-byte aligned
+ *     (an unaligned block, like an ld that is no multiple of 8, runs one channel per thread, which
+ *     can change the strip count and with it the length). The count pass adds one partial table per
+ *     row block and channel strip; tests put blocks around this length. */
+typedef struct mkid_thr_stats { double med, p05; int32_t lo, hi; } mkid_thr_stats;
+int mkid_phase_thresholds(mkid_ctx* ctx, const int16_t* d_raw, int64_t rows, int64_t ld, int32_t nch,
+                          double nsigma, int32_t* d_thr /* [nch] */, mkid_thr_stats* d_stats /* nullable */);
+int mkid_phase_thresholds_host(const int16_t* raw, int64_t rows, int64_t ld, int32_t nch, double nsigma,
+                               int32_t* thr, mkid_thr_stats* stats /* nullable */);
+int mkid_phase_thresholds_block_rows(const mkid_ctx* ctx, int64_t rows, int64_t ld, int32_t nch,
+                                     int32_t aligned16, int64_t* block_rows);
+
 /* Kernel timing with HIP events on the context stream (for bench roofline numbers). */
 #define MKID_K_CHANNELIZE 0
 #define MKID_K_FIR_PHASE 1

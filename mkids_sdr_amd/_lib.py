@@ -69,6 +69,11 @@ class BankResult(ctypes.Structure):
                 ('status', ctypes.c_int32), ('ready', ctypes.c_int32)]
 
 
+class ThrStats(ctypes.Structure):
+    """mkid_thr_stats: the median and 5 % edges behind a channel's threshold and its raw range."""
+    _fields_ = [('med', ctypes.c_double), ('p05', ctypes.c_double), ('lo', ctypes.c_int32), ('hi', ctypes.c_int32)]
+
+
 BANK_USED, BANK_FEW_RECORDS, BANK_NONE_PASS1, BANK_NONE_PASS2 = range(4)
 
 
@@ -125,6 +130,9 @@ _SIGS = {
     'mkid_set_capture': [P, I32, I32, I32],
     'mkid_capture_pulses': [P, P, I64, I64, P, I64, P, P, P],
     'mkid_capture_pulses_counted': [P, P, I64, I64, P, P, I64, P, P, P],
+    'mkid_phase_thresholds': [P, P, I64, I64, I32, ctypes.c_double, P, P],
+    'mkid_phase_thresholds_host': [P, I64, I64, I32, ctypes.c_double, P, P],
+    'mkid_phase_thresholds_block_rows': [P, I64, I64, I32, I32, P],
     'mkid_stream_copy': [P, P, P, I64],
     'mkid_synth_adc': [P, P, I64, I64, P, P, P, I64, ctypes.c_float, ctypes.c_float, I32,
                        ctypes.c_float, ctypes.c_uint32],

@@ -174,6 +174,62 @@ class Channelizer:
         self._chk(self._L.mkid_read_raw_phase(self._h, _ptr(out), rows, ctypes.byref(n)))
         return out
 
+    # ---- thresholds from a quiet phase block (loadThresholds, ROACH_Pulses.py:211-299) ---------
+    def phase_thresholds_device(self, d_raw, rows, ld, nch, nsigma, d_thr, d_stats=None):
+        """The reference's threshold rule on device Fix16_13 rows d_raw[rows][ld], channels
+        0..nch-1, into d_thr int32 [nch] (and d_stats, _lib.ThrStats [nch]); device pointers or
+        torch tensors, asynchronous on the context stream (mkid_phase_thresholds)."""
+        self._chk(self._L.mkid_phase_thresholds(self._h, _ptr(d_raw), int(rows), int(ld), int(nch),
+                                                float(nsigma), _ptr(d_thr), _ptr(d_stats)))
+
+    def phase_thresholds_block_rows(self, rows, ld, nch, aligned16=True):
+        """Rows per workgroup row block of phase_thresholds_device for a block of that shape;
+        aligned16: whether the block starts on a 16-byte boundary."""
+        b = ctypes.c_int64()
+        self._chk(self._L.mkid_phase_thresholds_block_rows(self._h, int(rows), int(ld), int(nch),
+                                                           1 if aligned16 else 0, ctypes.byref(b)))
+        return b.value
+
+    def phase_thresholds_of(self, d_raw, rows, ld, nch, nsigma=2.5):
+        """(thr int32 [nch], med float64 [nch]) on the host for channels 0..nch-1 of device rows
+        d_raw[rows][ld] (pointer or tensor on this context's GPU): one phase_thresholds_device
+        call, one synchronisation and the copy of the 28 nch result bytes."""
+        import torch
+        dev = self.torch_device()
+        d_thr = torch.empty(nch, dtype=torch.int32, device=dev)
+        d_st = torch.empty(nch * ctypes.sizeof(_lib.ThrStats), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)      # d_raw may have been written on another stream
+        self.phase_thresholds_device(d_raw, rows, ld, nch, nsigma, d_thr, d_st)
+        torch.cuda.synchronize(dev)      # the call ran on the context's stream
+        st = d_st.cpu().numpy().view(np.dtype([('med', '<f8'), ('p05', '<f8'), ('lo', '<i4'), ('hi', '<i4')]))
+        return d_thr.cpu().numpy(), st['med'].copy()
+
+    def phase_thresholds(self, raw=None, nsigma=2.5):
+        """(thr int32 [nch], med float64 [nch]) of every channel of a phase block, computed on the
+        device: raw int16 [rows][nch] host array (uploaded), or None for the last process call's
+        raw phase where it lies (raw_phase_ptr). Bit-identical to
+        codecs.thresholds_from_phase_block / threshold_from_phase on the same rows."""
+        if raw is None:
+            d_raw, rows = self.raw_phase_ptr()
+            if rows < 1:
+                raise _lib.MkidError(_lib.MKID_E_STATE, 'phase_thresholds: no processed call to take rows from')
+            return self.phase_thresholds_of(d_raw, rows, self.C, self.C, nsigma)
+        import torch
+        r = np.ascontiguousarray(raw, np.int16)
+        if r.ndim != 2:
+            raise ValueError('raw must be [rows][channels]')
+        d_raw = torch.from_numpy(r).to(self.torch_device())
+        return self.phase_thresholds_of(d_raw, r.shape[0], r.shape[1], r.shape[1], nsigma)
+
+    def load_thresholds(self, nsigma=2.5):
+        """loadThresholds for every channel at once: the thresholds of the last process call's raw
+        phase (a quiet stretch of the stream), loaded with set_thresholds. The thresholds cross the
+        host once (4 C bytes); the re-arm levels follow them as for any set_thresholds.
+        Returns (thr, med)."""
+        thr, med = self.phase_thresholds(None, nsigma)
+        self.set_thresholds(thr)
+        return thr, med
+
     def set_iq_tap(self, channel):
         """Record channel's low-pass output (IQ snapshot source); channel < 0 turns it off."""
         self._chk(self._L.mkid_set_iq_tap(self._h, int(channel)))

@@ -169,6 +169,27 @@ def thresholds_from_phase_block(raw, nsigma=2.5):
                     np.int32)
 
 
+def phase_thresholds_host(raw, nsigma=2.5, nch=None, want_stats=False):
+    """raw [J][ld] Fix16_13 (int16) -> (thr int32 [nch], med float64 [nch]) for columns 0..nch-1 (all
+    by default) through libmkidgpu's mkid_phase_thresholds_host: the CPU statement of the device call
+    mkid_phase_thresholds, bit-identical to threshold_from_phase column by column under numpy 2. No
+    GPU is needed. want_stats adds the per-channel stats as a structured array (med, p05, lo, hi)."""
+    import ctypes
+    from . import _lib
+    r = np.ascontiguousarray(raw, np.int16)
+    if r.ndim != 2:
+        raise ValueError('raw must be [rows][channels]')
+    rows, ld = r.shape
+    nch = ld if nch is None else int(nch)
+    thr = np.zeros(max(nch, 0), np.int32)
+    stats = np.zeros(max(nch, 0), np.dtype([('med', '<f8'), ('p05', '<f8'), ('lo', '<i4'), ('hi', '<i4')]))
+    assert stats.dtype.itemsize == ctypes.sizeof(_lib.ThrStats)
+    _lib.check(_lib.load().mkid_phase_thresholds_host(
+        r.ctypes.data_as(ctypes.c_void_p), rows, ld, nch, float(nsigma),
+        thr.ctypes.data_as(ctypes.c_void_p), stats.ctypes.data_as(ctypes.c_void_p)))
+    return (thr, stats['med'].copy(), stats) if want_stats else (thr, stats['med'].copy())
+
+
 # ---- snapshots ----------------------------------------------------------------------------------
 def encode_snap_phase(raw):
     """Fix16_13 samples -> snapPhase_bram bytes (2 per word, halves swapped: decode reads [2:4]

@@ -1,11 +1,12 @@
 // C ABI of libmkidgpu.so (include/mkidgpu.h): calibration and pulse analysis — replay trigger,
-// template, optimal filter, bank filters, pulse heights, pulse capture, the synthetic ADC stream,
-// stream copy.
+// template, optimal filter, bank filters, pulse heights, pulse capture, phase thresholds, the
+// synthetic ADC stream, stream copy.
 // Every entry point that replaces buffers of the context allocates the new ones into locals and
 // moves them in, with the scalars that describe them, only once every allocation has succeeded.
 #include <cmath>
 
 #include "mkid_ctx.h"
+#include "thr_common.h"
 
 using namespace mkid;
 
@@ -264,6 +265,63 @@ int mkid_capture_pulses_counted(mkid_ctx* c, const float* d_phase, int64_t rows,
                                 int64_t* d_stamps, int32_t* d_info) {
     if (!d_count) return MKID_E_ARG;
     return capture_pulses(c, d_phase, rows, j0, d_events, d_count, cap, d_records, d_stamps, d_info);
+}
+
+// ---- thresholds from a phase block (loadThresholds) ----------------------------------------------
+static bool thr_args_ok(const int16_t* raw, int64_t rows, int64_t ld, int32_t nch, double nsigma, const int32_t* thr) {
+    return raw && thr && rows >= 1 && rows <= INT32_MAX && nch >= 1 && ld >= nch && std::isfinite(nsigma) &&
+           nsigma >= 0.0;
+}
+
+int mkid_phase_thresholds(mkid_ctx* c, const int16_t* d_raw, int64_t rows, int64_t ld, int32_t nch, double nsigma,
+                          int32_t* d_thr, mkid_thr_stats* d_stats) {
+    if (!c) return MKID_E_ARG;
+    if (!thr_args_ok(d_raw, rows, ld, nch, nsigma, d_thr))
+        FAIL(c, MKID_E_ARG, "phase_thresholds: need pointers, 1 <= rows < 2^31, 1 <= nch <= ld, finite nsigma >= 0");
+    HIPCHK(c, hipSetDevice(c->device));
+    const plan::ThrPlan p = plan::plan_thresholds(rows, ld, nch, ((uintptr_t)d_raw & 15) == 0, c->ncu);
+    if ((size_t)p.bytes > c->thrws_n) {   // grow the workspace
+        DevBuf<char> ws;
+        HIPCHK(c, ws.alloc((size_t)p.bytes));
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // an earlier call may still use the old one
+        c->d_thrws = std::move(ws), c->thrws_n = (size_t)p.bytes;
+    }
+    HIPCHK(c, launch_thresholds(d_raw, rows, ld, nch, nsigma, p, c->d_thrws.get(), d_thr, d_stats, c->stream));
+    return MKID_OK;
+}
+
+int mkid_phase_thresholds_block_rows(const mkid_ctx* c, int64_t rows, int64_t ld, int32_t nch, int32_t aligned16,
+                                     int64_t* block_rows) {
+    if (!c || !block_rows || rows < 1 || rows > INT32_MAX || nch < 1 || ld < nch) return MKID_E_ARG;
+    *block_rows = plan::plan_thresholds(rows, ld, nch, aligned16 != 0, c->ncu).B;
+    return MKID_OK;
+}
+
+// The CPU statement of the device call: the same cut tables, bin rule, prefix sums and finish
+// (thr_common.h), one channel at a time.
+int mkid_phase_thresholds_host(const int16_t* raw, int64_t rows, int64_t ld, int32_t nch, double nsigma,
+                               int32_t* thr_out, mkid_thr_stats* stats) {
+    if (!thr_args_ok(raw, rows, ld, nch, nsigma, thr_out)) return MKID_E_ARG;
+    for (int32_t ch = 0; ch < nch; ++ch) {
+        const int16_t* x = raw + ch;
+        int32_t lo = x[0], hi = x[0];
+        for (int64_t r = 1; r < rows; ++r) lo = std::min<int32_t>(lo, x[r * ld]), hi = std::max<int32_t>(hi, x[r * ld]);
+        const thr::Range rg = thr::make_range(lo, hi);
+        int32_t ct[thr::kBins + 1];
+        ct[0] = INT32_MIN, ct[thr::kBins] = INT32_MAX;
+        for (int i = 1; i < thr::kBins; ++i) ct[i] = thr::cut(rg, i);
+        uint32_t count[thr::kBins] = {0};
+        int b = 0;   // the estimate: the previous sample's bin
+        for (int64_t r = 0; r < rows; ++r) {
+            b = thr::bin_of(x[r * ld], ct, b);
+            ++count[b];
+        }
+        double n[thr::kBins];
+        for (int i = 0; i < thr::kBins; ++i) n[i] = thr::fraction(count[i], rows);
+        const thr::Pick p = thr::pick_scan([&n](int i) { return n[i]; }, 0, 1);
+        thr_out[ch] = thr::finish(lo, hi, p, nsigma, stats ? &stats[ch] : nullptr);
+    }
+    return MKID_OK;
 }
 
 int mkid_stream_copy(mkid_ctx* c, void* d_dst, const void* d_src, int64_t bytes) {

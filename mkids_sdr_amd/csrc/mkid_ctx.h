@@ -204,6 +204,9 @@ struct mkid_ctx : CtxHandles {
     size_t bankws_n = 0;
     struct TplSlot { mkid_bank_result result; int32_t ready; };
     DevBuf<TplSlot> d_tplslot;
+    // workspace of mkid_phase_thresholds (lazy, grown on demand; plan::plan_thresholds carves it)
+    DevBuf<char> d_thrws;
+    size_t thrws_n = 0;
     // host-API staging (lazy)
     DevBuf<uint32_t> d_in;
     DevBuf<float> d_phase_ws;

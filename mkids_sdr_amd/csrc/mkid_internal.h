@@ -252,6 +252,14 @@ struct BankArgs {
 };
 hipError_t launch_bank_filters(const BankArgs& a, hipStream_t s);
 
+// mkid_phase_thresholds (k_thresholds.hip): init, range pass, count pass and finish on stream s; `p`
+// is the call's plan (mkid_plan.h ThrPlan), ws its workspace of p.bytes bytes
+namespace plan {
+struct ThrPlan;
+}
+hipError_t launch_thresholds(const int16_t* raw, int64_t rows, int64_t ld, int32_t nch, double nsigma,
+                             const plan::ThrPlan& p, char* ws, int32_t* thr, mkid_thr_stats* stats, hipStream_t s);
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device), thread-safe: the
 // attribute is per device, and several contexts (devices, host threads) may launch concurrently.
 // `mask` is one static per kernel instantiation; the call is idempotent, so a race only repeats it.

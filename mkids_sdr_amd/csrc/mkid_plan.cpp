@@ -285,5 +285,30 @@ BankWs plan_bank(int64_t Cb, int64_t R, int64_t budget, int64_t want) {
     return w;
 }
 
+ThrPlan plan_thresholds(int64_t rows, int64_t ld, int32_t nch, bool aligned16, int ncu) {
+    ThrPlan p;
+    p.vec = (aligned16 && ld % 8 == 0) ? 8 : 1;
+    p.nch_vec = p.vec == 8 ? (nch / 8) * 8 : 0;
+    p.strips_vec = (p.nch_vec + kThrStrip - 1) / kThrStrip;
+    p.strips_tail = ((int64_t)nch - p.nch_vec + kThrStrip - 1) / kThrStrip;
+    const int64_t strips = p.strips_vec + p.strips_tail;
+    const int64_t target = 2 * (int64_t)std::max(ncu, 1);
+    // rows per block so that strips x row blocks is about the target: rows strips / target, rounded up
+    // (rows < 2^31 and strips < 2^26: the product fits)
+    int64_t B = (rows * strips + target - 1) / target;
+    B = (B + kThrRowStep - 1) / kThrRowStep * kThrRowStep;
+    p.B = std::min(std::max(B, kThrMinB), kThrMaxB);
+    p.row_blocks = (rows + p.B - 1) / p.B;
+    p.grid_vec = std::min(p.strips_vec * p.row_blocks, kThrMaxGrid);
+    p.grid_tail = std::min(p.strips_tail * p.row_blocks, kThrMaxGrid);
+    p.grid_init = std::min(((int64_t)nch * 100 + kThrThreads - 1) / kThrThreads, kThrMaxInitGrid);
+    p.grid_finish = ((int64_t)nch + kThrFinishCh - 1) / kThrFinishCh;
+    p.off_lo = 0;
+    p.off_hi = (int64_t)nch * 4;
+    p.off_counts = (int64_t)nch * 8;
+    p.bytes = p.off_counts + (int64_t)nch * 400;
+    return p;
+}
+
 }  // namespace plan
 }  // namespace mkid

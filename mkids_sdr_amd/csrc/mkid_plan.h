@@ -2,8 +2,9 @@
 // AddressSanitizer / UndefinedBehaviorSanitizer (make -C mkids_sdr_amd/csrc asan; tools/plan_fuzz.cpp):
 // workspace sizing at context creation, the per-call trigger segmentation and its slot-table
 // geometry, the k_front3 select-slot order, the K1 tap quantisation, the merge of per-chunk packet
-// lists, the reference packet re-encode, the validity bookkeeping of a carried history and the
-// grouping and workspace layout of mkid_bank_filters. The host
+// lists, the reference packet re-encode, the validity bookkeeping of a carried history, the
+// grouping and workspace layout of mkid_bank_filters and the launch geometry and workspace of
+// mkid_phase_thresholds. The host
 // files mkid_api.hip, mkid_stream.hip and mkid_calib.hip are the only product callers.
 #pragma once
 #include <stdint.h>
@@ -97,6 +98,31 @@ struct BankWs {
             coeff = 0, refmed = 0, accept = 0, appended = 0, status = 0, nready = 0;
 };
 BankWs plan_bank(int64_t Cb, int64_t R, int64_t budget, int64_t want = 0);
+
+// mkid_phase_thresholds (k_thresholds.hip): a workgroup of kThrThreads threads takes a strip of
+// kThrStrip channels x a block of B rows; a thread holds `vec` adjacent channels of a row (8: one
+// 16-byte load, when the block is 16-byte aligned and ld a multiple of 8; else 1). Channels
+// [0, nch_vec) run vec-wide, the tail [nch_vec, nch) one channel per thread. B is a multiple of
+// kThrRowStep in kThrMinB..kThrMaxB that gives about two workgroups per compute unit where the
+// block is large enough; the jobs (strip x row block) of either launch are walked by a grid of at
+// most kThrMaxGrid workgroups. Workspace: lo [nch] int32, hi [nch] int32, counts [nch][100] uint32
+// at the byte offsets below.
+constexpr int kThrStrip = 64;
+constexpr int kThrThreads = 256;
+constexpr int64_t kThrRowStep = 32, kThrMinB = 128, kThrMaxB = 1024;
+constexpr int64_t kThrMaxGrid = 1 << 20;
+constexpr int kThrFinishCh = 16;          // channels a finish workgroup takes
+constexpr int64_t kThrMaxInitGrid = 4096; // the init kernel strides over [nch][100]
+struct ThrPlan {
+    int32_t vec = 1, nch_vec = 0;
+    int64_t B = 0, row_blocks = 0;
+    int64_t strips_vec = 0, strips_tail = 0;   // strips of the two launches
+    int64_t grid_vec = 0, grid_tail = 0;       // their grids (0: no launch)
+    int64_t grid_init = 0, grid_finish = 0;    // workgroups of the init and the finish kernel
+    int64_t off_lo = 0, off_hi = 0, off_counts = 0, bytes = 0;
+};
+// rows >= 1, 1 <= nch <= ld, ncu >= 1 (the entry point checks)
+ThrPlan plan_thresholds(int64_t rows, int64_t ld, int32_t nch, bool aligned16, int ncu);
 
 // k_front3 select-slot order (mkid_api.hip / include/mkidgpu.h mkid_slot_order): out[slot] = channel
 void slot_order(const std::vector<int32_t>& bins, int C, std::vector<int16_t>& out);

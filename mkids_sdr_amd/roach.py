@@ -611,6 +611,36 @@ class RoachPulses:
     def loadThresholds(self):
         return [self.loadSingleThreshold(ch) for ch in range(self.N_freqs)]
 
+    def loadThresholdsBlock(self, steps=10, L=2 ** 10, nsigma=2.5):
+        """loadThresholds for every channel < N_freqs from ONE block of the running stream: one
+        run(steps * L), the threshold rule on the device for all channels at once
+        (Channelizer.phase_thresholds, bit-identical to codecs.threshold_from_phase on each column of
+        that block), customThresholds applied by loadSingleThreshold's rule, self.thresholds /
+        self.medians filled in degrees the same way, and the thresholds loaded through the shim's
+        threshold state, so that a later register-level write to one channel composes with it.
+        loadThresholds / loadSingleThreshold snapshot a different stretch of the stream for each
+        channel (steps snapshots of L samples one channel after the other), so the two methods see
+        different noise and are not expected to agree bit for bit. Returns the loaded thresholds."""
+        roach = self.roach
+        rows, nf = int(steps) * int(L), int(self.N_freqs)
+        phase, _ = roach.run(rows)
+        ch = roach.channelizer()
+        d_raw, have = ch.raw_phase_ptr()
+        if have == rows:      # the call was one piece: its Fix16_13 rows are still on the device
+            thr, med = ch.phase_thresholds_of(d_raw, rows, ch.C, nf, nsigma)
+        else:                 # run in pieces: the device's quantisation of the returned phase (_raw_of)
+            raw = np.clip(np.rint(phase[:, :nf] * np.float32(8192)), -25736, 25736).astype(np.int16)
+            thr, med = ch.phase_thresholds(raw, nsigma)
+        self.thresholds[:nf] = self.scale_to_angle * thr
+        self.medians[:nf] = self.scale_to_angle * med
+        loaded = [int(t) for t in thr]
+        for c in range(nf):
+            if self.customThresholds[c] != 360.0:
+                loaded[c] = max(int(self.customThresholds[c] / self.scale_to_angle), -25736)
+        roach.cfg.thr[:nf] = loaded
+        roach.cfg.dirty.add('thr')
+        return loaded
+
     def _snap_qdr(self, ch, steps, L=2 ** 10, n_qdr=2 ** 19):
         """The snapshot loop shared by longsnapshot and contsnapshot (ROACH_Pulses.py:449-463,
         585-597): per step arm snapPhase + snapqdr, read 2^10 snapPhase words and 2^19 qdr0 words."""

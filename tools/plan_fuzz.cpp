@@ -396,6 +396,70 @@ static void fuzz_bank(int iters) {
     CHECK(iters < 100 || over > 0, "no one-channel plan above the budget in %d iterations", iters);
 }
 
+// plan_thresholds (mkid_phase_thresholds): the row blocks cover the rows once, the two launches'
+// strips cover the channels once with whole 8-channel threads in the vector launch, the jobs of a
+// small block replayed as the kernels decode them touch every sample once and stay inside the
+// block, and the workspace tables lie inside `bytes` without overlap.
+static void fuzz_thresholds(int iters) {
+    for (int it = 0; it < iters; ++it) {
+        const bool small = rint_(0, 1) == 0;
+        const int64_t rows = small ? rint_(1, 700) : (rint_(0, 3) == 0 ? rint_(1, (1ll << 31) - 1) : rint_(1, 20000));
+        const int32_t nch = (int32_t)(small ? rint_(1, 200) : (rint_(0, 3) == 0 ? rint_(1, (1ll << 31) - 1) : rint_(1, 5000)));
+        const int64_t ld = std::min<int64_t>((int64_t)nch + (rint_(0, 1) ? 0 : rint_(0, 40)), (1ll << 31) - 1);
+        const bool aligned = rint_(0, 2) != 0;
+        const int ncu = (int)rint_(1, 512);
+        const ThrPlan p = plan_thresholds(rows, ld, nch, aligned, ncu);
+        CHECK(p.B >= kThrMinB && p.B <= kThrMaxB && p.B % kThrRowStep == 0, "B %lld", (long long)p.B);
+        CHECK(p.row_blocks >= 1 && p.row_blocks * p.B >= rows && (p.row_blocks - 1) * p.B < rows,
+              "%lld row blocks of %lld for %lld rows", (long long)p.row_blocks, (long long)p.B, (long long)rows);
+        CHECK(p.vec == 1 || (p.vec == 8 && aligned && ld % 8 == 0), "vec %d (ld %lld)", p.vec, (long long)ld);
+        CHECK(p.nch_vec >= 0 && p.nch_vec <= nch && p.nch_vec % 8 == 0 && (p.vec == 8 || p.nch_vec == 0) &&
+                  (p.vec == 1 || nch - p.nch_vec < 8),
+              "nch_vec %d of %d", p.nch_vec, nch);
+        CHECK(p.strips_vec * kThrStrip >= p.nch_vec && (p.strips_vec == 0 || (p.strips_vec - 1) * kThrStrip < p.nch_vec),
+              "vector strips %lld", (long long)p.strips_vec);
+        CHECK(p.strips_tail * kThrStrip >= nch - p.nch_vec &&
+                  (p.strips_tail == 0 || (p.strips_tail - 1) * kThrStrip < nch - p.nch_vec),
+              "tail strips %lld", (long long)p.strips_tail);
+        CHECK(p.grid_vec <= kThrMaxGrid && p.grid_tail <= kThrMaxGrid && (p.grid_vec > 0) == (p.strips_vec > 0) &&
+                  (p.grid_tail > 0) == (p.strips_tail > 0) && p.grid_vec <= p.strips_vec * p.row_blocks &&
+                  p.grid_tail <= p.strips_tail * p.row_blocks,
+              "grids %lld %lld", (long long)p.grid_vec, (long long)p.grid_tail);
+        CHECK(p.grid_init >= 1 && p.grid_init <= kThrMaxInitGrid && p.grid_finish >= 1 &&
+                  p.grid_finish * kThrFinishCh >= nch && (p.grid_finish - 1) * kThrFinishCh < nch,
+              "init grid %lld, finish grid %lld for %d channels", (long long)p.grid_init, (long long)p.grid_finish, nch);
+        CHECK(p.off_lo == 0 && p.off_hi == p.off_lo + 4ll * nch && p.off_counts == p.off_hi + 4ll * nch &&
+                  p.bytes == p.off_counts + 400ll * nch,
+              "workspace layout for %d channels", nch);
+        if (!small) continue;
+        // replay both launches' jobs as k_thresholds.hip's Job decodes them
+        std::vector<uint8_t> seen((size_t)(rows * ld), 0);
+        for (int launch = 0; launch < 2; ++launch) {
+            const int V = launch == 0 ? 8 : 1;
+            const int64_t cbeg = launch == 0 ? 0 : p.nch_vec, cend = launch == 0 ? p.nch_vec : nch;
+            const int64_t strips = launch == 0 ? p.strips_vec : p.strips_tail;
+            if (launch == 0 && p.vec != 8) continue;
+            const int cols = kThrStrip / V, rslots = kThrThreads / cols;
+            for (int64_t job = 0; job < strips * p.row_blocks; ++job) {
+                const int64_t rb = job / strips, st = job - rb * strips;
+                const int64_t r0 = rb * p.B, r1 = std::min(r0 + p.B, rows), c0 = cbeg + st * kThrStrip;
+                const int64_t nloc = std::min<int64_t>(cend - c0, kThrStrip);
+                CHECK(nloc >= 1, "empty strip");
+                for (int t = 0; t < kThrThreads; ++t) {
+                    const int col = t % cols, rslot = t / cols;
+                    if (col * V >= nloc) continue;
+                    for (int64_t r = r0 + rslot; r < r1; r += rslots)
+                        for (int k = 0; k < V; ++k) ++seen[(size_t)(r * ld + c0 + col * V + k)];   // ASan: in the block
+                }
+            }
+        }
+        bool once = true;
+        for (int64_t r = 0; r < rows; ++r)
+            for (int64_t c = 0; c < ld; ++c) once = once && seen[(size_t)(r * ld + c)] == (c < nch ? 1 : 0);
+        CHECK(once, "jobs do not touch every sample of %lld x %d (ld %lld) once", (long long)rows, nch, (long long)ld);
+    }
+}
+
 int main(int argc, char** argv) {
     const int iters = argc > 1 ? atoi(argv[1]) : 300;
     rng.seed(argc > 2 ? strtoull(argv[2], nullptr, 10) : 12345);
@@ -407,6 +471,7 @@ int main(int argc, char** argv) {
     fuzz_merge_pack(iters);
     fuzz_carry(iters);
     fuzz_bank(iters);
+    fuzz_thresholds(iters / 2 + 1);
     if (failures) {
         fprintf(stderr, "%d failures\n", failures);
         return 1;
