@@ -439,6 +439,40 @@ int mkid_phase_thresholds_host(const int16_t* raw, int64_t rows, int64_t ld, int
 int mkid_phase_thresholds_block_rows(const mkid_ctx* ctx, int64_t rows, int64_t ld, int32_t nch,
                                      int32_t aligned16, int64_t* block_rows);
 
+/* Every channel's phase-noise spectrum from a Fix16_13 phase block in one call: the reference's
+ * longsnapshot rule (ROACH_Pulses.py:521-543; mkids_sdr_amd.codecs.noise_spectrum) for columns
+ * 0..nch-1 of d_raw [rows][ld] int16 (the layout of mkid_replay_trigger and mkid_phase_thresholds;
+ * e.g. mkid_last_raw_phase of a quiet call). Only the arithmetic width differs from the reference.
+ *   n = rows / n_averages (integer division); rows at or beyond n n_averages are never read
+ *   piece a of channel c: x_a[j] = scale raw[(a n + j) ld + c], j < n
+ *   spec[c][k] = (1 / n_averages) sum_a 20 log10(|X_a[k]| / norm1 / 1e-6), X_a = DFT_n(x_a),
+ *   all n bins in np.fft.fft order; the factor scale / norm1 / 1e-6 is one float64 constant added
+ *   after the logarithm. |X| == 0 gives -inf (as numpy), and so does the mean over the pieces then;
+ *   finite input never gives NaN.
+ * A channel's n outputs depend only on its own column, rows, n_averages, scale and norm1: not on its
+ * index, nch, ld, the block's alignment, its neighbours or any grouping, and they are the same bits
+ * from run to run (the pieces are added in a fixed order, without floating-point atomics). Two
+ * pieces of one channel travel as the real and imaginary part of one complex transform; an odd
+ * n_averages leaves the last piece unpaired. Every n in 1..MKID_NOISE_MAX_N is supported, primes
+ * included: a mixed-radix transform over n's prime factors, a piece held in LDS as complex float32
+ * (MKID_NOISE_MAX_N x 8 B = 128 KiB), at a cost of n x (sum of the prime factors) per piece.
+ *   - mkid_phase_noise_spectra: device pointers only, asynchronous on the context stream; nch need
+ *     not equal the context's C; the block is never written. The tables for an n (twiddles, radix
+ *     tables, index maps: under 200 KiB, no workspace that grows with rows or nch) are owned by the
+ *     context and made when a call brings a new n: allocate, upload, synchronise once, move in. A
+ *     call with the n of the call before makes no device-to-host copy and no synchronisation.
+ *     MKID_E_ARG before any launch, d_spec untouched: a null pointer, rows < 1 or > 2^31 - 1,
+ *     nch < 1 or > ld, n_averages < 1 or > rows, n > MKID_NOISE_MAX_N, scale or norm1 not finite
+ *     or <= 0. Not timed (no MKID_K_ id).
+ *   - mkid_phase_noise_spectra_host: the same rule in float64 on host memory through the same
+ *     definitions (csrc/noise_common.h, the plan of csrc/mkid_plan.h); needs no device and no
+ *     context. The same MKID_E_ARG cases. */
+#define MKID_NOISE_MAX_N 16384
+int mkid_phase_noise_spectra(mkid_ctx* ctx, const int16_t* d_raw, int64_t rows, int64_t ld, int32_t nch,
+                             int32_t n_averages, double scale, double norm1, double* d_spec /* [nch][n] */);
+int mkid_phase_noise_spectra_host(const int16_t* raw, int64_t rows, int64_t ld, int32_t nch,
+                                  int32_t n_averages, double scale, double norm1, double* spec);
+
 /* Kernel timing with HIP events on the context stream (for bench roofline numbers). */
 #define MKID_K_CHANNELIZE 0
 #define MKID_K_FIR_PHASE 1

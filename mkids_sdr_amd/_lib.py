@@ -133,6 +133,8 @@ _SIGS = {
     'mkid_phase_thresholds': [P, P, I64, I64, I32, ctypes.c_double, P, P],
     'mkid_phase_thresholds_host': [P, I64, I64, I32, ctypes.c_double, P, P],
     'mkid_phase_thresholds_block_rows': [P, I64, I64, I32, I32, P],
+    'mkid_phase_noise_spectra': [P, P, I64, I64, I32, I32, ctypes.c_double, ctypes.c_double, P],
+    'mkid_phase_noise_spectra_host': [P, I64, I64, I32, I32, ctypes.c_double, ctypes.c_double, P],
     'mkid_stream_copy': [P, P, P, I64],
     'mkid_synth_adc': [P, P, I64, I64, P, P, P, I64, ctypes.c_float, ctypes.c_float, I32,
                        ctypes.c_float, ctypes.c_uint32],

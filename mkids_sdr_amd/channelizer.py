@@ -9,7 +9,7 @@ import ctypes
 
 import numpy as np
 
-from . import _lib
+from . import _lib, codecs
 from .pfb import pfb_prototype
 
 
@@ -229,6 +229,45 @@ class Channelizer:
         thr, med = self.phase_thresholds(None, nsigma)
         self.set_thresholds(thr)
         return thr, med
+
+    # ---- phase-noise spectra of a phase block (longsnapshot's noise FFT, ROACH_Pulses.py:521-543) --
+    def noise_spectra_device(self, d_raw, rows, ld, nch, n_averages, scale, norm1, d_spec):
+        """The reference's phase-noise spectrum of channels 0..nch-1 of device Fix16_13 rows
+        d_raw[rows][ld] into d_spec float64 [nch][rows // n_averages]; device pointers or torch
+        tensors, asynchronous on the context stream (mkid_phase_noise_spectra)."""
+        self._chk(self._L.mkid_phase_noise_spectra(self._h, _ptr(d_raw), int(rows), int(ld), int(nch),
+                                                   int(n_averages), float(scale), float(norm1), _ptr(d_spec)))
+
+    def noise_spectra_of(self, d_raw, rows, ld, nch, n_averages=100, norm1=50.0):
+        """(np.fft.fftfreq(n), spec float64 [nch][n]) on the host, n = rows // n_averages, for
+        channels 0..nch-1 of device rows d_raw[rows][ld] (pointer or tensor on this context's GPU),
+        in degrees (scale = codecs.SCALE_TO_ANGLE): one noise_spectra_device call, one
+        synchronisation and the copy of the result."""
+        import torch
+        dev = self.torch_device()
+        n = int(rows) // int(n_averages) if n_averages >= 1 else 0
+        d_spec = torch.empty((int(nch), max(n, 0)), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)      # d_raw may have been written on another stream
+        self.noise_spectra_device(d_raw, rows, ld, nch, n_averages, codecs.SCALE_TO_ANGLE, norm1, d_spec)
+        torch.cuda.synchronize(dev)      # the call ran on the context's stream
+        return np.fft.fftfreq(n), d_spec.cpu().numpy()
+
+    def noise_spectra(self, raw=None, n_averages=100, norm1=50.0):
+        """(np.fft.fftfreq(n), spec float64 [nch][n]) of every channel of a phase block, computed on
+        the device: raw int16 [rows][nch] host array (uploaded), or None for the last process call's
+        raw phase where it lies (raw_phase_ptr). codecs.noise_spectrum(raw[:, c] * SCALE_TO_ANGLE,
+        n_averages, norm1) channel by channel, in float32 arithmetic."""
+        if raw is None:
+            d_raw, rows = self.raw_phase_ptr()
+            if rows < 1:
+                raise _lib.MkidError(_lib.MKID_E_STATE, 'noise_spectra: no processed call to take rows from')
+            return self.noise_spectra_of(d_raw, rows, self.C, self.C, n_averages, norm1)
+        import torch
+        r = np.ascontiguousarray(raw, np.int16)
+        if r.ndim != 2:
+            raise ValueError('raw must be [rows][channels]')
+        d_raw = torch.from_numpy(r).to(self.torch_device())
+        return self.noise_spectra_of(d_raw, r.shape[0], r.shape[1], r.shape[1], n_averages, norm1)
 
     def set_iq_tap(self, channel):
         """Record channel's low-pass output (IQ snapshot source); channel < 0 turns it off."""

@@ -225,6 +225,26 @@ def noise_spectrum(phase_deg, n_averages=100, norm1=50.0):
     return np.fft.fftfreq(n), spec
 
 
+def phase_noise_spectra_host(raw, n_averages=100, norm1=50.0, nch=None, scale=SCALE_TO_ANGLE):
+    """raw [rows][ld] Fix16_13 (int16) -> (fftfreq(n), spec float64 [nch][n]), n = rows // n_averages,
+    for columns 0..nch-1 (all by default) through libmkidgpu's mkid_phase_noise_spectra_host: the CPU
+    statement, in float64, of the device call mkid_phase_noise_spectra, i.e.
+    noise_spectrum(raw[:, c] * scale, n_averages, norm1) column by column. No GPU is needed."""
+    import ctypes
+    from . import _lib
+    r = np.ascontiguousarray(raw, np.int16)
+    if r.ndim != 2:
+        raise ValueError('raw must be [rows][channels]')
+    rows, ld = r.shape
+    nch = ld if nch is None else int(nch)
+    n = rows // int(n_averages) if n_averages >= 1 else 0
+    spec = np.zeros((max(nch, 0), n), np.float64)
+    _lib.check(_lib.load().mkid_phase_noise_spectra_host(
+        r.ctypes.data_as(ctypes.c_void_p), rows, ld, nch, int(n_averages), float(scale), float(norm1),
+        spec.ctypes.data_as(ctypes.c_void_p)))
+    return np.fft.fftfreq(n), spec
+
+
 def encode_conv_phase_snap(raw):
     """conv_phase_snapPhase_bram: one sample per word in bytes [2:4] (pulse_triggering_v2.py:94)."""
     r = np.asarray(raw, np.int64)

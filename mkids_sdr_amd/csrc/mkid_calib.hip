@@ -1,11 +1,12 @@
 // C ABI of libmkidgpu.so (include/mkidgpu.h): calibration and pulse analysis — replay trigger,
-// template, optimal filter, bank filters, pulse heights, pulse capture, phase thresholds, the
-// synthetic ADC stream, stream copy.
+// template, optimal filter, bank filters, pulse heights, pulse capture, phase thresholds, phase-noise
+// spectra, the synthetic ADC stream, stream copy.
 // Every entry point that replaces buffers of the context allocates the new ones into locals and
 // moves them in, with the scalars that describe them, only once every allocation has succeeded.
 #include <cmath>
 
 #include "mkid_ctx.h"
+#include "noise_common.h"
 #include "thr_common.h"
 
 using namespace mkid;
@@ -320,6 +321,76 @@ int mkid_phase_thresholds_host(const int16_t* raw, int64_t rows, int64_t ld, int
         for (int i = 0; i < thr::kBins; ++i) n[i] = thr::fraction(count[i], rows);
         const thr::Pick p = thr::pick_scan([&n](int i) { return n[i]; }, 0, 1);
         thr_out[ch] = thr::finish(lo, hi, p, nsigma, stats ? &stats[ch] : nullptr);
+    }
+    return MKID_OK;
+}
+
+// ---- phase-noise spectra from a phase block (longsnapshot's noise FFT) ----------------------------
+static bool noise_args_ok(const int16_t* raw, int64_t rows, int64_t ld, int32_t nch, int32_t n_averages, double scale,
+                          double norm1, const double* spec) {
+    return raw && spec && rows >= 1 && rows <= INT32_MAX && nch >= 1 && ld >= nch && n_averages >= 1 &&
+           n_averages <= rows && rows / n_averages <= MKID_NOISE_MAX_N && std::isfinite(scale) && scale > 0.0 &&
+           std::isfinite(norm1) && norm1 > 0.0;
+}
+#define NOISE_ARGS_MSG \
+    "need pointers, 1 <= rows < 2^31, 1 <= nch <= ld, 1 <= n_averages <= rows, rows / n_averages <= 16384, finite scale, norm1 > 0"
+
+// spec = mul * (sum over the pieces of log2 |X|^2) + add
+static void noise_constants(int32_t n_averages, double scale, double norm1, double& mul, double& add) {
+    mul = 10.0 * std::log10(2.0) / (double)n_averages;
+    add = 20.0 * std::log10(scale / norm1 / 1e-6);
+}
+
+int mkid_phase_noise_spectra(mkid_ctx* c, const int16_t* d_raw, int64_t rows, int64_t ld, int32_t nch,
+                             int32_t n_averages, double scale, double norm1, double* d_spec) {
+    if (!c) return MKID_E_ARG;
+    if (!noise_args_ok(d_raw, rows, ld, nch, n_averages, scale, norm1, d_spec))
+        FAIL(c, MKID_E_ARG, "phase_noise_spectra: " NOISE_ARGS_MSG);
+    HIPCHK(c, hipSetDevice(c->device));
+    const int32_t n = (int32_t)(rows / n_averages);
+    if (c->noise_plan.n != n) {   // another n: make its tables, then replace the old ones
+        plan::NoisePlan p;
+        if (!plan::plan_noise(n, p)) FAIL(c, MKID_E_ARG, "phase_noise_spectra: no plan for this n");
+        std::vector<char> image((size_t)p.bytes);
+        plan::noise_pack_tables(p, image.data());
+        DevBuf<char> tab;
+        HIPCHK(c, tab.alloc((size_t)p.bytes));
+        HIPCHK(c, hipMemcpyAsync(tab.get(), image.data(), (size_t)p.bytes, hipMemcpyHostToDevice, c->stream));
+        // the upload has left `image`, and an earlier call may still use the old tables
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        p.wn = {}, p.wr = {}, p.bin_of_pos = {}, p.partner = {};   // the context keeps passes and offsets
+        c->d_noisetab = std::move(tab), c->noise_plan = std::move(p);
+    }
+    double mul, add;
+    noise_constants(n_averages, scale, norm1, mul, add);
+    HIPCHK(c, launch_noise(d_raw, ld, nch, n_averages, mul, add, c->noise_plan, c->d_noisetab.get(), d_spec, c->stream));
+    return MKID_OK;
+}
+
+// The CPU statement of the device call: the same plan, passes, unpacking and finish
+// (noise_common.h) in float64, one channel at a time.
+int mkid_phase_noise_spectra_host(const int16_t* raw, int64_t rows, int64_t ld, int32_t nch, int32_t n_averages,
+                                  double scale, double norm1, double* spec) {
+    if (!noise_args_ok(raw, rows, ld, nch, n_averages, scale, norm1, spec)) return MKID_E_ARG;
+    const int32_t n = (int32_t)(rows / n_averages);
+    plan::NoisePlan p;
+    if (!plan::plan_noise(n, p)) return MKID_E_ARG;
+    const noise::View<double> v{n, (int32_t)p.passes.size(), p.passes.data(), p.wn.data(), p.wr.data(),
+                                p.bin_of_pos.data(), p.partner.data()};
+    double mul, add;
+    noise_constants(n_averages, scale, norm1, mul, add);
+    std::vector<noise::Cx<double>> z((size_t)n), y((size_t)n);
+    std::vector<double> acc((size_t)n);
+    for (int32_t ch = 0; ch < nch; ++ch) {
+        std::fill(acc.begin(), acc.end(), 0.0);
+        for (int32_t a = 0; a < n_averages; a += 2) {
+            const int16_t* colA = raw + (int64_t)a * n * ld + ch;
+            const int16_t* colB = a + 1 < n_averages ? colA + (int64_t)n * ld : nullptr;
+            noise::pair_host<double>(v, colA, colB, ld, z.data(), y.data(), acc.data(),
+                                     [](double x) { return std::log2(x); });
+        }
+        for (int32_t pos = 0; pos < n; ++pos)
+            spec[(int64_t)ch * n + p.bin_of_pos[(size_t)pos]] = noise::finish(acc[(size_t)pos], mul, add);
     }
     return MKID_OK;
 }

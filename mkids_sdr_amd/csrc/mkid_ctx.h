@@ -207,6 +207,10 @@ struct mkid_ctx : CtxHandles {
     // workspace of mkid_phase_thresholds (lazy, grown on demand; plan::plan_thresholds carves it)
     DevBuf<char> d_thrws;
     size_t thrws_n = 0;
+    // tables of mkid_phase_noise_spectra for the last call's n (lazy; noise_plan.n == 0: none;
+    // plan::noise_pack_tables lays them out; noise_plan keeps the passes and offsets only)
+    DevBuf<char> d_noisetab;
+    mkid::plan::NoisePlan noise_plan;
     // host-API staging (lazy)
     DevBuf<uint32_t> d_in;
     DevBuf<float> d_phase_ws;

@@ -260,6 +260,14 @@ struct ThrPlan;
 hipError_t launch_thresholds(const int16_t* raw, int64_t rows, int64_t ld, int32_t nch, double nsigma,
                              const plan::ThrPlan& p, char* ws, int32_t* thr, mkid_thr_stats* stats, hipStream_t s);
 
+// mkid_phase_noise_spectra (k_noise.hip): one launch on stream s; `p` is the plan of n (its passes,
+// geometry and table offsets), tab the device image of its tables; spec = acc * mul + add
+namespace plan {
+struct NoisePlan;
+}
+hipError_t launch_noise(const int16_t* raw, int64_t ld, int32_t nch, int32_t n_averages, double mul, double add,
+                        const plan::NoisePlan& p, const char* tab, double* spec, hipStream_t s);
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device), thread-safe: the
 // attribute is per device, and several contexts (devices, host threads) may launch concurrently.
 // `mask` is one static per kernel instantiation; the call is idempotent, so a race only repeats it.

@@ -310,5 +310,74 @@ ThrPlan plan_thresholds(int64_t rows, int64_t ld, int32_t nch, bool aligned16, i
     return p;
 }
 
+// exp(-2 pi i k / m), exact at the quarter turns: radix-2 and radix-4 butterflies then add and
+// subtract only, and the bins of an integer piece that are sums and differences stay exact
+static noise::Cx<double> unit_root(int64_t k, int64_t m) {
+    if (4 * k % m == 0) {
+        const noise::Cx<double> q[4] = {{1.0, 0.0}, {0.0, -1.0}, {-1.0, 0.0}, {0.0, 1.0}};
+        return q[4 * k / m];
+    }
+    const double a = -6.283185307179586476925286766559 * (double)k / (double)m;
+    return {std::cos(a), std::sin(a)};
+}
+
+bool plan_noise(int32_t n, NoisePlan& p) {
+    p = NoisePlan{};
+    if (n < 1 || n > MKID_NOISE_MAX_N) return false;
+    static_assert(MKID_NOISE_MAX_N <= 65536 && MKID_NOISE_MAX_N <= kNoiseThreadsLarge * kNoisePerLarge, "uint16 index tables");
+    p.n = n;
+    std::vector<int32_t> radix;
+    int32_t m = n, twos = 0;
+    while (m % 2 == 0) m /= 2, ++twos;
+    for (int i = 0; i < twos / 2; ++i) radix.push_back(4);
+    if (twos % 2) radix.push_back(2);
+    for (int32_t f = 3; m > 1; f += 2) {
+        if ((int64_t)f * f > m) f = m;
+        while (m % f == 0) m /= f, radix.push_back(f);
+    }
+    std::sort(radix.begin(), radix.end(), [](int32_t a, int32_t b) { return a > b; });
+    int32_t L = n, tw = 0;
+    for (int32_t r : radix) {
+        p.passes.push_back(noise::Pass{r, L, L / r, n / L, tw});
+        for (int32_t i = 0; i < r; ++i) p.wr.push_back(unit_root(i, r));
+        L /= r, tw += r;
+    }
+    p.wn.resize((size_t)n);
+    for (int32_t i = 0; i < n; ++i) p.wn[(size_t)i] = unit_root(i, n);
+    // position p = t_0 M_0 + t_1 M_1 + ... holds bin t_0 + r_0 (t_1 + r_1 (t_2 + ...))
+    p.bin_of_pos.resize((size_t)n);
+    std::vector<uint16_t> pos_of_bin((size_t)n);
+    for (int32_t pos = 0; pos < n; ++pos) {
+        int32_t rem = pos, k = 0, w = 1;
+        for (const noise::Pass& ps : p.passes) k += (rem / ps.M) * w, rem %= ps.M, w *= ps.r;
+        p.bin_of_pos[(size_t)pos] = (uint16_t)k;
+        pos_of_bin[(size_t)k] = (uint16_t)pos;
+    }
+    p.partner.resize((size_t)n);
+    for (int32_t pos = 0; pos < n; ++pos)
+        p.partner[(size_t)pos] = pos_of_bin[(size_t)((n - p.bin_of_pos[(size_t)pos]) % n)];
+    const bool large = n > kNoiseThreadsSmall * kNoisePerSmall;
+    p.threads = large ? kNoiseThreadsLarge : kNoiseThreadsSmall;
+    p.per_thread = large ? kNoisePerLarge : kNoisePerSmall;
+    p.lds_bytes = 8ll * n + 8ll * kNoiseStageR + 16ll * (p.threads / 64);
+    const auto up = [](int64_t v) { return (v + 15) / 16 * 16; };
+    p.off_wn = 0;
+    p.off_wr = up(8ll * n);
+    p.off_bin = up(p.off_wr + 8ll * tw);
+    p.off_partner = up(p.off_bin + 2ll * n);
+    p.bytes = up(p.off_partner + 2ll * n);
+    return true;
+}
+
+void noise_pack_tables(const NoisePlan& p, char* out) {
+    std::fill(out, out + p.bytes, 0);
+    float* wn = (float*)(out + p.off_wn);
+    for (size_t i = 0; i < p.wn.size(); ++i) wn[2 * i] = (float)p.wn[i].re, wn[2 * i + 1] = (float)p.wn[i].im;
+    float* wr = (float*)(out + p.off_wr);
+    for (size_t i = 0; i < p.wr.size(); ++i) wr[2 * i] = (float)p.wr[i].re, wr[2 * i + 1] = (float)p.wr[i].im;
+    std::copy(p.bin_of_pos.begin(), p.bin_of_pos.end(), (uint16_t*)(out + p.off_bin));
+    std::copy(p.partner.begin(), p.partner.end(), (uint16_t*)(out + p.off_partner));
+}
+
 }  // namespace plan
 }  // namespace mkid

@@ -3,8 +3,8 @@
 // workspace sizing at context creation, the per-call trigger segmentation and its slot-table
 // geometry, the k_front3 select-slot order, the K1 tap quantisation, the merge of per-chunk packet
 // lists, the reference packet re-encode, the validity bookkeeping of a carried history, the
-// grouping and workspace layout of mkid_bank_filters and the launch geometry and workspace of
-// mkid_phase_thresholds. The host
+// grouping and workspace layout of mkid_bank_filters, the launch geometry and workspace of
+// mkid_phase_thresholds and the radix list, tables and index maps of mkid_phase_noise_spectra. The host
 // files mkid_api.hip, mkid_stream.hip and mkid_calib.hip are the only product callers.
 #pragma once
 #include <stdint.h>
@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "mkidgpu.h"
+#include "noise_common.h"
 
 namespace mkid {
 namespace plan {
@@ -123,6 +124,45 @@ struct ThrPlan {
 };
 // rows >= 1, 1 <= nch <= ld, ncu >= 1 (the entry point checks)
 ThrPlan plan_thresholds(int64_t rows, int64_t ld, int32_t nch, bool aligned16, int ncu);
+
+// mkid_phase_noise_spectra (k_noise.hip, noise_common.h): the transform of length n as in-place
+// decimation-in-frequency passes, one per radix. The radices are n's prime factors with the twos
+// taken in pairs (radix 4, then one 2 if their count is odd), in descending order: a large radix
+// runs while M = L / r is still large, so that the lanes of a wave share the output index t and
+// with it the radix-table entry they read. wn [n] is W_n^i and wr the passes' W_r^i tables one after
+// the other (Pass::tw_off), in float64; bin_of_pos[p] is the bin that position p holds after the
+// last pass and partner[p] the position of bin (n - bin_of_pos[p]) mod n. The device image of the
+// tables (noise_pack_tables) is wn and wr as float32 pairs, then the two index tables, at the byte
+// offsets below, `bytes` in all. A workgroup of `threads` threads takes a channel; every thread
+// holds per_thread positions in registers (an output and a float64 sum each), threads * per_thread
+// >= n: 256 x 16 up to n = 4096, 1024 x 16 above. lds_bytes: the piece as
+// float32 pairs, kNoiseStageR radix-table entries and four partial words per wave.
+constexpr int kNoiseThreadsSmall = 256, kNoisePerSmall = 16;
+constexpr int kNoiseThreadsLarge = 1024, kNoisePerLarge = 16;
+constexpr int kNoiseStageR = 1024;         // radix tables up to this length are staged in LDS
+constexpr int64_t kNoiseMaxGrid = 1 << 20;
+constexpr int64_t kNoiseXcdSpan = 256;     // the grid is a multiple of 8 XCDs x 32 channels of a 64-byte line
+struct NoisePlan {
+    int32_t n = 0;
+    std::vector<noise::Pass> passes;
+    std::vector<noise::Cx<double>> wn, wr;
+    std::vector<uint16_t> bin_of_pos, partner;
+    int32_t threads = 0, per_thread = 0;
+    int64_t lds_bytes = 0;
+    int64_t off_wn = 0, off_wr = 0, off_bin = 0, off_partner = 0, bytes = 0;
+};
+// 1 <= n <= MKID_NOISE_MAX_N (the entry point checks); false otherwise
+bool plan_noise(int32_t n, NoisePlan& p);
+// the device image of p's tables into out [p.bytes]
+void noise_pack_tables(const NoisePlan& p, char* out);
+// blocks the launch walks for nch channels (a multiple of kNoiseXcdSpan) and the channel of block
+// b: blocks b and b + 8 tend to share an XCD, so the 32 channels of a 64-byte line of the block go
+// to blocks 8 apart. A permutation of 0 .. blocks-1; channels >= nch are skipped. Speed only.
+inline int64_t noise_blocks(int64_t nch) { return (nch + kNoiseXcdSpan - 1) / kNoiseXcdSpan * kNoiseXcdSpan; }
+NOISE_HD int64_t noise_channel_of_block(int64_t b) {
+    const int64_t i = b >> 3, xcd = b & 7;
+    return (((i >> 5) << 3) + xcd) * 32 + (i & 31);
+}
 
 // k_front3 select-slot order (mkid_api.hip / include/mkidgpu.h mkid_slot_order): out[slot] = channel
 void slot_order(const std::vector<int32_t>& bins, int C, std::vector<int16_t>& out);

@@ -641,6 +641,32 @@ class RoachPulses:
         roach.cfg.dirty.add('thr')
         return loaded
 
+    def noiseSpectraBlock(self, rows=2 ** 20, n_averages=100, norm1=50.0, keep_raw=False):
+        """longsnapshot's phase-noise spectrum (ROACH_Pulses.py:521-543) for every channel < N_freqs
+        from ONE block of the running stream: one run(rows) and one device call on that block's
+        Fix16_13 rows (Channelizer.noise_spectra_of; codecs.noise_spectrum of each column in
+        degrees, in float32 arithmetic). longsnapshot stays as it is: one channel through the qdr
+        snapshot registers and the host FFT. Returns dict(noiseFFTFreqs [n], noiseFFT [N_freqs][n]),
+        n = rows // n_averages, plus raw (int16 [rows][N_freqs], the rows the spectra were made
+        from) with keep_raw."""
+        roach = self.roach
+        rows, nf = int(rows), int(self.N_freqs)
+        phase, _ = roach.run(rows)
+        ch = roach.channelizer()
+        d_raw, have = ch.raw_phase_ptr()
+        raw = None
+        if have == rows:      # the call was one piece: its Fix16_13 rows are still on the device
+            freqs, spec = ch.noise_spectra_of(d_raw, rows, ch.C, nf, n_averages, norm1)
+            if keep_raw:
+                raw = ch.raw_phase()[:, :nf].copy()
+        else:                 # run in pieces: the device's quantisation of the returned phase (_raw_of)
+            raw = np.clip(np.rint(phase[:, :nf] * np.float32(8192)), -25736, 25736).astype(np.int16)
+            freqs, spec = ch.noise_spectra(raw, n_averages, norm1)
+        out = dict(noiseFFTFreqs=freqs, noiseFFT=spec)
+        if keep_raw:
+            out['raw'] = raw
+        return out
+
     def _snap_qdr(self, ch, steps, L=2 ** 10, n_qdr=2 ** 19):
         """The snapshot loop shared by longsnapshot and contsnapshot (ROACH_Pulses.py:449-463,
         585-597): per step arm snapPhase + snapqdr, read 2^10 snapPhase words and 2^19 qdr0 words."""

@@ -10,6 +10,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <cmath>
 #include <random>
 #include <vector>
 
@@ -460,6 +461,105 @@ static void fuzz_thresholds(int iters) {
     }
 }
 
+// plan_noise (mkid_phase_noise_spectra): for random n and for 1, 2, 233, 10485, 16381 (prime) and
+// 16384 the radices multiply to n and the passes chain (L, M, stride, tw_off), the tables have the
+// planned sizes, bin_of_pos is a permutation with partner its reflection, the device image is
+// written into a buffer of exactly `bytes`, the launch geometry covers n and the channel order is a
+// permutation; then the host transform (noise_common.h pair_host, what the kernel does per pair of
+// pieces) runs on buffers of exactly n elements and a block of exactly the rows it may read, paired
+// and unpaired, and its bins are checked against a direct DFT at a few k. A length whose cost
+// n * (sum of radices) is large is replayed only when it is one of the listed ones.
+static void check_noise(int32_t n, bool replay) {
+    NoisePlan p;
+    CHECK(plan_noise(n, p), "no plan for n %d", n);
+    if (p.n != n) return;
+    int64_t prod = 1, sum = 0, L = n;
+    for (const mkid::noise::Pass& ps : p.passes) {
+        CHECK(ps.r >= 2 && ps.L == L && ps.M * ps.r == ps.L && ps.stride * ps.L == n && ps.tw_off == sum,
+              "pass r %d L %d M %d stride %d tw_off %d (n %d)", ps.r, ps.L, ps.M, ps.stride, ps.tw_off, n);
+        prod *= ps.r, sum += ps.r, L /= ps.r;
+    }
+    CHECK(prod == n && L == 1 && (int)p.passes.size() <= mkid::noise::kMaxPasses, "radices multiply to %lld, n %d",
+          (long long)prod, n);
+    CHECK((int64_t)p.wn.size() == n && (int64_t)p.wr.size() == sum && (int64_t)p.bin_of_pos.size() == n &&
+              (int64_t)p.partner.size() == n,
+          "table sizes (n %d)", n);
+    std::vector<int> seen((size_t)n, 0);
+    bool perm = true;
+    for (int32_t pos = 0; pos < n && perm; ++pos) perm = p.bin_of_pos[(size_t)pos] < n && !seen[p.bin_of_pos[(size_t)pos]]++;
+    CHECK(perm, "bin_of_pos is not a permutation (n %d)", n);
+    for (int32_t pos = 0; pos < n && perm; ++pos) {
+        const int32_t q = p.partner[(size_t)pos];
+        CHECK(q < n && (p.bin_of_pos[(size_t)pos] + p.bin_of_pos[(size_t)q]) % n == 0, "partner of position %d (n %d)", pos, n);
+    }
+    CHECK(p.off_wn == 0 && p.off_wr >= 8ll * n && p.off_bin >= p.off_wr + 8 * sum && p.off_partner >= p.off_bin + 2ll * n &&
+              p.bytes >= p.off_partner + 2ll * n && p.off_wr % 16 == 0 && p.off_bin % 16 == 0 && p.off_partner % 16 == 0,
+          "device image layout (n %d)", n);
+    std::vector<char> image((size_t)p.bytes);
+    noise_pack_tables(p, image.data());   // ASan: inside `bytes`
+    CHECK((int64_t)p.threads * p.per_thread >= n && (p.threads == kNoiseThreadsSmall || p.threads == kNoiseThreadsLarge) &&
+              p.lds_bytes == 8ll * n + 8ll * kNoiseStageR + 16ll * (p.threads / 64) && p.lds_bytes <= 160 * 1024,
+          "launch geometry (n %d)", n);
+    if (!replay) return;
+    const int64_t ld = rint_(1, 3), col = rint_(0, ld - 1);
+    for (int pieces = 1; pieces <= 2; ++pieces) {
+        std::vector<int16_t> raw((size_t)(((int64_t)pieces * n - 1) * ld + col + 1));   // the last row ends at the column
+        for (int16_t& v : raw) v = (int16_t)rint_(-25736, 25736);
+        std::vector<mkid::noise::Cx<double>> z((size_t)n), y((size_t)n);
+        std::vector<double> acc((size_t)n, 0.0);
+        const mkid::noise::View<double> v{n, (int32_t)p.passes.size(), p.passes.data(), p.wn.data(), p.wr.data(),
+                                          p.bin_of_pos.data(), p.partner.data()};
+        std::vector<double> pw((size_t)n * 2);
+        int calls = 0;
+        mkid::noise::pair_host<double>(v, raw.data() + col, pieces == 2 ? raw.data() + (int64_t)n * ld + col : nullptr, ld,
+                                       z.data(), y.data(), acc.data(), [&pw, &calls](double x) {
+                                           pw[(size_t)calls++] = x;   // |A[k]|^2 (, |B[k]|^2) in position order
+                                           return 0.0;
+                                       });
+        CHECK(calls == pieces * n, "%d powers for %d pieces of %d", calls, pieces, n);
+        for (int probe = 0; probe < 3; ++probe) {   // against the direct DFT
+            const int32_t pos = (int32_t)rint_(0, n - 1), k = p.bin_of_pos[(size_t)pos];
+            for (int w = 0; w < pieces; ++w) {
+                double re = 0, im = 0, tot = 0;
+                for (int32_t j = 0; j < n; ++j) {
+                    const double x = raw[(size_t)(((int64_t)w * n + j) * ld + col)];
+                    const mkid::noise::Cx<double> t = p.wn[(size_t)((int64_t)j * k % n)];
+                    re += x * t.re, im += x * t.im, tot += x * x;
+                }
+                const double got = pw[(size_t)(pos * pieces + w)], want = re * re + im * im;
+                CHECK(std::abs(got - want) <= 1e-9 * tot * n + 1e-9, "n %d bin %d piece %d: %g, direct %g", n, k, w, got, want);
+            }
+        }
+    }
+}
+
+static void fuzz_noise(int iters) {
+    const int32_t listed[] = {1, 2, 233, 10485, 16381, MKID_NOISE_MAX_N};
+    for (int32_t n : listed) check_noise(n, true);
+    NoisePlan none;
+    CHECK(!plan_noise(0, none) && !plan_noise(MKID_NOISE_MAX_N + 1, none) && !plan_noise(-5, none), "n out of range planned");
+    for (int it = 0; it < iters; ++it) {
+        const int32_t n = (int32_t)(rint_(0, 2) == 0 ? rint_(1, 300) : rint_(1, MKID_NOISE_MAX_N));
+        NoisePlan p;
+        int64_t cost = 0;
+        if (plan_noise(n, p))
+            for (const mkid::noise::Pass& ps : p.passes) cost += (int64_t)n * ps.r;
+        check_noise(n, cost <= 4000000);
+    }
+    // the order in which the blocks take the channels: a permutation of 0 .. blocks - 1
+    for (int64_t nch : {(int64_t)1, (int64_t)255, (int64_t)256, (int64_t)257, (int64_t)1024, rint_(1, 5000)}) {
+        const int64_t blocks = noise_blocks(nch);
+        CHECK(blocks >= nch && blocks % kNoiseXcdSpan == 0 && blocks - nch < kNoiseXcdSpan, "blocks for %lld channels", (long long)nch);
+        std::vector<int> seen((size_t)blocks, 0);
+        bool ok = true;
+        for (int64_t b = 0; b < blocks && ok; ++b) {
+            const int64_t c = noise_channel_of_block(b);
+            ok = c >= 0 && c < blocks && !seen[(size_t)c]++;
+        }
+        CHECK(ok, "channel order is not a permutation (%lld channels)", (long long)nch);
+    }
+}
+
 int main(int argc, char** argv) {
     const int iters = argc > 1 ? atoi(argv[1]) : 300;
     rng.seed(argc > 2 ? strtoull(argv[2], nullptr, 10) : 12345);
@@ -472,6 +572,7 @@ int main(int argc, char** argv) {
     fuzz_carry(iters);
     fuzz_bank(iters);
     fuzz_thresholds(iters / 2 + 1);
+    fuzz_noise(iters / 10 + 1);
     if (failures) {
         fprintf(stderr, "%d failures\n", failures);
         return 1;
