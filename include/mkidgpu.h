@@ -304,6 +304,66 @@ int mkid_pulse_heights(mkid_ctx* ctx, const float* d_phase, int64_t rows, int64_
 int mkid_pulse_heights_counted(mkid_ctx* ctx, const float* d_phase, int64_t rows, int64_t j0,
                                const uint64_t* d_events, const int64_t* d_count, int64_t cap,
                                float* d_heights);
+/* mkid_set_pulse_filter from a device table [nch = C][ncoeff] fp32, e.g. the d_coeff that
+ * mkid_bank_filters wrote: one device-to-device copy on the context stream (so it follows whatever
+ * that stream still has to write into the table), then one synchronisation, as the host form. The
+ * same checks, and it resets the same state: the rows carried for mkid_pulse_heights and for
+ * mkid_pulse_fit are forgotten. */
+int mkid_set_pulse_filter_device(mkid_ctx* ctx, const float* d_coeff, int32_t nch, int32_t ncoeff,
+                                 int32_t pre);
+
+/* Pulse height with a lag search and a sub-sample arrival time: the filter of mkid_set_pulse_filter
+ * applied at the 2 L + 1 alignments around the trigger's stamp, and the reference's peakfit
+ * (Utils/bin.py:12-16, the 3-point parabolic vertex) on the best of them. Per packet, with ch, ts
+ * and the unwrapped stamp jg exactly as for mkid_pulse_heights, r0 = jg - j0 - pre, search
+ * half-width L and polarity s:
+ *   lag values   H[d] = sum_{i < ncoeff} coeff[ch][i] * phase[r0 + d + i][ch],  d = -L .. L
+ *   chosen lag   d* = the lowest d that maximises s H[d]
+ *   edge         |d*| == L (always for L = 0): height = H[d*], dt = d*
+ *   interior     y1, y2, y3 = s H[d*-1], s H[d*], s H[d*+1]; a = y2 - y1, b = y2 - y3, c = a + b;
+ *                c == 0: height = H[d*], dt = d*; otherwise
+ *                height = s (y2 + (a - b)^2 / (8 c)),  dt = d* + (a - b) / (2 c)   (|dt - d*| <= 1/2)
+ *   outputs      d_heights [n] float; nullable d_dt [n] float (rows relative to the stamp: the
+ *                arrival is jg + dt), d_lag [n] int32 (d*), d_h0 [n] float (H[0], the value
+ *                mkid_pulse_heights gives)
+ *   outside      a packet whose rows r0 - L .. r0 + L + ncoeff - 1 are not all inside (carried rows,
+ *                rows), or whose ch >= C, gets NaN in every float output and INT32_MIN in d_lag
+ * mkid_set_pulse_fit: 0 <= search <= 31 and polarity +1 or -1 (MKID_E_ARG otherwise). The fit
+ * carries rows of its own, ncoeff + 2 search of them, apart from those of mkid_pulse_heights, which
+ * behaves exactly as without the fit; both calls may be given the same rows. The call forgets the
+ * fit's carried rows, and so does mkid_set_pulse_filter[_device], which also re-sizes them; the two
+ * setters may come in either order.
+ * mkid_pulse_fit: d_phase, rows, j0, d_events and n as for mkid_pulse_heights. When a call's j0
+ * continues the previous call's rows, windows that start before row j0 read the carried rows. The
+ * packets of a call's last (ncoeff - pre + L) rows come back NaN: pass them again with the next
+ * contiguous call, as for mkid_pulse_heights; the outputs of a call are otherwise final. Every H[d]
+ * is summed in an order that depends on ncoeff and L only, in fp32 with no atomics, and a carried
+ * row holds the float it was given: a packet's outputs are the same bits from run to run and
+ * whatever its place in the list, its neighbours, n, or the chunking of the stream into calls. A
+ * non-finite phase inside a packet's window leaves that packet's outputs unspecified and touches no
+ * other packet. Device pointers only; asynchronous on the context stream; no device-to-host copy
+ * and no synchronisation; rows == 0 and n == 0 are valid. The counted form reads min(*d_count, cap)
+ * packets and leaves the outputs of the others as they were. MKID_E_STATE when no filter is set or
+ * before mkid_set_pulse_fit; MKID_E_ARG on a null required pointer (d_phase when rows > 0, d_events
+ * and d_heights when n > 0, d_count) or a negative rows, j0 or n. Not timed (no MKID_K_ id).
+ * mkid_pulse_fit_host: the same rule on host memory through the same definitions
+ * (csrc/fit_common.h), H accumulated in float64; needs no device and no context. phase [rows][C]
+ * float32 are global rows j0 .. j0 + rows - 1, coeff [C][ncoeff] float32; there are no carried
+ * rows, so a window must lie inside the rows. Outputs float64 heights [n], nullable dt and h0 [n]
+ * and int32 lag [n]. MKID_E_ARG: a null coeff, a null phase with rows > 0, null events or heights
+ * with n > 0, negative rows, j0, n or pre, C outside 1..4096, ncoeff outside 1..4096, search outside
+ * 0..31, polarity not +1 or -1. */
+int mkid_set_pulse_fit(mkid_ctx* ctx, int32_t search, int32_t polarity);
+int mkid_pulse_fit(mkid_ctx* ctx, const float* d_phase, int64_t rows, int64_t j0,
+                   const uint64_t* d_events, int64_t n, float* d_heights, float* d_dt /* nullable */,
+                   int32_t* d_lag /* nullable */, float* d_h0 /* nullable */);
+int mkid_pulse_fit_counted(mkid_ctx* ctx, const float* d_phase, int64_t rows, int64_t j0,
+                           const uint64_t* d_events, const int64_t* d_count, int64_t cap,
+                           float* d_heights, float* d_dt, int32_t* d_lag, float* d_h0);
+int mkid_pulse_fit_host(const float* phase, int64_t rows, int32_t n_channels, int64_t j0,
+                        const uint64_t* events, int64_t n, const float* coeff, int32_t ncoeff,
+                        int32_t pre, int32_t search, int32_t polarity, double* heights,
+                        double* dt /* nullable */, int32_t* lag /* nullable */, double* h0 /* nullable */);
 
 /* Pulse capture: the firmware-style capture block between the stream and the template analysis.
  * For every photon packet the phase window around its stamp is copied into a caller-owned,

@@ -127,6 +127,11 @@ _SIGS = {
     'mkid_set_pulse_filter': [P, P, I32, I32, I32],
     'mkid_pulse_heights': [P, P, I64, I64, P, I64, P],
     'mkid_pulse_heights_counted': [P, P, I64, I64, P, P, I64, P],
+    'mkid_set_pulse_filter_device': [P, P, I32, I32, I32],
+    'mkid_set_pulse_fit': [P, I32, I32],
+    'mkid_pulse_fit': [P, P, I64, I64, P, I64, P, P, P, P],
+    'mkid_pulse_fit_counted': [P, P, I64, I64, P, P, I64, P, P, P, P],
+    'mkid_pulse_fit_host': [P, I64, I32, I64, P, I64, P, I32, I32, I32, I32, P, P, P, P],
     'mkid_set_capture': [P, I32, I32, I32],
     'mkid_capture_pulses': [P, P, I64, I64, P, I64, P, P, P],
     'mkid_capture_pulses_counted': [P, P, I64, I64, P, P, I64, P, P, P],

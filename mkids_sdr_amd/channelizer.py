@@ -346,6 +346,61 @@ class Channelizer:
         torch.cuda.synchronize(dev)
         return out.cpu().numpy()
 
+    # ---- pulse height with a lag search and a sub-sample arrival time (mkid_pulse_fit) -------------
+    def set_pulse_filter_device(self, d_coeff, pre, ncoeff=None):
+        """set_pulse_filter from a device table float32 [C][ncoeff], e.g. the coeff tensor of
+        template.bank_filters: a device-to-device copy, nothing passes through the host. ncoeff
+        defaults to the tensor's row length (give it with a raw pointer)."""
+        if hasattr(d_coeff, 'data_ptr'):
+            import torch
+            if d_coeff.dtype != torch.float32 or not d_coeff.is_contiguous() or d_coeff.numel() % self.C:
+                raise ValueError('d_coeff must be contiguous float32 [C][ncoeff]')
+            if ncoeff is None:
+                ncoeff = d_coeff.numel() // self.C
+            torch.cuda.synchronize(self.torch_device())   # the table may have been written on another stream
+        if ncoeff is None:
+            raise ValueError('ncoeff is needed with a raw pointer')
+        self._chk(self._L.mkid_set_pulse_filter_device(self._h, _ptr(d_coeff), self.C, int(ncoeff), int(pre)))
+
+    def set_pulse_fit(self, search=3, polarity=-1):
+        """Search half-width L (0..31 rows around the stamp) and polarity of pulse_fit. The lag that
+        maximises polarity * H is chosen. The default -1 follows template.matched_fir_taps' sign
+        convention: phase pulses are negative-going at the trigger and the filters of
+        template.optimal_filter / bank_filters respond positively to the (sign-flipped, positive)
+        template, so a photon gives a negative H and the fit looks for its minimum. Either order
+        with set_pulse_filter; forgets the fit's carried rows."""
+        self._chk(self._L.mkid_set_pulse_fit(self._h, int(search), int(polarity)))
+
+    def pulse_fit_device(self, d_phase, rows, j0, d_events, n, d_heights, d_dt=None, d_lag=None, d_h0=None):
+        """Device pointers; asynchronous on the context stream (include/mkidgpu.h mkid_pulse_fit).
+        d_dt, d_lag and d_h0 may be None."""
+        self._chk(self._L.mkid_pulse_fit(self._h, _ptr(d_phase), int(rows), int(j0), _ptr(d_events), int(n),
+                                         _ptr(d_heights), _ptr(d_dt), _ptr(d_lag), _ptr(d_h0)))
+
+    def pulse_fit_counted(self, d_phase, rows, j0, d_events, d_count, cap, d_heights, d_dt=None, d_lag=None,
+                          d_h0=None):
+        """As pulse_fit_device with the packet count read on the device (d_count: an int64 device
+        pointer/tensor, e.g. the d_counts[1:] of the process call)."""
+        self._chk(self._L.mkid_pulse_fit_counted(self._h, _ptr(d_phase), int(rows), int(j0), _ptr(d_events),
+                                                 _ptr(d_count), int(cap), _ptr(d_heights), _ptr(d_dt), _ptr(d_lag),
+                                                 _ptr(d_h0)))
+
+    def pulse_fit(self, phase, events, j0=0):
+        """Host convenience: phase float32 [rows][C] (rad) of global rows j0.., events uint64 [n] ->
+        (heights float32 [n], dt float32 [n], lag int32 [n], h0 float32 [n]); NaN / INT32_MIN where
+        the search window leaves the rows. The arrival of a packet is its unwrapped stamp + dt."""
+        import torch
+        dev = self.torch_device()
+        ph = torch.from_numpy(np.ascontiguousarray(phase, np.float32).reshape(-1, self.C)).to(dev)
+        ev = torch.from_numpy(np.ascontiguousarray(events, np.uint64).view(np.int64)).to(dev)
+        n = ev.numel()
+        h, dt, h0 = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(3))
+        lag = torch.empty(n, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)  # the uploads run on torch's stream, the kernel on the context's
+        self.pulse_fit_device(ph, ph.shape[0], j0, ev, n, h, dt, lag, h0)
+        torch.cuda.synchronize(dev)
+        return h.cpu().numpy(), dt.cpu().numpy(), lag.cpu().numpy(), h0.cpu().numpy()
+
     # ---- pulse capture: phase windows around the packets, into a per-channel record bank -----------
     def set_capture(self, length=2000, pre=1000, max_per_ch=256):
         """Records of `length` phase rows starting `pre` rows before each packet's stamp, at most

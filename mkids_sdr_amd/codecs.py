@@ -190,6 +190,29 @@ def phase_thresholds_host(raw, nsigma=2.5, nch=None, want_stats=False):
     return (thr, stats['med'].copy(), stats) if want_stats else (thr, stats['med'].copy())
 
 
+def pulse_fit_host(phase, events, coeff, pre, search=3, polarity=-1, j0=0):
+    """phase float32 [rows][C] (rad) of global rows j0.., events uint64 [n] wide packets, coeff
+    float32 [C][ncoeff] -> (heights float64 [n], dt float64 [n], lag int32 [n], h0 float64 [n])
+    through libmkidgpu's mkid_pulse_fit_host: the CPU statement, on float64 lag values, of the
+    device call mkid_pulse_fit (include/mkidgpu.h states the rule). There are no carried rows: NaN /
+    INT32_MIN where the search window is not inside the rows. No GPU is needed."""
+    import ctypes
+    from . import _lib
+    ph = np.ascontiguousarray(phase, np.float32)
+    cf = np.ascontiguousarray(coeff, np.float32)
+    if ph.ndim != 2 or cf.ndim != 2 or cf.shape[0] != ph.shape[1]:
+        raise ValueError('phase must be [rows][C] and coeff [C][ncoeff]')
+    ev = np.ascontiguousarray(events, np.uint64).reshape(-1)
+    n = ev.size
+    heights, dt, h0 = np.zeros(n), np.zeros(n), np.zeros(n)
+    lag = np.zeros(n, np.int32)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    _lib.check(_lib.load().mkid_pulse_fit_host(p(ph), ph.shape[0], ph.shape[1], int(j0), p(ev), n, p(cf),
+                                               cf.shape[1], int(pre), int(search), int(polarity), p(heights),
+                                               p(dt), p(lag), p(h0)))
+    return heights, dt, lag, h0
+
+
 # ---- snapshots ----------------------------------------------------------------------------------
 def encode_snap_phase(raw):
     """Fix16_13 samples -> snapPhase_bram bytes (2 per word, halves swapped: decode reads [2:4]

@@ -448,6 +448,7 @@ int mkid_reset_stream(mkid_ctx* c) {
     c->stream_kind = 0;
     c->last_J = 0;
     c->pcarry.drop();   // pulse-height phase history: a reset starts a new stream
+    c->fcarry.drop();   // and the pulse fit's
     c->ccarry.drop();   // pulse capture: the next call starts a segment (rows and pending list forgotten)
     return MKID_OK;
 }

@@ -1,10 +1,11 @@
 // C ABI of libmkidgpu.so (include/mkidgpu.h): calibration and pulse analysis — replay trigger,
-// template, optimal filter, bank filters, pulse heights, pulse capture, phase thresholds, phase-noise
+// template, optimal filter, bank filters, pulse heights, the pulse-height fit, pulse capture, phase thresholds, phase-noise
 // spectra, the synthetic ADC stream, stream copy.
 // Every entry point that replaces buffers of the context allocates the new ones into locals and
 // moves them in, with the scalars that describe them, only once every allocation has succeeded.
 #include <cmath>
 
+#include "fit_common.h"
 #include "mkid_ctx.h"
 #include "noise_common.h"
 #include "thr_common.h"
@@ -138,23 +139,40 @@ int mkid_bank_filters(mkid_ctx* c, const float* d_I, const float* d_Q, const int
     return MKID_OK;
 }
 
-int mkid_set_pulse_filter(mkid_ctx* c, const float* coeff, int32_t nch, int32_t ncoeff, int32_t pre) {
+// mkid_set_pulse_filter and mkid_set_pulse_filter_device: the table comes from host or device memory
+static int set_pulse_filter(mkid_ctx* c, const float* coeff, int32_t nch, int32_t ncoeff, int32_t pre,
+                            hipMemcpyKind kind) {
     if (!c || !coeff) return MKID_E_ARG;
     if (nch != c->C) FAIL(c, MKID_E_ARG, "pulse filter: need one filter per channel");
     if (ncoeff < 1 || ncoeff > 4096 || pre < 0) FAIL(c, MKID_E_ARG, "pulse filter: bad ncoeff/pre");
     HIPCHK(c, hipSetDevice(c->device));
     DevBuf<float> co;
-    RollBuf<float> hist;
+    RollBuf<float> hist, fhist;
+    const int64_t fit_rows = ncoeff + 2 * (int64_t)std::max(c->fit_L, 0);
     HIPCHK(c, co.alloc((size_t)nch * ncoeff));
     HIPCHK(c, hist.alloc(ncoeff, (int64_t)nch * 4));
-    // the upload drains the stream: no kernel still reads the filter and the rows replaced below
-    if (int r = upload(c, co.get(), coeff, (size_t)nch * ncoeff * 4)) return r;
+    if (c->fit_L >= 0) HIPCHK(c, fhist.alloc(fit_rows, (int64_t)nch * 4));
+    // the copy drains the stream: no kernel still reads the filter and the rows replaced below
+    HIPCHK(c, hipMemcpyAsync(co.get(), coeff, (size_t)nch * ncoeff * 4, kind, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     c->d_hcoeff = std::move(co);
     c->phist = std::move(hist);
     c->pcarry = plan::Carry{ncoeff};   // the rows carried for the old filter are forgotten
+    if (c->fit_L >= 0) {
+        c->fhist = std::move(fhist);
+        c->fcarry = plan::Carry{fit_rows};
+    }
     c->h_ncoeff = ncoeff;
     c->h_pre = pre;
     return MKID_OK;
+}
+
+int mkid_set_pulse_filter(mkid_ctx* c, const float* coeff, int32_t nch, int32_t ncoeff, int32_t pre) {
+    return set_pulse_filter(c, coeff, nch, ncoeff, pre, hipMemcpyHostToDevice);
+}
+
+int mkid_set_pulse_filter_device(mkid_ctx* c, const float* d_coeff, int32_t nch, int32_t ncoeff, int32_t pre) {
+    return set_pulse_filter(c, d_coeff, nch, ncoeff, pre, hipMemcpyDeviceToDevice);
 }
 
 static int pulse_heights(mkid_ctx* c, const float* d_phase, int64_t rows, int64_t j0, const uint64_t* d_events,
@@ -188,6 +206,91 @@ int mkid_pulse_heights_counted(mkid_ctx* c, const float* d_phase, int64_t rows, 
                                const uint64_t* d_events, const int64_t* d_count, int64_t cap, float* d_heights) {
     if (!d_count) return MKID_E_ARG;
     return pulse_heights(c, d_phase, rows, j0, d_events, d_count, cap, d_heights);
+}
+
+// ---- pulse heights with a lag search and a parabolic vertex (fit_common.h) ------------------------
+int mkid_set_pulse_fit(mkid_ctx* c, int32_t search, int32_t polarity) {
+    if (!c) return MKID_E_ARG;
+    if (!fit::params_ok(search, polarity)) FAIL(c, MKID_E_ARG, "pulse fit: need 0 <= search <= 31, polarity +1 or -1");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->h_ncoeff > 0) {   // else mkid_set_pulse_filter allocates the rows
+        const int64_t fit_rows = c->h_ncoeff + 2 * (int64_t)search;
+        RollBuf<float> fhist;
+        HIPCHK(c, fhist.alloc(fit_rows, (int64_t)c->C * 4));
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // an earlier fit may still read the old rows
+        c->fhist = std::move(fhist);
+        c->fcarry = plan::Carry{fit_rows};
+    }
+    c->fit_L = search;
+    c->fit_s = polarity;
+    return MKID_OK;
+}
+
+static int pulse_fit(mkid_ctx* c, const float* d_phase, int64_t rows, int64_t j0, const uint64_t* d_events,
+                     const int64_t* d_n, int64_t n, float* d_heights, float* d_dt, int32_t* d_lag, float* d_h0) {
+    if (!c || (rows > 0 && !d_phase) || (n > 0 && (!d_events || !d_heights))) return MKID_E_ARG;
+    if (rows < 0 || j0 < 0 || n < 0) FAIL(c, MKID_E_ARG, "pulse fit: negative rows/j0/n");
+    if (!c->d_hcoeff.get()) FAIL(c, MKID_E_STATE, "pulse fit: no filter set (mkid_set_pulse_filter)");
+    if (c->fit_L < 0) FAIL(c, MKID_E_STATE, "pulse fit: not configured (mkid_set_pulse_fit)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const plan::Carry& k = c->fcarry;
+    const plan::FitPlan p = plan::plan_fit(c->h_ncoeff, c->fit_L, c->ncu);
+    FitArgs a{};
+    a.phase = d_phase, a.hist = c->fhist.get() + k.offset(j0) * c->C, a.events = d_events;
+    a.coeff = c->d_hcoeff.get(), a.d_n = d_n;
+    a.heights = d_heights, a.dt = d_dt, a.lag = d_lag, a.h0 = d_h0;
+    a.rows = rows, a.j0 = j0, a.n = n, a.hrows = k.before(j0);
+    a.C = c->C, a.ncoeff = c->h_ncoeff, a.pre = c->h_pre, a.L = c->fit_L, a.s = c->fit_s;
+    HIPCHK(c, launch_pulse_fit(a, p, c->stream));
+    // keep the last rows of (carried rows, these rows) for the next call's early windows
+    if (rows > 0) {
+        HIPCHK(c, c->fhist.roll(d_phase, rows, c->stream));
+        c->fcarry.advance(j0, rows);
+    }
+    return MKID_OK;
+}
+
+int mkid_pulse_fit(mkid_ctx* c, const float* d_phase, int64_t rows, int64_t j0, const uint64_t* d_events, int64_t n,
+                   float* d_heights, float* d_dt, int32_t* d_lag, float* d_h0) {
+    return pulse_fit(c, d_phase, rows, j0, d_events, nullptr, n, d_heights, d_dt, d_lag, d_h0);
+}
+
+int mkid_pulse_fit_counted(mkid_ctx* c, const float* d_phase, int64_t rows, int64_t j0, const uint64_t* d_events,
+                           const int64_t* d_count, int64_t cap, float* d_heights, float* d_dt, int32_t* d_lag,
+                           float* d_h0) {
+    if (!d_count) return MKID_E_ARG;
+    return pulse_fit(c, d_phase, rows, j0, d_events, d_count, cap, d_heights, d_dt, d_lag, d_h0);
+}
+
+// The CPU statement of the device call: the same decode, window test and selection (fit_common.h)
+// on lag values accumulated in float64; no carried rows.
+int mkid_pulse_fit_host(const float* phase, int64_t rows, int32_t C, int64_t j0, const uint64_t* events, int64_t n,
+                        const float* coeff, int32_t ncoeff, int32_t pre, int32_t search, int32_t polarity,
+                        double* heights, double* dt, int32_t* lag, double* h0) {
+    if (!coeff || (rows > 0 && !phase) || (n > 0 && (!events || !heights))) return MKID_E_ARG;
+    if (rows < 0 || j0 < 0 || n < 0 || C < 1 || C > 4096 || ncoeff < 1 || ncoeff > fit::kMaxCoeff || pre < 0 ||
+        !fit::params_ok(search, polarity))
+        return MKID_E_ARG;
+    double H[2 * fit::kMaxSearch + 1];
+    for (int64_t p = 0; p < n; ++p) {
+        const fit::Stamp st = fit::decode(events[p], j0);
+        const int64_t r0 = st.jg - j0 - pre;
+        fit::Result<double> r{NAN, NAN, NAN, INT32_MIN};
+        if (fit::inside(st.ch, C, r0, search, ncoeff, 0, rows)) {
+            const float* cf = coeff + (size_t)st.ch * ncoeff;
+            for (int32_t d = -search; d <= search; ++d) {
+                double acc = 0.0;
+                for (int32_t i = 0; i < ncoeff; ++i) acc += (double)cf[i] * (double)phase[(r0 + d + i) * C + st.ch];
+                H[d + search] = acc;
+            }
+            r = fit::select<double>(H, search, polarity);
+        }
+        heights[p] = r.height;
+        if (dt) dt[p] = r.dt;
+        if (lag) lag[p] = r.lag;
+        if (h0) h0[p] = r.h0;
+    }
+    return MKID_OK;
 }
 
 int mkid_set_capture(mkid_ctx* c, int32_t length, int32_t pre, int32_t max_per_ch) {

@@ -179,6 +179,12 @@ struct mkid_ctx : CtxHandles {
     int32_t h_ncoeff = 0, h_pre = 0;
     RollBuf<float> phist;           // [h_ncoeff][C]
     mkid::plan::Carry pcarry;
+    // pulse fit (mkid_set_pulse_fit): the search, and carried rows of its own, so that
+    // mkid_pulse_heights and mkid_pulse_fit may be given the same rows; allocated once both the
+    // filter and the search are known
+    int32_t fit_L = -1, fit_s = -1;   // fit_L < 0: not configured
+    RollBuf<float> fhist;             // [h_ncoeff + 2 fit_L][C]
+    mkid::plan::Carry fcarry;
     // pulse capture (mkid_set_capture): carried phase rows and the double-buffered pending list
     int32_t cap_L = 0, cap_pre = 0, cap_R = 0, cap_PC = 0;   // cap_L = 0: not configured
     RollBuf<float> chist;                                    // [max(L - 1, pre + 1)][C]

@@ -168,6 +168,27 @@ struct HeightArgs {
     int32_t pad;
 };
 
+// mkid_pulse_fit (k_heights_fit.hip): HeightArgs' stream, packets, filter and carried rows, the
+// search and the four outputs; the LDS geometry comes from the call's plan (mkid_plan.h FitPlan)
+struct FitArgs {
+    const float* phase;      // [rows][C] rad, global phase rows j0 .. j0 + rows - 1
+    const float* hist;       // [hrows][C] carried rows j0 - hrows .. j0 - 1 (hrows = 0: none)
+    const uint64_t* events;  // [n] wide packets
+    const float* coeff;      // [C][ncoeff]
+    const int64_t* d_n;      // nullable: device packet count (min(*d_n, n) packets are processed)
+    float* heights;          // [n] fitted height (NaN: window outside the rows or unknown channel)
+    float* dt;               // [n] nullable: vertex position in rows relative to the stamp
+    int32_t* lag;            // [n] nullable: chosen lag (INT32_MIN where the height is NaN)
+    float* h0;               // [n] nullable: the value at lag 0
+    int64_t rows, j0, n, hrows;
+    int32_t C, ncoeff, pre, L, s;
+    int32_t W, nl, G, off_cf, off_part, off_h, wave_floats;
+};
+namespace plan {
+struct FitPlan;
+}
+hipError_t launch_pulse_fit(FitArgs a, const plan::FitPlan& p, hipStream_t s);
+
 // Pulse capture (k_capture.hip; the contract is in its header comment)
 struct CaptureArgs {
     const float* phase;      // [rows][C] rad, global phase rows j0 .. j0 + rows - 1

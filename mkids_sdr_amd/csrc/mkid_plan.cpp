@@ -200,6 +200,23 @@ void slot_order(const std::vector<int32_t>& bins, int C, std::vector<int16_t>& o
     }
 }
 
+// mkid_pulse_fit: the LDS region of one wave and how many a workgroup holds (mkid_plan.h)
+FitPlan plan_fit(int32_t ncoeff, int32_t L, int ncu) {
+    FitPlan p;
+    p.nl = 2 * L + 1;
+    p.G = 64 / p.nl;
+    p.W = ncoeff + 2 * L;
+    p.off_w = 0;
+    p.off_cf = p.W;
+    p.off_part = p.off_cf + ncoeff;
+    p.off_h = p.off_part + 64;
+    p.wave_floats = p.off_h + 64;
+    p.waves = (int32_t)std::max<int64_t>(1, std::min<int64_t>(kFitWaves, kFitLdsBytes / (4ll * p.wave_floats)));
+    p.lds_bytes = 4ll * p.wave_floats * p.waves;
+    p.grid_cap = std::max<int64_t>(1, (int64_t)std::max(ncu, 1) * 32 / p.waves);
+    return p;
+}
+
 // K1 taps as the device applies them (include/mkidgpu.h, mkid_set_pfb): h_q = rint(h 2^S) int16
 // with the largest S such that every point's four |h_q| sum to <= 65535 and every |h_q| <= 32767
 // (so the fused kernels' int16 dot products never overflow int32 on int16 samples).

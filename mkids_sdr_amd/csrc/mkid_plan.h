@@ -164,6 +164,25 @@ NOISE_HD int64_t noise_channel_of_block(int64_t b) {
     return (((i >> 5) << 3) + xcd) * 32 + (i & 31);
 }
 
+// mkid_pulse_fit (k_heights_fit.hip): one wave per packet, its LDS region of wave_floats floats
+// holding, at the float offsets below, the window's W = ncoeff + 2 L rows, the channel's ncoeff
+// coefficients, the wave's 64 partial sums and the nl = 2 L + 1 lag values. Lanes 0 .. G nl - 1 work,
+// G = 64 / nl: lane g nl + d adds the taps i = g, g + G, g + 2 G, ... of lag d - L, reading
+// coefficient i and window row i + d (<= ncoeff - 1 + 2 L = W - 1). A workgroup holds `waves`
+// regions, at most kFitWaves and as many as kFitLdsBytes hold; the grid is capped at eight waves per
+// SIMD of every compute unit and strides over the packets.
+constexpr int kFitWaves = 4;
+constexpr int64_t kFitLdsBytes = 64 * 1024;
+struct FitPlan {
+    int32_t W = 0, nl = 0, G = 0;
+    int32_t off_w = 0, off_cf = 0, off_part = 0, off_h = 0, wave_floats = 0;
+    int32_t waves = 0;
+    int64_t lds_bytes = 0, grid_cap = 0;
+    int64_t blocks(int64_t n) const { return std::min((n + waves - 1) / waves, grid_cap); }
+};
+// 1 <= ncoeff <= 4096, 0 <= L <= 31, ncu >= 1 (the entry points check)
+FitPlan plan_fit(int32_t ncoeff, int32_t L, int ncu);
+
 // k_front3 select-slot order (mkid_api.hip / include/mkidgpu.h mkid_slot_order): out[slot] = channel
 void slot_order(const std::vector<int32_t>& bins, int C, std::vector<int16_t>& out);
 

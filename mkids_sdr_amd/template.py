@@ -158,16 +158,21 @@ def bank_filters(ch, I, Q, ready, *, pre=100, ncoeff=100, min_records=20, fallba
     return out
 
 
-def filters_from_bank_device(ch, bank, ncoeff=100, pre=100, min_records=20, fallback=None, keep_templates=False):
+def filters_from_bank_device(ch, bank, ncoeff=100, pre=100, min_records=20, fallback=None, keep_templates=False,
+                             load=False):
     """`filters_from_bank` in one device call: the bank's phase records go through
     mkid_bank_filters in phase mode where they lie (ready read from the bank's info, no per-channel
     host step), then the small outputs are copied once. Same arguments, same dict, plus status [C]
-    int32 (mkid_bank_result.status; used = status == 0)."""
+    int32 (mkid_bank_result.status; used = status == 0). load=True also makes the table the
+    context's pulse filter where it lies (Channelizer.set_pulse_filter_device with pre = 10, the
+    rows the weights start before the template peak): it does not leave the device for that."""
     records, _, info = bank
     if records.shape[2] != NPTS:
         raise ValueError('filters_from_bank_device needs records of %d rows (set_capture(length=%d))' % (NPTS, NPTS))
     r = bank_filters(ch, records, None, info, pre=pre, ncoeff=ncoeff, min_records=min_records, fallback=fallback,
                      keep_templates=keep_templates, sign=-1.0)
+    if load:
+        ch.set_pulse_filter_device(r['coeff'], pre=10)
     t = result_table(r['result'])
     used = t['status'] == 0
     out = dict(coeff=r['coeff'].cpu().numpy(), count=t['count'].copy(), flag=t['flag'].copy(),

@@ -14,6 +14,7 @@
 #include <random>
 #include <vector>
 
+#include "fit_common.h"
 #include "mkid_plan.h"
 
 extern "C" {
@@ -560,6 +561,83 @@ static void fuzz_noise(int iters) {
     }
 }
 
+// plan_fit (mkid_pulse_fit): for random and for boundary (ncoeff, L) the wave's LDS region is laid
+// out without overlap, a workgroup's regions stay inside the static 64 KiB, and the kernel's maps,
+// replayed as k_heights_fit.hip runs them into a buffer of exactly one wave's region, stay inside
+// their tables: the staging writes touch every window row and coefficient once, every (tap, lag)
+// pair is read by exactly one lane at window index tap + lag <= W - 1, the partial sums fill 64
+// slots of which the sum pass reads G per lag, and fit::select on the nl lag values reads only those
+// and returns a lag in -L .. L with |dt - lag| <= 1/2.
+static void check_fit(int32_t ncoeff, int32_t L, int ncu) {
+    const FitPlan p = plan_fit(ncoeff, L, ncu);
+    CHECK(p.nl == 2 * L + 1 && p.G == 64 / p.nl && p.G >= 1 && p.G * p.nl <= 64 && p.W == ncoeff + 2 * L,
+          "fit geometry (ncoeff %d, L %d)", ncoeff, L);
+    CHECK(p.off_w == 0 && p.off_cf == p.off_w + p.W && p.off_part == p.off_cf + ncoeff && p.off_h == p.off_part + 64 &&
+              p.wave_floats == p.off_h + 64,
+          "fit region layout (ncoeff %d, L %d)", ncoeff, L);
+    CHECK(p.waves >= 1 && p.waves <= kFitWaves && p.lds_bytes == 4ll * p.wave_floats * p.waves &&
+              p.lds_bytes <= kFitLdsBytes && (p.waves == kFitWaves || 4ll * p.wave_floats * (p.waves + 1) > kFitLdsBytes),
+          "fit workgroup: %d waves, %lld bytes (ncoeff %d, L %d)", p.waves, (long long)p.lds_bytes, ncoeff, L);
+    CHECK(p.grid_cap >= 1 && p.blocks(1) == 1 && p.blocks(1ll << 40) == p.grid_cap &&
+              p.blocks(p.waves + 1) == std::min<int64_t>(2, p.grid_cap),
+          "fit grid (ncu %d)", ncu);
+    std::vector<float> region((size_t)p.wave_floats, 0.f);   // ASan: every index below is inside it
+    float* w = region.data() + p.off_w;
+    float* cf = region.data() + p.off_cf;
+    float* part = region.data() + p.off_part;
+    float* hv = region.data() + p.off_h;
+    for (int lane = 0; lane < 64; ++lane) {
+        for (int i = lane; i < p.W; i += 64) w[i] += 1.f;
+        for (int i = lane; i < ncoeff; i += 64) cf[i] += 1.f;
+    }
+    bool once = true;
+    for (int i = 0; i < p.W; ++i) once = once && w[i] == 1.f;
+    for (int i = 0; i < ncoeff; ++i) once = once && cf[i] == 1.f;
+    CHECK(once, "staging does not fill the region once (ncoeff %d, L %d)", ncoeff, L);
+    std::vector<int32_t> seen((size_t)ncoeff * p.nl, 0);
+    for (int lane = 0; lane < 64; ++lane) {
+        const int g = lane / p.nl, d = lane - g * p.nl;
+        float acc = 0.f;
+        if (g < p.G)
+            for (int i = g; i < ncoeff; i += p.G) {
+                acc += cf[i] * w[i + d];
+                ++seen[(size_t)i * p.nl + d];
+            }
+        part[lane] = acc;
+    }
+    CHECK(std::all_of(seen.begin(), seen.end(), [](int32_t n) { return n == 1; }), "taps x lags not covered once (ncoeff %d, L %d)",
+          ncoeff, L);
+    for (int lane = 0; lane < p.nl; ++lane) {
+        float h = part[lane];
+        for (int k = 1; k < p.G; ++k) h += part[k * p.nl + lane];
+        hv[lane] = h;
+        CHECK(h == (float)ncoeff, "lag %d sums %g of %d products", lane - L, h, ncoeff);
+    }
+    for (int lane = 0; lane < p.nl; ++lane) hv[lane] = (float)rint_(-3, 3);
+    for (int s = -1; s <= 1; s += 2) {
+        const mkid::fit::Result<float> r = mkid::fit::select<float>(hv, L, s);
+        CHECK(r.lag >= -L && r.lag <= L && std::abs(r.dt - (float)r.lag) <= 0.5f && r.h0 == hv[L] &&
+                  (float)s * r.height >= (float)s * hv[r.lag + L],
+              "select: lag %d dt %g (L %d)", r.lag, r.dt, L);
+        for (int d = 0; d < p.nl; ++d)
+            CHECK((float)s * hv[d] < (float)s * hv[r.lag + L] || (d >= r.lag + L && hv[d] == hv[r.lag + L]),
+                  "select: lag %d is not the lowest maximum (L %d)", r.lag, L);
+    }
+}
+
+static void fuzz_fit(int iters) {
+    for (int32_t L : {0, 1, 2, 3, 8, 10, 15, 16, 21, 31})
+        for (int32_t ncoeff : {1, 2, 63, 64, 65, 100, 800, 4095, 4096}) check_fit(ncoeff, L, 256);
+    for (int it = 0; it < iters; ++it)
+        check_fit((int32_t)(rint_(0, 1) ? rint_(1, 300) : rint_(1, mkid::fit::kMaxCoeff)), (int32_t)rint_(0, mkid::fit::kMaxSearch),
+                  (int)rint_(1, 512));
+    mkid::fit::Stamp st = mkid::fit::decode(((uint64_t)5 << MKID_PKT_CH_SHIFT) | 3, ((int64_t)1 << 28) + 1);
+    CHECK(st.ch == 5 && st.jg == ((int64_t)1 << 28) + 3, "decode: channel %d stamp %lld", st.ch, (long long)st.jg);
+    CHECK(mkid::fit::inside(0, 1, -3, 3, 10, 6, 10) && !mkid::fit::inside(0, 1, -4, 3, 10, 6, 10) &&
+              !mkid::fit::inside(0, 1, -2, 3, 10, 6, 10) && !mkid::fit::inside(1, 1, -3, 3, 10, 6, 10),
+          "window test");
+}
+
 int main(int argc, char** argv) {
     const int iters = argc > 1 ? atoi(argv[1]) : 300;
     rng.seed(argc > 2 ? strtoull(argv[2], nullptr, 10) : 12345);
@@ -573,6 +651,7 @@ int main(int argc, char** argv) {
     fuzz_bank(iters);
     fuzz_thresholds(iters / 2 + 1);
     fuzz_noise(iters / 10 + 1);
+    fuzz_fit(iters);
     if (failures) {
         fprintf(stderr, "%d failures\n", failures);
         return 1;
