@@ -365,6 +365,82 @@ int mkid_pulse_fit_host(const float* phase, int64_t rows, int32_t n_channels, in
                         int32_t pre, int32_t search, int32_t polarity, double* heights,
                         double* dt /* nullable */, int32_t* lag /* nullable */, double* h0 /* nullable */);
 
+/* The observing products after the heights: the per-second count image that the reference's
+ * PacketMaster keeps as photon_counts[sec][pixel] (PacketMaster.c:371-381; the dashboard's quick-look
+ * image), the per-channel pulse-height spectra, and the two list operations that keep the deferral
+ * protocol of mkid_pulse_heights / mkid_pulse_fit on the device. All results are integers: they do
+ * not depend on the order of the list, on the chunking of a stream into calls, or on the run. The
+ * rules have one definition, csrc/obs_common.h. Per packet, ch and the unwrapped stamp jg are
+ * exactly those of mkid_pulse_heights (base = max(j0 - 2^27, 0), jg = base + ((ts - base) mod 2^28)).
+ *
+ * mkid_count_photons: sec = (jg fft_len) / sample_rate in int64 integer division (the context's
+ * configuration; phase row j is ADC sample j fft_len, and the first sample after a reset is a PPS
+ * edge). image[sec][ch] += 1 for every packet with ch < C and sec < n_seconds; d_image is
+ * [n_seconds][C] int32, caller-owned, zeroed by the caller to start an observation and continued
+ * otherwise. d_outside int64[2], caller-owned likewise: [0] += packets with ch >= C (PacketMaster's
+ * "photon from non-pixel"), [1] += packets with ch < C and sec >= n_seconds (PacketMaster ignores
+ * seconds at or beyond exptime). Each packet is passed once, with the call that produced it (j0 =
+ * that call's first global row). Correct for a list in any order; built for the device's order
+ * (channel-major, time-ascending in a channel), where a cell's packets are one run and cost two
+ * atomics together. MKID_E_ARG before any launch: a null d_image or d_outside, a null d_events with
+ * n > 0, a null d_count, a negative n, cap or j0 (or one so large that jg fft_len leaves int64),
+ * n_seconds outside 1 .. 2^20, a sample_rate that is not a positive integer below 2^53.
+ *
+ * mkid_height_spectra: spectra[ch][column] += 1 for every packet with ch < C; d_spectra is
+ * [C][nbins + 3] int32, caller-owned as the image. The column of height h in channel ch, with the
+ * device tables d_lo [C] and d_inv [C] (float32: lower edge of the first bin, 1 / bin width):
+ *     t = h - lo[ch], u = t * inv[ch], each rounded once in fp32
+ *     h not finite, or u NaN   -> nbins + 2  (no height)
+ *     u < 0                    -> 0          (under)
+ *     u >= (float)nbins        -> nbins + 1  (over)
+ *     otherwise                -> 1 + (int)u
+ * so -0.0 lands in column 1, and any lo / inv gives defined columns. Except a packet that is
+ * deferred: d_deferred != NULL, its height is not finite and jg >= j_defer (the first stamp whose
+ * window passes the call's last row: j0 + rows + pre - ncoeff - search + 1). Such a packet is
+ * appended to d_deferred instead, in list order, at index d_ndef[1]; d_ndef int64[2], caller-owned:
+ * [0] += packets that qualified, [1] += packets written (it stops at cap_def). Packets with ch >= C
+ * touch nothing. So every packet with ch < C ends in exactly one column or in the deferred list.
+ * MKID_E_ARG before any launch: a null d_lo, d_inv or d_spectra, null d_events or d_heights with
+ * n > 0, a null d_count, a negative n, cap, j0 or cap_def, nbins outside 1 .. 16384, d_deferred
+ * without d_ndef.
+ *
+ * mkid_concat_packets: d_out = the first min(*d_na, cap_a) words of d_a, then the first
+ * min(*d_nb, cap_b) of d_b, cut at cap_out; d_nout int64[2] = {produced, written}. d_out overlaps
+ * neither input; a list of capacity 0 may be NULL. MKID_E_ARG: a null count pointer, a negative
+ * capacity, a null list with a capacity. A streamed step is then: count the call's packets; join
+ * (deferred of the last step, the call's packets); one mkid_pulse_heights_counted or
+ * mkid_pulse_fit_counted over the joined list; mkid_height_spectra_counted over it into the other
+ * deferred list.
+ *
+ * Common to the five device calls: device pointers only; asynchronous on the context stream; no
+ * device-to-host copy, and no synchronisation (mkid_height_spectra allocates two small tables on its
+ * first call with d_deferred); n == 0 is valid; the counted forms read min(*d_count, cap) packets.
+ * Not timed (no MKID_K_ id).
+ * mkid_count_photons_host / mkid_height_spectra_host: the same rules on host memory through the
+ * same definitions; no device, no context. The same MKID_E_ARG cases, and n_channels outside
+ * 1 .. 4096 or fft_len < 1. */
+int mkid_count_photons(mkid_ctx* ctx, const uint64_t* d_events, int64_t n, int64_t j0, int32_t n_seconds,
+                       int32_t* d_image, int64_t* d_outside);
+int mkid_count_photons_counted(mkid_ctx* ctx, const uint64_t* d_events, const int64_t* d_count, int64_t cap,
+                               int64_t j0, int32_t n_seconds, int32_t* d_image, int64_t* d_outside);
+int mkid_height_spectra(mkid_ctx* ctx, const uint64_t* d_events, const float* d_heights, int64_t n, int64_t j0,
+                        int64_t j_defer, const float* d_lo, const float* d_inv, int32_t nbins,
+                        int32_t* d_spectra, uint64_t* d_deferred /* nullable */, int64_t cap_def,
+                        int64_t* d_ndef /* nullable with d_deferred */);
+int mkid_height_spectra_counted(mkid_ctx* ctx, const uint64_t* d_events, const float* d_heights,
+                                const int64_t* d_count, int64_t cap, int64_t j0, int64_t j_defer,
+                                const float* d_lo, const float* d_inv, int32_t nbins, int32_t* d_spectra,
+                                uint64_t* d_deferred, int64_t cap_def, int64_t* d_ndef);
+int mkid_concat_packets(mkid_ctx* ctx, const uint64_t* d_a, const int64_t* d_na, int64_t cap_a,
+                        const uint64_t* d_b, const int64_t* d_nb, int64_t cap_b, uint64_t* d_out,
+                        int64_t cap_out, int64_t* d_nout);
+int mkid_count_photons_host(const uint64_t* events, int64_t n, int64_t j0, int32_t fft_len, double sample_rate,
+                            int32_t n_channels, int32_t n_seconds, int32_t* image, int64_t* outside);
+int mkid_height_spectra_host(const uint64_t* events, const float* heights, int64_t n, int64_t j0,
+                             int64_t j_defer, int32_t n_channels, const float* lo, const float* inv,
+                             int32_t nbins, int32_t* spectra, uint64_t* deferred /* nullable */,
+                             int64_t cap_def, int64_t* ndef /* nullable with deferred */);
+
 /* Pulse capture: the firmware-style capture block between the stream and the template analysis.
  * For every photon packet the phase window around its stamp is copied into a caller-owned,
  * per-channel record bank on the device, for all channels at once and across streamed calls (the

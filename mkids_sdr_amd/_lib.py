@@ -132,6 +132,13 @@ _SIGS = {
     'mkid_pulse_fit': [P, P, I64, I64, P, I64, P, P, P, P],
     'mkid_pulse_fit_counted': [P, P, I64, I64, P, P, I64, P, P, P, P],
     'mkid_pulse_fit_host': [P, I64, I32, I64, P, I64, P, I32, I32, I32, I32, P, P, P, P],
+    'mkid_count_photons': [P, P, I64, I64, I32, P, P],
+    'mkid_count_photons_counted': [P, P, P, I64, I64, I32, P, P],
+    'mkid_height_spectra': [P, P, P, I64, I64, I64, P, P, I32, P, P, I64, P],
+    'mkid_height_spectra_counted': [P, P, P, P, I64, I64, I64, P, P, I32, P, P, I64, P],
+    'mkid_concat_packets': [P, P, P, I64, P, P, I64, P, I64, P],
+    'mkid_count_photons_host': [P, I64, I64, I32, ctypes.c_double, I32, I32, P, P],
+    'mkid_height_spectra_host': [P, P, I64, I64, I64, I32, P, P, I32, P, P, I64, P],
     'mkid_set_capture': [P, I32, I32, I32],
     'mkid_capture_pulses': [P, P, I64, I64, P, I64, P, P, P],
     'mkid_capture_pulses_counted': [P, P, I64, I64, P, P, I64, P, P, P],

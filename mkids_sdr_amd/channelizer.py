@@ -45,6 +45,8 @@ class Channelizer:
         self.C = cfg.n_channels
         self.N = cfg.fft_len
         self.P = cfg.dds_entries
+        self.pulse_filter = None       # (ncoeff, pre) once a pulse filter is set
+        self.pulse_fit_search = None   # search half-width once set_pulse_fit ran
         self.set_pfb(pfb_prototype(self.N, cfg.pfb_taps))
 
     # ---- lifecycle -------------------------------------------------------------------------
@@ -321,6 +323,7 @@ class Channelizer:
         tiled); the height of a packet stamped ts is sum_i coeff[ch][i] phase[ts - pre + i][ch]."""
         cf = np.ascontiguousarray(coeff, np.float32).reshape(self.C, -1)
         self._chk(self._L.mkid_set_pulse_filter(self._h, _ptr(cf), cf.shape[0], cf.shape[1], int(pre)))
+        self.pulse_filter = (int(cf.shape[1]), int(pre))   # (ncoeff, pre), for observe.Observation
 
     def pulse_heights_device(self, d_phase, rows, j0, d_events, n, d_heights):
         """Device pointers; asynchronous on the context stream (include/mkidgpu.h)."""
@@ -361,6 +364,7 @@ class Channelizer:
         if ncoeff is None:
             raise ValueError('ncoeff is needed with a raw pointer')
         self._chk(self._L.mkid_set_pulse_filter_device(self._h, _ptr(d_coeff), self.C, int(ncoeff), int(pre)))
+        self.pulse_filter = (int(ncoeff), int(pre))
 
     def set_pulse_fit(self, search=3, polarity=-1):
         """Search half-width L (0..31 rows around the stamp) and polarity of pulse_fit. The lag that
@@ -370,6 +374,7 @@ class Channelizer:
         template, so a photon gives a negative H and the fit looks for its minimum. Either order
         with set_pulse_filter; forgets the fit's carried rows."""
         self._chk(self._L.mkid_set_pulse_fit(self._h, int(search), int(polarity)))
+        self.pulse_fit_search = int(search)
 
     def pulse_fit_device(self, d_phase, rows, j0, d_events, n, d_heights, d_dt=None, d_lag=None, d_h0=None):
         """Device pointers; asynchronous on the context stream (include/mkidgpu.h mkid_pulse_fit).
@@ -400,6 +405,80 @@ class Channelizer:
         self.pulse_fit_device(ph, ph.shape[0], j0, ev, n, h, dt, lag, h0)
         torch.cuda.synchronize(dev)
         return h.cpu().numpy(), dt.cpu().numpy(), lag.cpu().numpy(), h0.cpu().numpy()
+
+    # ---- count image and pulse-height spectra (mkid_count_photons, mkid_height_spectra) -----------
+    def count_photons_device(self, d_events, n, j0, n_seconds, d_image, d_outside):
+        """Device pointers; asynchronous on the context stream (include/mkidgpu.h mkid_count_photons):
+        d_image int32 [n_seconds][C] and d_outside int64 [2] are added to."""
+        self._chk(self._L.mkid_count_photons(self._h, _ptr(d_events), int(n), int(j0), int(n_seconds),
+                                             _ptr(d_image), _ptr(d_outside)))
+
+    def count_photons_counted(self, d_events, d_count, cap, j0, n_seconds, d_image, d_outside):
+        """As count_photons_device with the packet count read on the device."""
+        self._chk(self._L.mkid_count_photons_counted(self._h, _ptr(d_events), _ptr(d_count), int(cap), int(j0),
+                                                     int(n_seconds), _ptr(d_image), _ptr(d_outside)))
+
+    def height_spectra_device(self, d_events, d_heights, n, j0, j_defer, d_lo, d_inv, nbins, d_spectra,
+                              d_deferred=None, cap_def=0, d_ndef=None):
+        """Device pointers; asynchronous on the context stream (include/mkidgpu.h mkid_height_spectra):
+        d_spectra int32 [C][nbins + 3] is added to; with d_deferred, the packets that still wait for
+        their height are appended there and counted in d_ndef int64 [2]."""
+        self._chk(self._L.mkid_height_spectra(self._h, _ptr(d_events), _ptr(d_heights), int(n), int(j0), int(j_defer),
+                                              _ptr(d_lo), _ptr(d_inv), int(nbins), _ptr(d_spectra), _ptr(d_deferred),
+                                              int(cap_def), _ptr(d_ndef)))
+
+    def height_spectra_counted(self, d_events, d_heights, d_count, cap, j0, j_defer, d_lo, d_inv, nbins, d_spectra,
+                               d_deferred=None, cap_def=0, d_ndef=None):
+        """As height_spectra_device with the packet count read on the device."""
+        self._chk(self._L.mkid_height_spectra_counted(self._h, _ptr(d_events), _ptr(d_heights), _ptr(d_count), int(cap),
+                                                      int(j0), int(j_defer), _ptr(d_lo), _ptr(d_inv), int(nbins),
+                                                      _ptr(d_spectra), _ptr(d_deferred), int(cap_def), _ptr(d_ndef)))
+
+    def concat_packets(self, d_a, d_na, cap_a, d_b, d_nb, cap_b, d_out, cap_out, d_nout):
+        """d_out = the first min(*d_na, cap_a) packets of d_a, then the first min(*d_nb, cap_b) of d_b,
+        cut at cap_out; d_nout int64 [2] = {produced, written}. Both counts are read on the device."""
+        self._chk(self._L.mkid_concat_packets(self._h, _ptr(d_a), _ptr(d_na), int(cap_a), _ptr(d_b), _ptr(d_nb),
+                                              int(cap_b), _ptr(d_out), int(cap_out), _ptr(d_nout)))
+
+    def count_photons(self, events, j0, n_seconds):
+        """Host convenience: events uint64 [n] of the call whose first global row is j0 ->
+        (image int32 [n_seconds][C], outside int64 [2])."""
+        import torch
+        dev = self.torch_device()
+        ev = torch.from_numpy(np.ascontiguousarray(events, np.uint64).view(np.int64)).to(dev)
+        image = torch.zeros((int(n_seconds), self.C), dtype=torch.int32, device=dev)
+        outside = torch.zeros(2, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(dev)  # the uploads run on torch's stream, the kernel on the context's
+        self.count_photons_device(ev if ev.numel() else None, ev.numel(), j0, n_seconds, image, outside)
+        torch.cuda.synchronize(dev)
+        return image.cpu().numpy(), outside.cpu().numpy()
+
+    def height_spectra(self, events, heights, lo, step, nbins, j0=0, j_defer=None, cap_def=0):
+        """Host convenience: events uint64 [n] and their heights float32 [n]; lo and step scalars or
+        [C] (bin b of channel c is [lo[c] + b step[c], lo[c] + (b + 1) step[c]) up to fp32 rounding;
+        the rule is include/mkidgpu.h's, with inv = float32(1) / float32(step)) -> spectra int32
+        [C][nbins + 3]. With j_defer also (deferred uint64 [written], ndef int64 [2])."""
+        import torch
+        dev = self.torch_device()
+        ev = torch.from_numpy(np.ascontiguousarray(events, np.uint64).view(np.int64)).to(dev)
+        h = torch.from_numpy(np.ascontiguousarray(heights, np.float32)).to(dev)
+        lo32 = np.ascontiguousarray(np.broadcast_to(np.asarray(lo, np.float32), (self.C,)))
+        with np.errstate(divide='ignore', invalid='ignore'):
+            inv32 = np.ascontiguousarray(np.broadcast_to(np.float32(1) / np.asarray(step, np.float32), (self.C,)))
+        d_lo, d_inv = torch.from_numpy(lo32).to(dev), torch.from_numpy(inv32).to(dev)
+        spectra = torch.zeros((self.C, int(nbins) + 3), dtype=torch.int32, device=dev)
+        defer = j_defer is not None
+        d_def = torch.zeros(max(int(cap_def), 1), dtype=torch.int64, device=dev) if defer else None
+        d_ndef = torch.zeros(2, dtype=torch.int64, device=dev) if defer else None
+        torch.cuda.synchronize(dev)  # the uploads run on torch's stream, the kernels on the context's
+        n = ev.numel()
+        self.height_spectra_device(ev if n else None, h if n else None, n, j0, j_defer if defer else 0, d_lo, d_inv,
+                                   nbins, spectra, d_def, cap_def, d_ndef)
+        torch.cuda.synchronize(dev)
+        if not defer:
+            return spectra.cpu().numpy()
+        ndef = d_ndef.cpu().numpy()
+        return spectra.cpu().numpy(), d_def[:int(ndef[1])].cpu().numpy().view(np.uint64), ndef
 
     # ---- pulse capture: phase windows around the packets, into a per-channel record bank -----------
     def set_capture(self, length=2000, pre=1000, max_per_ch=256):

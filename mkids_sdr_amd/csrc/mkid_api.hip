@@ -133,6 +133,7 @@ int mkid_create(const mkid_cfg* cfg, int32_t device, mkid_ctx** out) {
         const char* so = getenv("MKID_SLOT_ORDER");
         c->slot_order_on = !(so && atoi(so) == 0);
         if (const char* fl = getenv("MKID_FAULT_LAUNCH")) c->fault_launch = atoll(fl);
+        if (const char* ol = getenv("MKID_OBS_LDS")) c->obs_lds = atoi(ol) != 0;
     }
     int64_t trig_slots = trigger_wave_slots(device);
     // tuning/test knob: pretend the GPU holds this many trigger waves (forces longer segments)

@@ -1,5 +1,5 @@
 // The context behind the C ABI and what owns its device memory; private to the host translation
-// units of libmkidgpu.so (mkid_api.hip, mkid_stream.hip, mkid_calib.hip).
+// units of libmkidgpu.so (mkid_api.hip, mkid_stream.hip, mkid_calib.hip, mkid_observe.hip).
 #pragma once
 #include <algorithm>
 #include <string>
@@ -217,6 +217,13 @@ struct mkid_ctx : CtxHandles {
     // plan::noise_pack_tables lays them out; noise_plan keeps the passes and offsets only)
     DevBuf<char> d_noisetab;
     mkid::plan::NoisePlan noise_plan;
+    // mkid_height_spectra: per-workgroup deferred counts and offsets (lazy; their size is fixed,
+    // mkid_internal.h kObsMaxBlocks), and the form of the spectra kernel: the plain one (one global
+    // atomic per packet) unless MKID_OBS_LDS=1 at mkid_create asks for the LDS table, which the
+    // same-process A/B of tools/observe_rate.py did not find clear of it
+    DevBuf<int32_t> d_obs_count;
+    DevBuf<int64_t> d_obs_off;
+    bool obs_lds = false;
     // host-API staging (lazy)
     DevBuf<uint32_t> d_in;
     DevBuf<float> d_phase_ws;

@@ -189,6 +189,50 @@ struct FitPlan;
 }
 hipError_t launch_pulse_fit(FitArgs a, const plan::FitPlan& p, hipStream_t s);
 
+// mkid_count_photons (k_observe.hip): the count image and the two `outside` counters
+struct ObsCountArgs {
+    const uint64_t* events;  // [n] wide packets
+    const int64_t* d_n;      // nullable: device packet count (min(*d_n, n) packets are read)
+    int32_t* image;          // [n_seconds][C]
+    int64_t* outside;        // [2]
+    int64_t n, j0, N, fs;    // fs: samples per second (an integer, obs_common.h fs_ok)
+    int32_t C, n_seconds, ncu, pad;
+};
+hipError_t launch_count_photons(const ObsCountArgs& a, hipStream_t s);
+
+// mkid_height_spectra (k_observe.hip). A call's grid and LDS table come from plan_spectra: at most
+// kObsMaxBlocks workgroups (one thread each in the scan of their deferred counts) of contiguous
+// slices of about kObsSlice packets, and an LDS table of as many channel rows as fit kObsLdsBytes,
+// kObsMaxRows at the most (a slice of the device's order spans few channels, and the table is
+// zeroed and flushed in full), none in the plain form.
+constexpr int kObsMaxBlocks = 1024;
+constexpr int kObsSlice = 2048;
+constexpr int kObsLdsBytes = 32768;
+constexpr int kObsMaxRows = 16;
+struct ObsPlan {
+    int32_t blocks, lds_rows, lds_bytes, pad;
+    int64_t slice;
+};
+ObsPlan plan_spectra(int64_t n, int32_t nbins, bool lds);
+struct ObsSpectraArgs {
+    const uint64_t* events;  // [n] wide packets
+    const float* heights;    // [n]
+    const int64_t* d_n;      // nullable: device packet count (min(*d_n, n) packets are read)
+    const float* lo;         // [C] lower edge of bin 0
+    const float* inv;        // [C] 1 / bin width
+    int32_t* spectra;        // [C][nbins + 3]
+    uint64_t* deferred;      // nullable: [cap_def] packets that wait for their height
+    int64_t* ndef;           // [2] {qualified, written} (with deferred)
+    int32_t* wg_count;       // [kObsMaxBlocks] deferred packets of each workgroup's slice (with deferred)
+    int64_t* wg_off;         // [kObsMaxBlocks] where each workgroup's deferred packets start
+    int64_t n, j0, j_defer, cap_def, slice;
+    int32_t C, nbins, lds_rows, pad;
+};
+hipError_t launch_height_spectra(const ObsSpectraArgs& a, const ObsPlan& p, hipStream_t s);
+hipError_t launch_concat_packets(const uint64_t* a, const int64_t* d_na, int64_t cap_a, const uint64_t* b,
+                                 const int64_t* d_nb, int64_t cap_b, uint64_t* out, int64_t cap_out, int64_t* nout,
+                                 int32_t ncu, hipStream_t s);
+
 // Pulse capture (k_capture.hip; the contract is in its header comment)
 struct CaptureArgs {
     const float* phase;      // [rows][C] rad, global phase rows j0 .. j0 + rows - 1

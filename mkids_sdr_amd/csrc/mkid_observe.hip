@@ -1,0 +1,106 @@
+// C ABI of libmkidgpu.so (include/mkidgpu.h): the observing products after the heights — the
+// per-second count image, the per-channel pulse-height spectra with the list of packets that still
+// wait for their height, joining two counted lists, and the host twins of the first two. The rules
+// are obs_common.h; the kernels k_observe.hip.
+#include "mkid_ctx.h"
+#include "obs_common.h"
+
+using namespace mkid;
+
+extern "C" {
+
+static int count_photons(mkid_ctx* c, const uint64_t* d_events, const int64_t* d_n, int64_t n, int64_t j0,
+                         int32_t n_seconds, int32_t* d_image, int64_t* d_outside) {
+    if (!c || !d_image || !d_outside || (n > 0 && !d_events)) return MKID_E_ARG;
+    if (n < 0 || !obs::j0_ok(j0, c->N)) FAIL(c, MKID_E_ARG, "count photons: negative n / j0, or j0 N past int64");
+    if (!obs::seconds_ok(n_seconds)) FAIL(c, MKID_E_ARG, "count photons: need 1 <= n_seconds <= 2^20");
+    if (!obs::fs_ok(c->cfg.sample_rate))
+        FAIL(c, MKID_E_ARG, "count photons: the sample rate must be a positive integer number of samples per second");
+    HIPCHK(c, hipSetDevice(c->device));
+    const ObsCountArgs a{d_events, d_n, d_image, d_outside, n, j0, c->N, (int64_t)c->cfg.sample_rate,
+                         c->C, n_seconds, c->ncu, 0};
+    HIPCHK(c, launch_count_photons(a, c->stream));
+    return MKID_OK;
+}
+
+int mkid_count_photons(mkid_ctx* c, const uint64_t* d_events, int64_t n, int64_t j0, int32_t n_seconds,
+                       int32_t* d_image, int64_t* d_outside) {
+    return count_photons(c, d_events, nullptr, n, j0, n_seconds, d_image, d_outside);
+}
+
+int mkid_count_photons_counted(mkid_ctx* c, const uint64_t* d_events, const int64_t* d_count, int64_t cap, int64_t j0,
+                               int32_t n_seconds, int32_t* d_image, int64_t* d_outside) {
+    if (!d_count) return MKID_E_ARG;
+    return count_photons(c, d_events, d_count, cap, j0, n_seconds, d_image, d_outside);
+}
+
+static int height_spectra(mkid_ctx* c, const uint64_t* d_events, const float* d_heights, const int64_t* d_n, int64_t n,
+                          int64_t j0, int64_t j_defer, const float* d_lo, const float* d_inv, int32_t nbins,
+                          int32_t* d_spectra, uint64_t* d_deferred, int64_t cap_def, int64_t* d_ndef) {
+    if (!c) return MKID_E_ARG;
+    if (!obs::spectra_args_ok(d_events, d_heights, n, j0, c->C, d_lo, d_inv, nbins, d_spectra, d_deferred, cap_def,
+                              d_ndef))
+        FAIL(c, MKID_E_ARG,
+             "height spectra: need pointers, n, j0, cap_def >= 0, 1 <= nbins <= 16384, d_ndef with d_deferred");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (d_deferred && !c->d_obs_count.get()) {   // first use: nothing enqueued reads them yet
+        DevBuf<int32_t> cnt;
+        DevBuf<int64_t> off;
+        HIPCHK(c, cnt.alloc(kObsMaxBlocks));
+        HIPCHK(c, off.alloc(kObsMaxBlocks));
+        c->d_obs_count = std::move(cnt), c->d_obs_off = std::move(off);
+    }
+    ObsSpectraArgs a{};
+    a.events = d_events, a.heights = d_heights, a.d_n = d_n, a.lo = d_lo, a.inv = d_inv, a.spectra = d_spectra;
+    a.deferred = d_deferred, a.ndef = d_ndef, a.wg_count = c->d_obs_count.get(), a.wg_off = c->d_obs_off.get();
+    a.n = n, a.j0 = j0, a.j_defer = j_defer, a.cap_def = cap_def, a.C = c->C, a.nbins = nbins;
+    HIPCHK(c, launch_height_spectra(a, plan_spectra(n, nbins, c->obs_lds), c->stream));
+    return MKID_OK;
+}
+
+int mkid_height_spectra(mkid_ctx* c, const uint64_t* d_events, const float* d_heights, int64_t n, int64_t j0,
+                        int64_t j_defer, const float* d_lo, const float* d_inv, int32_t nbins, int32_t* d_spectra,
+                        uint64_t* d_deferred, int64_t cap_def, int64_t* d_ndef) {
+    return height_spectra(c, d_events, d_heights, nullptr, n, j0, j_defer, d_lo, d_inv, nbins, d_spectra, d_deferred,
+                          cap_def, d_ndef);
+}
+
+int mkid_height_spectra_counted(mkid_ctx* c, const uint64_t* d_events, const float* d_heights, const int64_t* d_count,
+                                int64_t cap, int64_t j0, int64_t j_defer, const float* d_lo, const float* d_inv,
+                                int32_t nbins, int32_t* d_spectra, uint64_t* d_deferred, int64_t cap_def,
+                                int64_t* d_ndef) {
+    if (!d_count) return MKID_E_ARG;
+    return height_spectra(c, d_events, d_heights, d_count, cap, j0, j_defer, d_lo, d_inv, nbins, d_spectra, d_deferred,
+                          cap_def, d_ndef);
+}
+
+int mkid_concat_packets(mkid_ctx* c, const uint64_t* d_a, const int64_t* d_na, int64_t cap_a, const uint64_t* d_b,
+                        const int64_t* d_nb, int64_t cap_b, uint64_t* d_out, int64_t cap_out, int64_t* d_nout) {
+    if (!c || !d_na || !d_nb || !d_nout) return MKID_E_ARG;
+    if (cap_a < 0 || cap_b < 0 || cap_out < 0) FAIL(c, MKID_E_ARG, "concat packets: negative capacity");
+    if ((cap_a > 0 && !d_a) || (cap_b > 0 && !d_b) || (cap_out > 0 && !d_out))
+        FAIL(c, MKID_E_ARG, "concat packets: a list with a capacity needs a pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, launch_concat_packets(d_a, d_na, cap_a, d_b, d_nb, cap_b, d_out, cap_out, d_nout, c->ncu, c->stream));
+    return MKID_OK;
+}
+
+// The CPU statements of the device calls: the loops of obs_common.h.
+int mkid_count_photons_host(const uint64_t* events, int64_t n, int64_t j0, int32_t fft_len, double sample_rate,
+                            int32_t n_channels, int32_t n_seconds, int32_t* image, int64_t* outside) {
+    if (!obs::count_args_ok(events, n, j0, fft_len, sample_rate, n_channels, n_seconds, image, outside))
+        return MKID_E_ARG;
+    obs::count_host(events, n, j0, fft_len, sample_rate, n_channels, n_seconds, image, outside);
+    return MKID_OK;
+}
+
+int mkid_height_spectra_host(const uint64_t* events, const float* heights, int64_t n, int64_t j0, int64_t j_defer,
+                             int32_t n_channels, const float* lo, const float* inv, int32_t nbins, int32_t* spectra,
+                             uint64_t* deferred, int64_t cap_def, int64_t* ndef) {
+    if (!obs::spectra_args_ok(events, heights, n, j0, n_channels, lo, inv, nbins, spectra, deferred, cap_def, ndef))
+        return MKID_E_ARG;
+    obs::spectra_host(events, heights, n, j0, j_defer, n_channels, lo, inv, nbins, spectra, deferred, cap_def, ndef);
+    return MKID_OK;
+}
+
+}  // extern "C"

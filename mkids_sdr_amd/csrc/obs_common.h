@@ -1,0 +1,107 @@
+// The observing products after the heights (include/mkidgpu.h mkid_count_photons and
+// mkid_height_spectra state them), one definition for the kernels of k_observe.hip and for the host
+// entry points mkid_count_photons_host / mkid_height_spectra_host: the second of a packet on the
+// 1 PPS timebase (packets.Timebase.second), where a packet is counted, the spectrum column of a
+// height, and which packets wait for their height. A packet's channel and unwrapped stamp are
+// fit::decode's. The host loops below are the whole of the host entry points, so that the CPU
+// sanitizer build (tools/plan_fuzz.cpp) runs them without HIP.
+#pragma once
+#include <stdint.h>
+
+#include "fit_common.h"
+#include "mkidgpu.h"
+
+#if defined(__HIPCC__)
+#define OBS_HD __host__ __device__ inline
+#else
+#define OBS_HD inline
+#endif
+
+namespace mkid {
+namespace obs {
+
+constexpr int32_t kMaxSeconds = 1 << 20;
+constexpr int32_t kMaxBins = 16384;
+constexpr int32_t kExtraCols = 3;   // under, over, no height
+
+// The sample clock as Timebase takes it: a positive integer number of samples per second that a
+// double holds exactly.
+OBS_HD bool fs_ok(double fs) { return fs >= 1.0 && fs < 9007199254740992.0 && fs == (double)(int64_t)fs; }
+OBS_HD bool seconds_ok(int32_t n_seconds) { return n_seconds >= 1 && n_seconds <= kMaxSeconds; }
+OBS_HD bool bins_ok(int32_t nbins) { return nbins >= 1 && nbins <= kMaxBins; }
+// every stamp of a call (below j0 + 2^28) times N stays inside int64
+OBS_HD bool j0_ok(int64_t j0, int32_t N) { return j0 >= 0 && N >= 1 && j0 <= INT64_MAX / N - ((int64_t)1 << 28); }
+
+// Second of phase row jg: ADC sample jg N at fs samples per second.
+OBS_HD int64_t second(int64_t jg, int64_t N, int64_t fs) { return jg * N / fs; }
+
+// Where a packet is counted: cell sec C + ch of the image, or one of the two `outside` counters.
+constexpr int64_t kNonPixel = -1, kLate = -2;   // outside[0], outside[1]
+OBS_HD int64_t cell(const fit::Stamp& st, int32_t C, int64_t N, int64_t fs, int32_t n_seconds) {
+    if (st.ch >= C) return kNonPixel;
+    const int64_t sec = second(st.jg, N, fs);
+    return sec < n_seconds ? sec * C + st.ch : kLate;
+}
+
+// Column of height h in a row of nbins + 3: 0 under, 1 .. nbins the bins, nbins + 1 over,
+// nbins + 2 no height. t = h - lo and u = t inv are each rounded once in fp32, and the float
+// compares come before the conversion to int, so every (h, lo, inv) has a defined column.
+OBS_HD int32_t column(float h, float lo, float inv, int32_t nbins) {
+    if (!__builtin_isfinite(h)) return nbins + 2;
+#if defined(__HIP_DEVICE_COMPILE__)
+    const float u = __fmul_rn(__fsub_rn(h, lo), inv);
+#else
+    const float t = h - lo;   // fp32 arithmetic on the hosts built for (no excess precision)
+    const float u = t * inv;
+#endif
+    if (u != u) return nbins + 2;
+    if (u < 0.f) return 0;
+    if (u >= (float)nbins) return nbins + 1;
+    return 1 + (int32_t)u;
+}
+
+// A packet that waits for its height: no finite height yet and a stamp whose window passes the
+// call's last row.
+OBS_HD bool deferred(float h, int64_t jg, int64_t j_defer) { return !__builtin_isfinite(h) && jg >= j_defer; }
+
+inline bool count_args_ok(const uint64_t* events, int64_t n, int64_t j0, int32_t N, double fs, int32_t C,
+                          int32_t n_seconds, const int32_t* image, const int64_t* outside) {
+    return image && outside && (n == 0 || events) && n >= 0 && C >= 1 && C <= 4096 && seconds_ok(n_seconds) &&
+           fs_ok(fs) && j0_ok(j0, N);
+}
+
+inline void count_host(const uint64_t* events, int64_t n, int64_t j0, int32_t N, double fs, int32_t C,
+                       int32_t n_seconds, int32_t* image, int64_t* outside) {
+    for (int64_t p = 0; p < n; ++p) {
+        const int64_t k = cell(fit::decode(events[p], j0), C, N, (int64_t)fs, n_seconds);
+        if (k >= 0)
+            ++image[k];
+        else
+            ++outside[k == kNonPixel ? 0 : 1];
+    }
+}
+
+inline bool spectra_args_ok(const uint64_t* events, const float* heights, int64_t n, int64_t j0, int32_t C,
+                            const float* lo, const float* inv, int32_t nbins, const int32_t* spectra,
+                            const uint64_t* deferred_out, int64_t cap_def, const int64_t* ndef) {
+    return lo && inv && spectra && (n == 0 || (events && heights)) && n >= 0 && j0 >= 0 && C >= 1 && C <= 4096 &&
+           bins_ok(nbins) && cap_def >= 0 && (!deferred_out || ndef);
+}
+
+inline void spectra_host(const uint64_t* events, const float* heights, int64_t n, int64_t j0, int64_t j_defer,
+                         int32_t C, const float* lo, const float* inv, int32_t nbins, int32_t* spectra,
+                         uint64_t* deferred_out, int64_t cap_def, int64_t* ndef) {
+    for (int64_t p = 0; p < n; ++p) {
+        const fit::Stamp st = fit::decode(events[p], j0);
+        if (st.ch >= C) continue;
+        if (deferred_out && deferred(heights[p], st.jg, j_defer)) {
+            ++ndef[0];
+            if (ndef[1] >= 0 && ndef[1] < cap_def) deferred_out[ndef[1]++] = events[p];
+            continue;
+        }
+        ++spectra[(int64_t)st.ch * (nbins + kExtraCols) + column(heights[p], lo[st.ch], inv[st.ch], nbins)];
+    }
+}
+
+}  // namespace obs
+}  // namespace mkid

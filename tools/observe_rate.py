@@ -1,0 +1,182 @@
+#!/usr/bin/env python3
+"""Time the stage after the heights (k_observe.hip: count image, pulse-height spectra, list join)
+against mkid_pulse_heights on the same list, in one process, at config 5's shape: phase
+[2^18][2048] (one 2^30-sample step at N = 4096), ncoeff = 100, pre = 20, 690 000 packets with
+ascending stamps spread over the channels, nbins = 256, a three-second image. The list is timed in
+two orders: `dev`, the device's own (channel-major, time-ascending in a channel: what mkid_process
+hands to the stage) and `time`, the same packets by ascending stamp (tools/heights_fit_rate.py's list;
+the worst case for the count kernel's runs and the spectra kernel's LDS rows).
+
+  heights        mkid_pulse_heights alone: the yardstick on the same list
+  count_*        mkid_count_photons
+  spectra_lds_*  mkid_height_spectra with the LDS table   (a context made under MKID_OBS_LDS=1)
+  spectra_plain_*  the same kernel, one global atomic per packet (MKID_OBS_LDS=0)
+  spectra_defer  the shipped form with a deferred list (the packets of the last ncoeff - pre rows wait)
+  concat         mkid_concat_packets of 5000 + 690 000 packets
+  host_route     what this replaces: device-to-host copy of list and heights, then the numpy restatement
+                 (tests/observe_cases.py), wall clock
+
+Every device path is one HIP-event interval on a stream shared with torch; the paths alternate inside
+each of --reps rounds after two warm-up rounds, and the median, minimum and maximum over the rounds
+are reported. On the way all paths must give the same integers as the numpy restatement. Prints one
+JSON line and, with --out, writes it.
+
+    python tools/observe_rate.py [--reps 20] [--packets 690000] [--out profiles/observe/observe_rate_c5.json]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+
+from heights_fit_rate import event_ms, stats  # noqa: E402
+
+
+def context(C, stream, lds=None):
+    from mkids_sdr_amd.channelizer import Channelizer
+    old = os.environ.pop('MKID_OBS_LDS', None)
+    if lds is not None:
+        os.environ['MKID_OBS_LDS'] = '1' if lds else '0'
+    try:
+        ch = Channelizer(C, max_chunk=1 << 20)
+    finally:
+        os.environ.pop('MKID_OBS_LDS', None)
+        if old is not None:
+            os.environ['MKID_OBS_LDS'] = old
+    ch.set_stream(stream.cuda_stream)
+    return ch
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--reps', type=int, default=20)
+    ap.add_argument('--packets', type=int, default=690000)
+    ap.add_argument('--channels', type=int, default=2048)
+    ap.add_argument('--rows', type=int, default=1 << 18)
+    ap.add_argument('--ncoeff', type=int, default=100)
+    ap.add_argument('--pre', type=int, default=20)
+    ap.add_argument('--nbins', type=int, default=256)
+    ap.add_argument('--out', default=None)
+    args = ap.parse_args()
+    import torch
+    import observe_cases as oc
+    C, J, nco, pre, n, nbins = args.channels, args.rows, args.ncoeff, args.pre, args.packets, args.nbins
+    n_seconds, n_a = 3, 5000
+    rng = np.random.default_rng(0)
+    coeff = rng.normal(size=(C, nco)).astype(np.float32)
+    s = torch.cuda.Stream()
+    ctx = {'default': context(C, s), 'lds': context(C, s, True), 'plain': context(C, s, False)}
+    ctx['default'].set_pulse_filter(coeff, pre)
+    N, fs = ctx['default'].N, int(ctx['default'].cfg.sample_rate)
+    d_ph = torch.randn(J, C, device='cuda')
+    chs = rng.integers(0, C, n).astype(np.uint64)
+    ts = np.sort(rng.integers(pre, J, n)).astype(np.int64)         # the last nco - pre rows: no height yet
+    ev = {'time': (chs << np.uint64(52)) | ts.astype(np.uint64)}
+    ev['dev'] = oc.device_order(ev['time'], 0)
+    j_defer = J + pre - nco + 1
+    lo = np.full(C, -32.0, np.float32) + rng.uniform(0, 1, C).astype(np.float32)
+    inv = np.full(C, np.float32(1) / np.float32(0.25), np.float32)
+    d_lo, d_inv = torch.from_numpy(lo).cuda(), torch.from_numpy(inv).cuda()
+    d_ev = {o: torch.from_numpy(e.view(np.int64)).cuda() for o, e in ev.items()}
+    d_h = {o: torch.empty(n, dtype=torch.float32, device='cuda') for o in ev}
+    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device='cuda')
+    names = ['count_dev', 'count_time', 'spectra_lds_dev', 'spectra_lds_time', 'spectra_plain_dev', 'spectra_plain_time',
+             'spectra_defer']
+    image = {k: z((n_seconds, C), torch.int32) for k in names if k.startswith('count')}
+    outside = {k: z(2, torch.int64) for k in image}
+    spectra = {k: z((C, nbins + 3), torch.int32) for k in names if k.startswith('spectra')}
+    d_def, d_ndef = z(n, torch.int64), z(2, torch.int64)
+    d_a, d_na, d_nb = d_ev['time'][:n_a].clone(), torch.tensor([n_a], device='cuda'), torch.tensor([n], device='cuda')
+    d_join, d_njoin = z(n + n_a, torch.int64), z(2, torch.int64)
+    torch.cuda.synchronize()
+    for o in ev:                               # the heights both orders are binned from
+        ctx['default'].pulse_heights_device(d_ph, J, 0, d_ev[o], n, d_h[o])
+    torch.cuda.synchronize()
+
+    def count(o):
+        k = 'count_' + o
+        return lambda: ctx['default'].count_photons_device(d_ev[o], n, 0, n_seconds, image[k], outside[k])
+
+    def spec(form, o):
+        k = 'spectra_%s_%s' % (form, o)
+        return lambda: ctx[form].height_spectra_device(d_ev[o], d_h[o], n, 0, 0, d_lo, d_inv, nbins, spectra[k])
+
+    def spec_defer():
+        ctx['default'].height_spectra_device(d_ev['dev'], d_h['dev'], n, 0, j_defer, d_lo, d_inv, nbins,
+                                             spectra['spectra_defer'], d_def, n, d_ndef)
+
+    paths = [('heights', lambda: ctx['default'].pulse_heights_device(d_ph, J, 0, d_ev['dev'], n, d_h['dev']))]
+    paths += [('count_' + o, count(o)) for o in ('dev', 'time')]
+    paths += [('spectra_%s_%s' % (f, o), spec(f, o)) for o in ('dev', 'time') for f in ('lds', 'plain')]
+    paths += [('spectra_defer', spec_defer),
+              ('concat', lambda: ctx['default'].concat_packets(d_a, d_na, n_a, d_ev['dev'], d_nb, n, d_join, n + n_a, d_njoin))]
+    times = {name: [] for name, _ in paths}
+    for rep in range(args.reps + 2):           # two warm-up rounds: code objects, clocks, caches
+        for name, fn in paths:
+            t = event_ms(s, fn)
+            if rep >= 2:
+                times[name].append(t)
+
+    # the route this replaces, and the integers every path must give
+    host_t = []
+    for _ in range(3):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        h_ev, h_h = d_ev['dev'].cpu().numpy().view(np.uint64), d_h['dev'].cpu().numpy()
+        t1 = time.perf_counter()
+        ref_image, ref_out = oc.count_ref(h_ev, 0, N, fs, C, n_seconds)
+        ref_sp, _, _ = oc.spectra_ref(h_ev, h_h, 0, 0, C, lo, inv, nbins)
+        host_t.append(((t1 - t0) * 1e3, (time.perf_counter() - t1) * 1e3))
+    ref_dsp, ref_def, ref_ndef = oc.spectra_ref(h_ev, h_h, 0, j_defer, C, lo, inv, nbins, defer=True, cap_def=n)
+    for t in list(image.values()) + list(outside.values()) + list(spectra.values()) + [d_ndef]:
+        t.zero_()
+    torch.cuda.synchronize()
+    for name, fn in paths[1:]:
+        fn()
+    torch.cuda.synchronize()
+    nd = d_ndef.cpu().numpy()
+    check = dict(
+        images_equal_numpy=bool(all(np.array_equal(t.cpu().numpy(), ref_image) for t in image.values())),
+        outside_equal_numpy=bool(all(np.array_equal(t.cpu().numpy(), ref_out) for t in outside.values())),
+        spectra_equal_numpy=bool(all(np.array_equal(spectra[k].cpu().numpy(), ref_sp) for k in names[2:6])),
+        deferred_equal_numpy=bool(np.array_equal(spectra['spectra_defer'].cpu().numpy(), ref_dsp) and
+                                  np.array_equal(nd, ref_ndef) and
+                                  np.array_equal(d_def[:int(nd[1])].cpu().numpy().view(np.uint64), ref_def)),
+        concat=bool(np.array_equal(d_join.cpu().numpy().view(np.uint64), np.concatenate([ev['time'][:n_a], ev['dev']])) and
+                    d_njoin.cpu().tolist() == [n + n_a, n + n_a]),
+        packets_in_image=int(ref_image.sum()), packets_late=int(ref_out[1]), no_height=int(ref_sp[:, nbins + 2].sum()),
+        deferred=int(ref_ndef[0]), channels_with_packets=int((ref_sp.sum(axis=1) > 0).sum()))
+    med = {name: float(np.median(t)) for name, t in times.items()}
+    out = dict(tool='observe_rate', channels=C, rows=J, ncoeff=nco, pre=pre, packets=n, nbins=nbins, n_seconds=n_seconds,
+               reps=args.reps)
+    for name, t in times.items():
+        out.update(stats(name, t))
+        out[name + '_mpackets_per_s'] = round(n / med[name] / 1e3, 1)
+    for o in ('dev', 'time'):
+        l, p = times['spectra_lds_' + o], times['spectra_plain_' + o]
+        out['lds_over_plain_' + o] = round(med['spectra_lds_' + o] / med['spectra_plain_' + o], 3)
+        out['lds_range_clear_of_plain_' + o] = bool(max(l) < min(p))
+    out['stage_over_heights'] = round((med['count_dev'] + med['concat'] + med['spectra_defer']) / med['heights'], 3)
+    out['host_route_copy_ms'] = round(float(np.median([a for a, _ in host_t])), 2)
+    out['host_route_numpy_ms'] = round(float(np.median([b for _, b in host_t])), 2)
+    out['checks'] = check
+    line = json.dumps(out)
+    print(line, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as f:
+            f.write(line + '\n')
+    for c in ctx.values():
+        c.set_stream(None)
+        c.close()
+    return 0 if all(v for v in check.values() if isinstance(v, bool)) else 1
+
+
+if __name__ == '__main__':
+    sys.exit(main())

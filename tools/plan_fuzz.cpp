@@ -4,6 +4,7 @@
 // device code relies on (include/mkidgpu.h); the slot-table writes are replayed into
 // buffers of exactly the planned size, so an undersized plan is an ASan heap overflow, not a
 // silent miscount (the ADVICE r02 scratch-sizing bug is that class).
+// fuzz_observe drives the observing rules and the host twins' loops (csrc/obs_common.h) likewise.
 //   plan_fuzz [iterations] [seed]
 #include <stdint.h>
 #include <stdio.h>
@@ -16,6 +17,7 @@
 
 #include "fit_common.h"
 #include "mkid_plan.h"
+#include "obs_common.h"
 
 extern "C" {
 typedef struct {
@@ -638,6 +640,109 @@ static void fuzz_fit(int iters) {
           "window test");
 }
 
+// The observing rules (obs_common.h) and the loops of the two host twins on random words, heights
+// (NaN, +-inf, +-0, bin edges) and shapes, against a plain per-packet restatement; the outputs are
+// buffers of exactly the documented sizes, so a column or cell outside them is an ASan report.
+static void fuzz_observe(int iters) {
+    namespace obs = mkid::obs;
+    CHECK(obs::fs_ok(1e6) && obs::fs_ok(1.0) && !obs::fs_ok(1e6 + 0.5) && !obs::fs_ok(0.0) && !obs::fs_ok(-2.0) &&
+              !obs::fs_ok(9007199254740992.0) && !obs::fs_ok(NAN) && !obs::fs_ok(INFINITY),
+          "fs_ok");
+    CHECK(obs::column(-0.0f, 0.f, 1.f, 4) == 1 && obs::column(INFINITY, 0.f, 1.f, 4) == 6 &&
+              obs::column(-INFINITY, 0.f, 1.f, 4) == 6 && obs::column(NAN, 0.f, 1.f, 4) == 6 &&
+              obs::column(4.f, 0.f, 1.f, 4) == 5 && obs::column(3.9999f, 0.f, 1.f, 4) == 4 &&
+              obs::column(-1e-30f, 0.f, 1.f, 4) == 0 && obs::column(1e38f, 0.f, 1e38f, 4) == 5 &&
+              obs::column(0.f, 0.f, INFINITY, 4) == 6 && obs::column(1.f, 0.f, NAN, 4) == 6,
+          "column rule fixed points");
+    const float specials[] = {NAN, INFINITY, -INFINITY, -0.0f, 0.0f, 1e38f, -1e38f, 3.4e38f};
+    for (int it = 0; it < iters; ++it) {
+        const int32_t C = (int32_t)rint_(1, 70), N = (int32_t)(1 << rint_(0, 12)), nbins = (int32_t)(rint_(0, 3) ? rint_(1, 40) : rint_(1, obs::kMaxBins));
+        const int32_t n_seconds = (int32_t)rint_(1, 6);
+        const int64_t n = rint_(0, 300), j0 = rint_(0, 3) ? rint_(0, 5000) : rint_(0, (int64_t)1 << 40);
+        const int64_t fs = (int64_t)N * rint_(1, 4000);   // 1 .. 4000 rows per second
+        const int64_t j_defer = j0 + rint_(-10, 3000), cap_def = rint_(0, 40);
+        const bool defer = rint_(0, 2) != 0;
+        std::vector<uint64_t> ev((size_t)n);
+        std::vector<float> h((size_t)n), lo((size_t)C), inv((size_t)C);
+        for (auto& x : lo) x = (float)rint_(-300, 300) / 100.f;
+        for (auto& x : inv) x = rint_(0, 20) ? (float)rint_(1, 4000) / 100.f : specials[rint_(0, 7)];
+        for (int64_t p = 0; p < n; ++p) {
+            const uint64_t ch = rint_(0, 5) ? (uint64_t)rint_(0, C - 1) : (uint64_t)rint_(0, 4095);
+            const int64_t jg = j0 + rint_(j0 > 0 ? -1 : 0, 6000);
+            ev[(size_t)p] = (ch << MKID_PKT_CH_SHIFT) | ((uint64_t)rint_(0, (1 << 24) - 1) << MKID_PKT_BASE_SHIFT) |
+                            ((uint64_t)jg & MKID_PKT_TS_MASK);
+            const int64_t k = rint_(0, 9);
+            h[(size_t)p] = k == 0 ? specials[rint_(0, 7)]
+                           : k == 1 ? lo[(size_t)std::min<uint64_t>(ch, C - 1)] + (float)rint_(0, nbins) / inv[(size_t)std::min<uint64_t>(ch, C - 1)]
+                                    : (float)rint_(-2000, 2000) / 100.f;
+        }
+        std::vector<int32_t> image((size_t)n_seconds * C, 0), ref_image(image);
+        int64_t outside[2] = {0, 0}, ref_outside[2] = {0, 0};
+        CHECK(obs::count_args_ok(ev.data(), n, j0, N, (double)fs, C, n_seconds, image.data(), outside), "count args");
+        // two calls over the halves: the results continue
+        obs::count_host(ev.data(), n / 2, j0, N, (double)fs, C, n_seconds, image.data(), outside);
+        obs::count_host(ev.data() + n / 2, n - n / 2, j0, N, (double)fs, C, n_seconds, image.data(), outside);
+        const int64_t base = j0 > ((int64_t)1 << 27) ? j0 - ((int64_t)1 << 27) : 0;
+        const int32_t cols = nbins + obs::kExtraCols;
+        std::vector<int32_t> spectra((size_t)C * cols, 0), ref_spectra(spectra);
+        std::vector<uint64_t> deferred((size_t)cap_def + 1), ref_deferred;   // + 1: never a null data()
+        int64_t ndef[2] = {0, 0}, qualified = 0;
+        obs::spectra_host(ev.data(), h.data(), n, j0, j_defer, C, lo.data(), inv.data(), nbins, spectra.data(),
+                          defer ? deferred.data() : nullptr, cap_def, defer ? ndef : nullptr);
+        for (int64_t p = 0; p < n; ++p) {
+            const uint64_t w = ev[(size_t)p];
+            const int64_t ch = (int64_t)(w >> 52), ts = (int64_t)(w & 0xFFFFFFF);
+            const int64_t jg = base + (((ts - base) % (1 << 28)) + (1 << 28)) % (1 << 28);
+            const mkid::fit::Stamp st = mkid::fit::decode(w, j0);
+            CHECK(st.ch == ch && st.jg == jg, "decode");
+            if (ch >= C) {
+                ++ref_outside[0];
+                continue;
+            }
+            const int64_t sec = (jg * N) / fs;
+            CHECK(sec == obs::second(jg, N, fs), "second");
+            if (sec >= n_seconds)
+                ++ref_outside[1];
+            else
+                ++ref_image[(size_t)(sec * C + ch)];
+            const float x = h[(size_t)p];
+            if (defer && !std::isfinite(x) && jg >= j_defer) {
+                ++qualified;
+                if ((int64_t)ref_deferred.size() < cap_def) ref_deferred.push_back(w);
+                continue;
+            }
+            int32_t col;
+            const float u = (x - lo[(size_t)ch]) * inv[(size_t)ch];
+            if (!std::isfinite(x) || std::isnan(u)) col = nbins + 2;
+            else if (u < 0.f) col = 0;
+            else if (u >= (float)nbins) col = nbins + 1;
+            else col = 1 + (int32_t)u;
+            CHECK(col == obs::column(x, lo[(size_t)ch], inv[(size_t)ch], nbins) && col >= 0 && col < cols, "column %d", col);
+            ++ref_spectra[(size_t)ch * cols + col];
+        }
+        CHECK(image == ref_image && outside[0] == ref_outside[0] && outside[1] == ref_outside[1], "count image");
+        CHECK(spectra == ref_spectra, "spectra");
+        CHECK(ndef[1] <= cap_def, "deferred list past cap_def");
+        deferred.resize((size_t)ndef[1]);
+        CHECK(ndef[0] == qualified && ndef[1] == (int64_t)ref_deferred.size() && deferred == ref_deferred, "deferred list");
+    }
+    int32_t i4 = 0;
+    int64_t o2[2] = {0, 0};
+    uint64_t w1 = 0;
+    float f1 = 0.f;
+    CHECK(!obs::count_args_ok(&w1, 1, 0, 128, 1e6, 64, 0, &i4, o2) && !obs::count_args_ok(&w1, 1, 0, 128, 1e6, 64, (1 << 20) + 1, &i4, o2) &&
+              !obs::count_args_ok(nullptr, 1, 0, 128, 1e6, 64, 1, &i4, o2) && !obs::count_args_ok(&w1, -1, 0, 128, 1e6, 64, 1, &i4, o2) &&
+              !obs::count_args_ok(&w1, 1, -1, 128, 1e6, 64, 1, &i4, o2) && !obs::count_args_ok(&w1, 1, INT64_MAX / 128, 128, 1e6, 64, 1, &i4, o2) &&
+              obs::count_args_ok(nullptr, 0, 0, 128, 1e6, 64, 1, &i4, o2),
+          "count argument checks");
+    CHECK(!obs::spectra_args_ok(&w1, &f1, 1, 0, 64, &f1, &f1, 0, &i4, nullptr, 0, nullptr) &&
+              !obs::spectra_args_ok(&w1, &f1, 1, 0, 64, &f1, &f1, 16385, &i4, nullptr, 0, nullptr) &&
+              !obs::spectra_args_ok(&w1, &f1, 1, 0, 64, &f1, &f1, 4, &i4, &w1, 0, nullptr) &&
+              !obs::spectra_args_ok(&w1, &f1, 1, 0, 64, &f1, &f1, 4, &i4, &w1, -1, o2) &&
+              obs::spectra_args_ok(&w1, &f1, 1, 0, 64, &f1, &f1, 4, &i4, &w1, 0, o2),
+          "spectra argument checks");
+}
+
 int main(int argc, char** argv) {
     const int iters = argc > 1 ? atoi(argv[1]) : 300;
     rng.seed(argc > 2 ? strtoull(argv[2], nullptr, 10) : 12345);
@@ -652,6 +757,7 @@ int main(int argc, char** argv) {
     fuzz_thresholds(iters / 2 + 1);
     fuzz_noise(iters / 10 + 1);
     fuzz_fit(iters);
+    fuzz_observe(iters);
     if (failures) {
         fprintf(stderr, "%d failures\n", failures);
         return 1;
