@@ -441,6 +441,95 @@ int mkid_height_spectra_host(const uint64_t* events, const float* heights, int64
                              int32_t nbins, int32_t* spectra, uint64_t* deferred /* nullable */,
                              int64_t cap_def, int64_t* ndef /* nullable with deferred */);
 
+/* The time-tagged photon list: the reference's PacketMaster writes one variable-length row of
+ * 64-bit packets per pixel per second (/r#/p#/t<obs>, PacketMaster.c:371-381, 978-1050) and keeps
+ * at most MAX_EVENTS_PER_SEC - 1 = 2499 events in each (PacketMaster.c:55); the count image above
+ * is that table's row lengths. Here the table is [n_seconds][C][K] on the device, 1 <= K <= 65536
+ * chosen by the caller, filled inside the streamed step, with each photon's height (and arrival
+ * offset) attached when the deferral protocol settles it. The rules have one definition,
+ * csrc/obs_common.h; ch, jg and the cell (sec = (jg fft_len) / sample_rate) are those of
+ * mkid_count_photons.
+ *
+ * mkid_list_photons: d_image and d_outside are updated exactly as mkid_count_photons updates them
+ * (the call replaces that call in a step; both caller-owned and continued across calls). The
+ * packets of cell (sec, ch) take slots in arrival order, starting at image[sec][ch] before the
+ * call; a packet with slot < K stores
+ *     d_words[sec][ch][slot]   the row word, by `layout`, with
+ *                              us = (((jg fft_len) mod sample_rate) * 1000000) / sample_rate in int64
+ *       MKID_ROW_WIDE       ch << 52 | peak << 40 | base << 28 | us   (the device packet with its
+ *                           time field replaced; any C)
+ *       MKID_ROW_REFERENCE  ch << 56 | peak << 44 | p1 << 32 | base << 20 | (us & 0xFFFFF),
+ *                           p1 = clip(peak - base + 2048, 0, 4095): mkid_pack_reference's fields
+ *                           (C <= 254)
+ *     d_stamps[sec][ch][slot]  jg, the exact time tag and the key mkid_fill_photon_heights searches
+ * and a packet with slot >= K is not stored and adds 1 to d_dropped int64[1] (the reference's
+ * "first K kept"). Slots >= min(count, K) of a row are never written. d_words uint64 and d_stamps
+ * int64 are [n_seconds][C][K], caller-owned. Each packet is passed once, with the call that
+ * produced it, as for mkid_count_photons.
+ *   - Device order (channel-major, stamp-ascending in a channel): a cell's packets are one
+ *     contiguous run of the list, and row (sec, ch) holds that cell's packets of the whole stream
+ *     in ascending stamp. Any chunking of a stream into calls, one-row calls included, gives the
+ *     bits of one call over it.
+ *   - Any other order: d_image, d_outside and d_dropped stay exact, and so does the set of (word,
+ *     stamp) pairs of every row that did not overflow; but each maximal run of one cell in the
+ *     list lands as a whole, and the runs of a cell in unspecified relative order (which packets
+ *     of an overflowing row are the K kept is then unspecified too).
+ * One integer atomic per run, no floating-point atomic; order comes from kernel boundaries. The
+ * call's workspace (12 bytes per packet of n or cap) is the context's, grown on demand: allocate,
+ * synchronise the stream once, move in; a call that does not grow it makes no synchronisation.
+ * MKID_E_ARG before any launch: a null d_image, d_outside, d_words, d_stamps or d_dropped, a null
+ * d_events with n > 0, a null d_count, a negative n, cap or j0 (or one so large that jg fft_len
+ * leaves int64), n_seconds outside 1 .. 2^20, K outside 1 .. 65536, an unknown layout,
+ * MKID_ROW_REFERENCE with C > 254, a sample_rate that is not a positive integer, or one above 2^43
+ * (the product for us stays inside int64).
+ *
+ * mkid_fill_photon_heights: given the list and heights of a step's joined list (what
+ * mkid_height_spectra is given; d_dt nullable, the second output of mkid_pulse_fit), for every
+ * packet with ch < C that is not deferred (height finite, or jg < j_defer: the predicate of
+ * mkid_height_spectra, so a packet is filled in exactly the step that bins it) jg is
+ * binary-searched in d_stamps[sec][ch][0 .. min(image[sec][ch], K)). Found: the height (and dt,
+ * with d_dt and d_row_dt) is copied into that slot of d_row_height (d_row_dt) bit for bit, NaN
+ * included, and d_fill[0] += 1. Not found (sec >= n_seconds, or a packet its row dropped):
+ * d_fill[1] += 1. Deferred packets and packets with ch >= C touch nothing. d_row_height float32
+ * [n_seconds][C][K] and the nullable d_row_dt of the same shape are caller-owned and pre-filled by
+ * the caller (with NaN); d_fill int64[2] is caller-owned and continued. Each row must be
+ * stamp-ascending with distinct stamps: the device order of mkid_list_photons and a trigger with a
+ * dead time give that. The result does not depend on the order of the list. No workspace.
+ * MKID_E_ARG as for mkid_list_photons (n, cap, j0, n_seconds, K, sample_rate), and a null d_image,
+ * d_stamps, d_row_height or d_fill, or null d_events or d_heights with n > 0.
+ *
+ * Common to the four device calls: device pointers only; asynchronous on the context stream; no
+ * device-to-host copy; n == 0 is valid; the counted forms read min(*d_count, cap) packets. Not
+ * timed (no MKID_K_ id).
+ * mkid_list_photons_host / mkid_fill_photon_heights_host: the same rules on host memory through the
+ * same definitions; no device, no context. The same MKID_E_ARG cases, and n_channels outside
+ * 1 .. 4096 or fft_len < 1. */
+#define MKID_ROW_WIDE 0
+#define MKID_ROW_REFERENCE 1
+int mkid_list_photons(mkid_ctx* ctx, const uint64_t* d_events, int64_t n, int64_t j0, int32_t n_seconds,
+                      int32_t K, int32_t layout, int32_t* d_image, int64_t* d_outside, uint64_t* d_words,
+                      int64_t* d_stamps, int64_t* d_dropped);
+int mkid_list_photons_counted(mkid_ctx* ctx, const uint64_t* d_events, const int64_t* d_count, int64_t cap,
+                              int64_t j0, int32_t n_seconds, int32_t K, int32_t layout, int32_t* d_image,
+                              int64_t* d_outside, uint64_t* d_words, int64_t* d_stamps, int64_t* d_dropped);
+int mkid_fill_photon_heights(mkid_ctx* ctx, const uint64_t* d_events, const float* d_heights,
+                             const float* d_dt /* nullable */, int64_t n, int64_t j0, int64_t j_defer,
+                             int32_t n_seconds, int32_t K, const int32_t* d_image, const int64_t* d_stamps,
+                             float* d_row_height, float* d_row_dt /* nullable */, int64_t* d_fill);
+int mkid_fill_photon_heights_counted(mkid_ctx* ctx, const uint64_t* d_events, const float* d_heights,
+                                     const float* d_dt, const int64_t* d_count, int64_t cap, int64_t j0,
+                                     int64_t j_defer, int32_t n_seconds, int32_t K, const int32_t* d_image,
+                                     const int64_t* d_stamps, float* d_row_height, float* d_row_dt,
+                                     int64_t* d_fill);
+int mkid_list_photons_host(const uint64_t* events, int64_t n, int64_t j0, int32_t fft_len, double sample_rate,
+                           int32_t n_channels, int32_t n_seconds, int32_t K, int32_t layout, int32_t* image,
+                           int64_t* outside, uint64_t* words, int64_t* stamps, int64_t* dropped);
+int mkid_fill_photon_heights_host(const uint64_t* events, const float* heights, const float* dt /* nullable */,
+                                  int64_t n, int64_t j0, int64_t j_defer, int32_t fft_len, double sample_rate,
+                                  int32_t n_channels, int32_t n_seconds, int32_t K, const int32_t* image,
+                                  const int64_t* stamps, float* row_height, float* row_dt /* nullable */,
+                                  int64_t* fill);
+
 /* Pulse capture: the firmware-style capture block between the stream and the template analysis.
  * For every photon packet the phase window around its stamp is copied into a caller-owned,
  * per-channel record bank on the device, for all channels at once and across streamed calls (the

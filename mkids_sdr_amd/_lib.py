@@ -24,6 +24,7 @@ FRONT_AUTO, FRONT_SPLIT = 0, 1
 
 PKT_CH_SHIFT, PKT_PEAK_SHIFT, PKT_BASE_SHIFT = 52, 40, 28
 PKT_TS_MASK = (1 << 28) - 1
+ROW_WIDE, ROW_REFERENCE = 0, 1       # mkid_list_photons' row word layouts
 
 
 class MkidError(RuntimeError):
@@ -139,6 +140,12 @@ _SIGS = {
     'mkid_concat_packets': [P, P, P, I64, P, P, I64, P, I64, P],
     'mkid_count_photons_host': [P, I64, I64, I32, ctypes.c_double, I32, I32, P, P],
     'mkid_height_spectra_host': [P, P, I64, I64, I64, I32, P, P, I32, P, P, I64, P],
+    'mkid_list_photons': [P, P, I64, I64, I32, I32, I32, P, P, P, P, P],
+    'mkid_list_photons_counted': [P, P, P, I64, I64, I32, I32, I32, P, P, P, P, P],
+    'mkid_fill_photon_heights': [P, P, P, P, I64, I64, I64, I32, I32, P, P, P, P, P],
+    'mkid_fill_photon_heights_counted': [P, P, P, P, P, I64, I64, I64, I32, I32, P, P, P, P, P],
+    'mkid_list_photons_host': [P, I64, I64, I32, ctypes.c_double, I32, I32, I32, I32, P, P, P, P, P],
+    'mkid_fill_photon_heights_host': [P, P, P, I64, I64, I64, I32, ctypes.c_double, I32, I32, I32, P, P, P, P, P],
     'mkid_set_capture': [P, I32, I32, I32],
     'mkid_capture_pulses': [P, P, I64, I64, P, I64, P, P, P],
     'mkid_capture_pulses_counted': [P, P, I64, I64, P, P, I64, P, P, P],

@@ -418,6 +418,41 @@ class Channelizer:
         self._chk(self._L.mkid_count_photons_counted(self._h, _ptr(d_events), _ptr(d_count), int(cap), int(j0),
                                                      int(n_seconds), _ptr(d_image), _ptr(d_outside)))
 
+    def list_photons_device(self, d_events, n, j0, n_seconds, K, layout, d_image, d_outside, d_words, d_stamps,
+                            d_dropped):
+        """Device pointers; asynchronous on the context stream (include/mkidgpu.h mkid_list_photons):
+        d_image and d_outside are added to as by count_photons_device, and the packets go to their
+        cells' rows of d_words uint64 / d_stamps int64 [n_seconds][C][K]; d_dropped int64 [1] counts
+        the packets past slot K - 1."""
+        self._chk(self._L.mkid_list_photons(self._h, _ptr(d_events), int(n), int(j0), int(n_seconds), int(K),
+                                            int(layout), _ptr(d_image), _ptr(d_outside), _ptr(d_words),
+                                            _ptr(d_stamps), _ptr(d_dropped)))
+
+    def list_photons_counted(self, d_events, d_count, cap, j0, n_seconds, K, layout, d_image, d_outside, d_words,
+                             d_stamps, d_dropped):
+        """As list_photons_device with the packet count read on the device."""
+        self._chk(self._L.mkid_list_photons_counted(self._h, _ptr(d_events), _ptr(d_count), int(cap), int(j0),
+                                                    int(n_seconds), int(K), int(layout), _ptr(d_image),
+                                                    _ptr(d_outside), _ptr(d_words), _ptr(d_stamps), _ptr(d_dropped)))
+
+    def fill_photon_heights_device(self, d_events, d_heights, d_dt, n, j0, j_defer, n_seconds, K, d_image, d_stamps,
+                                   d_row_height, d_row_dt, d_fill):
+        """Device pointers; asynchronous on the context stream (include/mkidgpu.h
+        mkid_fill_photon_heights): the heights (and d_dt, nullable) of the packets that are not
+        deferred go to their slots of d_row_height (d_row_dt, nullable) float32 [n_seconds][C][K];
+        d_fill int64 [2] counts those found and those not."""
+        self._chk(self._L.mkid_fill_photon_heights(self._h, _ptr(d_events), _ptr(d_heights), _ptr(d_dt), int(n),
+                                                   int(j0), int(j_defer), int(n_seconds), int(K), _ptr(d_image),
+                                                   _ptr(d_stamps), _ptr(d_row_height), _ptr(d_row_dt), _ptr(d_fill)))
+
+    def fill_photon_heights_counted(self, d_events, d_heights, d_dt, d_count, cap, j0, j_defer, n_seconds, K, d_image,
+                                    d_stamps, d_row_height, d_row_dt, d_fill):
+        """As fill_photon_heights_device with the packet count read on the device."""
+        self._chk(self._L.mkid_fill_photon_heights_counted(self._h, _ptr(d_events), _ptr(d_heights), _ptr(d_dt),
+                                                           _ptr(d_count), int(cap), int(j0), int(j_defer),
+                                                           int(n_seconds), int(K), _ptr(d_image), _ptr(d_stamps),
+                                                           _ptr(d_row_height), _ptr(d_row_dt), _ptr(d_fill)))
+
     def height_spectra_device(self, d_events, d_heights, n, j0, j_defer, d_lo, d_inv, nbins, d_spectra,
                               d_deferred=None, cap_def=0, d_ndef=None):
         """Device pointers; asynchronous on the context stream (include/mkidgpu.h mkid_height_spectra):

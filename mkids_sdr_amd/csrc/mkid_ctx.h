@@ -224,6 +224,10 @@ struct mkid_ctx : CtxHandles {
     DevBuf<int32_t> d_obs_count;
     DevBuf<int64_t> d_obs_off;
     bool obs_lds = false;
+    // workspace of mkid_list_photons (lazy, grown on demand with the list's n or cap;
+    // mkid_internal.h photon_ws_bytes)
+    DevBuf<char> d_phws;
+    size_t phws_n = 0;
     // host-API staging (lazy)
     DevBuf<uint32_t> d_in;
     DevBuf<float> d_phase_ws;

@@ -233,6 +233,47 @@ hipError_t launch_concat_packets(const uint64_t* a, const int64_t* d_na, int64_t
                                  const int64_t* d_nb, int64_t cap_b, uint64_t* out, int64_t cap_out, int64_t* nout,
                                  int32_t ncu, hipStream_t s);
 
+// mkid_list_photons and mkid_fill_photon_heights (k_photons.hip). The list call runs over slices
+// planned as the spectra's (plan_photons: at most kObsMaxBlocks of about kObsSlice packets) and
+// keeps, per packet, the index of the first packet of its run, and per run (at its head's index)
+// the cell's count before the run: photon_ws_bytes(n) of workspace, carved as below.
+struct PhotonArgs {
+    const uint64_t* events;  // [n] wide packets
+    const int64_t* d_n;      // nullable: device packet count (min(*d_n, n) packets are read)
+    int32_t* image;          // [n_seconds][C]
+    int64_t* outside;        // [2]
+    uint64_t* words;         // [n_seconds][C][K]
+    int64_t* stamps;         // [n_seconds][C][K]
+    int64_t* dropped;        // [1]
+    int64_t* head;           // workspace [n]: index of the first packet of packet i's run
+    int64_t* carry;          // workspace [kObsMaxBlocks]: last run head of a slice, then of the slices before it
+    uint32_t* base;          // workspace [n]: at a run head's index, the cell's count before the run
+    int64_t n, j0, N, fs, slice;
+    int32_t C, n_seconds, K, layout;
+};
+inline size_t photon_ws_bytes(int64_t n) { return (size_t)n * 12 + (size_t)kObsMaxBlocks * 8; }
+inline void photon_ws_carve(PhotonArgs& a, char* ws) {
+    a.head = reinterpret_cast<int64_t*>(ws);
+    a.carry = a.head + a.n;
+    a.base = reinterpret_cast<uint32_t*>(a.carry + kObsMaxBlocks);
+}
+ObsPlan plan_photons(int64_t n);
+hipError_t launch_list_photons(const PhotonArgs& a, const ObsPlan& p, hipStream_t s);
+struct PhotonFillArgs {
+    const uint64_t* events;  // [n] wide packets
+    const float* heights;    // [n]
+    const float* dt;         // nullable [n]
+    const int64_t* d_n;      // nullable: device packet count
+    const int32_t* image;    // [n_seconds][C]
+    const int64_t* stamps;   // [n_seconds][C][K]
+    float* row_height;       // [n_seconds][C][K]
+    float* row_dt;           // nullable, the same shape
+    int64_t* fill;           // [2] {found, not found}
+    int64_t n, j0, j_defer, N, fs;
+    int32_t C, n_seconds, K, ncu;
+};
+hipError_t launch_fill_photon_heights(const PhotonFillArgs& a, hipStream_t s);
+
 // Pulse capture (k_capture.hip; the contract is in its header comment)
 struct CaptureArgs {
     const float* phase;      // [rows][C] rad, global phase rows j0 .. j0 + rows - 1

@@ -1,7 +1,8 @@
 // C ABI of libmkidgpu.so (include/mkidgpu.h): the observing products after the heights — the
 // per-second count image, the per-channel pulse-height spectra with the list of packets that still
-// wait for their height, joining two counted lists, and the host twins of the first two. The rules
-// are obs_common.h; the kernels k_observe.hip.
+// wait for their height, joining two counted lists, the per-pixel, per-second photon rows and the
+// heights filled into them, and the host twins of all but the join. The rules are obs_common.h; the
+// kernels k_observe.hip and k_photons.hip.
 #include "mkid_ctx.h"
 #include "obs_common.h"
 
@@ -85,7 +86,108 @@ int mkid_concat_packets(mkid_ctx* c, const uint64_t* d_a, const int64_t* d_na, i
     return MKID_OK;
 }
 
+static int list_photons(mkid_ctx* c, const uint64_t* d_events, const int64_t* d_n, int64_t n, int64_t j0,
+                        int32_t n_seconds, int32_t K, int32_t layout, int32_t* d_image, int64_t* d_outside,
+                        uint64_t* d_words, int64_t* d_stamps, int64_t* d_dropped) {
+    if (!c) return MKID_E_ARG;
+    if (!obs::list_args_ok(d_events, n, j0, c->N, c->cfg.sample_rate, c->C, n_seconds, K, layout, d_image, d_outside,
+                           d_words, d_stamps, d_dropped))
+        FAIL(c, MKID_E_ARG,
+             "list photons: need pointers, n, j0 >= 0 (j0 N inside int64), 1 <= n_seconds <= 2^20, 1 <= K <= 65536, "
+             "a known layout (REFERENCE: C <= 254), an integer sample rate <= 2^43");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n == 0) return MKID_OK;
+    const size_t bytes = photon_ws_bytes(n);
+    if (bytes > c->phws_n) {   // grow the workspace
+        DevBuf<char> ws;
+        HIPCHK(c, ws.alloc(bytes));
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // an earlier call may still use the old one
+        c->d_phws = std::move(ws), c->phws_n = bytes;
+    }
+    PhotonArgs a{};
+    a.events = d_events, a.d_n = d_n, a.image = d_image, a.outside = d_outside, a.words = d_words, a.stamps = d_stamps;
+    a.dropped = d_dropped, a.n = n, a.j0 = j0, a.N = c->N, a.fs = (int64_t)c->cfg.sample_rate;
+    a.C = c->C, a.n_seconds = n_seconds, a.K = K, a.layout = layout;
+    photon_ws_carve(a, c->d_phws.get());
+    HIPCHK(c, launch_list_photons(a, plan_photons(n), c->stream));
+    return MKID_OK;
+}
+
+int mkid_list_photons(mkid_ctx* c, const uint64_t* d_events, int64_t n, int64_t j0, int32_t n_seconds, int32_t K,
+                      int32_t layout, int32_t* d_image, int64_t* d_outside, uint64_t* d_words, int64_t* d_stamps,
+                      int64_t* d_dropped) {
+    return list_photons(c, d_events, nullptr, n, j0, n_seconds, K, layout, d_image, d_outside, d_words, d_stamps,
+                        d_dropped);
+}
+
+int mkid_list_photons_counted(mkid_ctx* c, const uint64_t* d_events, const int64_t* d_count, int64_t cap, int64_t j0,
+                              int32_t n_seconds, int32_t K, int32_t layout, int32_t* d_image, int64_t* d_outside,
+                              uint64_t* d_words, int64_t* d_stamps, int64_t* d_dropped) {
+    if (!d_count) return MKID_E_ARG;
+    return list_photons(c, d_events, d_count, cap, j0, n_seconds, K, layout, d_image, d_outside, d_words, d_stamps,
+                        d_dropped);
+}
+
+static int fill_photon_heights(mkid_ctx* c, const uint64_t* d_events, const float* d_heights, const float* d_dt,
+                               const int64_t* d_n, int64_t n, int64_t j0, int64_t j_defer, int32_t n_seconds, int32_t K,
+                               const int32_t* d_image, const int64_t* d_stamps, float* d_row_height, float* d_row_dt,
+                               int64_t* d_fill) {
+    if (!c) return MKID_E_ARG;
+    if (!obs::fill_args_ok(d_events, d_heights, n, j0, c->N, c->cfg.sample_rate, c->C, n_seconds, K, d_image, d_stamps,
+                           d_row_height, d_fill))
+        FAIL(c, MKID_E_ARG,
+             "fill photon heights: need pointers, n, j0 >= 0 (j0 N inside int64), 1 <= n_seconds <= 2^20, "
+             "1 <= K <= 65536, an integer sample rate <= 2^43");
+    HIPCHK(c, hipSetDevice(c->device));
+    PhotonFillArgs a{};
+    a.events = d_events, a.heights = d_heights, a.dt = d_dt, a.d_n = d_n, a.image = d_image, a.stamps = d_stamps;
+    a.row_height = d_row_height, a.row_dt = d_row_dt, a.fill = d_fill;
+    a.n = n, a.j0 = j0, a.j_defer = j_defer, a.N = c->N, a.fs = (int64_t)c->cfg.sample_rate;
+    a.C = c->C, a.n_seconds = n_seconds, a.K = K, a.ncu = c->ncu;
+    HIPCHK(c, launch_fill_photon_heights(a, c->stream));
+    return MKID_OK;
+}
+
+int mkid_fill_photon_heights(mkid_ctx* c, const uint64_t* d_events, const float* d_heights, const float* d_dt, int64_t n,
+                             int64_t j0, int64_t j_defer, int32_t n_seconds, int32_t K, const int32_t* d_image,
+                             const int64_t* d_stamps, float* d_row_height, float* d_row_dt, int64_t* d_fill) {
+    return fill_photon_heights(c, d_events, d_heights, d_dt, nullptr, n, j0, j_defer, n_seconds, K, d_image, d_stamps,
+                               d_row_height, d_row_dt, d_fill);
+}
+
+int mkid_fill_photon_heights_counted(mkid_ctx* c, const uint64_t* d_events, const float* d_heights, const float* d_dt,
+                                     const int64_t* d_count, int64_t cap, int64_t j0, int64_t j_defer, int32_t n_seconds,
+                                     int32_t K, const int32_t* d_image, const int64_t* d_stamps, float* d_row_height,
+                                     float* d_row_dt, int64_t* d_fill) {
+    if (!d_count) return MKID_E_ARG;
+    return fill_photon_heights(c, d_events, d_heights, d_dt, d_count, cap, j0, j_defer, n_seconds, K, d_image, d_stamps,
+                               d_row_height, d_row_dt, d_fill);
+}
+
 // The CPU statements of the device calls: the loops of obs_common.h.
+int mkid_list_photons_host(const uint64_t* events, int64_t n, int64_t j0, int32_t fft_len, double sample_rate,
+                           int32_t n_channels, int32_t n_seconds, int32_t K, int32_t layout, int32_t* image,
+                           int64_t* outside, uint64_t* words, int64_t* stamps, int64_t* dropped) {
+    if (!obs::list_args_ok(events, n, j0, fft_len, sample_rate, n_channels, n_seconds, K, layout, image, outside, words,
+                           stamps, dropped))
+        return MKID_E_ARG;
+    obs::list_host(events, n, j0, fft_len, sample_rate, n_channels, n_seconds, K, layout, image, outside, words, stamps,
+                   dropped);
+    return MKID_OK;
+}
+
+int mkid_fill_photon_heights_host(const uint64_t* events, const float* heights, const float* dt, int64_t n, int64_t j0,
+                                  int64_t j_defer, int32_t fft_len, double sample_rate, int32_t n_channels,
+                                  int32_t n_seconds, int32_t K, const int32_t* image, const int64_t* stamps,
+                                  float* row_height, float* row_dt, int64_t* fill) {
+    if (!obs::fill_args_ok(events, heights, n, j0, fft_len, sample_rate, n_channels, n_seconds, K, image, stamps,
+                           row_height, fill))
+        return MKID_E_ARG;
+    obs::fill_host(events, heights, dt, n, j0, j_defer, fft_len, sample_rate, n_channels, n_seconds, K, image, stamps,
+                   row_height, row_dt, fill);
+    return MKID_OK;
+}
+
 int mkid_count_photons_host(const uint64_t* events, int64_t n, int64_t j0, int32_t fft_len, double sample_rate,
                             int32_t n_channels, int32_t n_seconds, int32_t* image, int64_t* outside) {
     if (!obs::count_args_ok(events, n, j0, fft_len, sample_rate, n_channels, n_seconds, image, outside))

@@ -2,8 +2,9 @@
 // mkid_height_spectra state them), one definition for the kernels of k_observe.hip and for the host
 // entry points mkid_count_photons_host / mkid_height_spectra_host: the second of a packet on the
 // 1 PPS timebase (packets.Timebase.second), where a packet is counted, the spectrum column of a
-// height, and which packets wait for their height. A packet's channel and unwrapped stamp are
-// fit::decode's. The host loops below are the whole of the host entry points, so that the CPU
+// height, and which packets wait for their height; and, further down, the photon rows of
+// mkid_list_photons / mkid_fill_photon_heights (k_photons.hip) with their host entry points. A
+// packet's channel and unwrapped stamp are fit::decode's. The host loops below are the whole of the host entry points, so that the CPU
 // sanitizer build (tools/plan_fuzz.cpp) runs them without HIP.
 #pragma once
 #include <stdint.h>
@@ -100,6 +101,105 @@ inline void spectra_host(const uint64_t* events, const float* heights, int64_t n
             continue;
         }
         ++spectra[(int64_t)st.ch * (nbins + kExtraCols) + column(heights[p], lo[st.ch], inv[st.ch], nbins)];
+    }
+}
+
+// ---- the per-pixel, per-second photon rows (mkid_list_photons, mkid_fill_photon_heights) ---------
+// PacketMaster's /r#/p#/t<obs> table (PacketMaster.c:371-381, 978-1050) as [n_seconds][C][K]: the
+// packets of cell (sec, ch) take slots in arrival order from the cell's count before the call, a
+// packet whose slot is >= K is dropped (the reference's "first K kept", K = 2499 there).
+constexpr int32_t kMaxRowSlots = 65536;
+OBS_HD bool row_slots_ok(int32_t K) { return K >= 1 && K <= kMaxRowSlots; }
+OBS_HD bool layout_ok(int32_t layout) { return layout == MKID_ROW_WIDE || layout == MKID_ROW_REFERENCE; }
+// (fs - 1) 10^6 stays inside int64 for fs <= 2^43
+OBS_HD bool fs_us_ok(double fs) { return fs_ok(fs) && fs <= 8796093022208.0; }
+// the reference word's 8-bit channel field, 255 being the end-of-second marker
+OBS_HD bool layout_fits(int32_t layout, int32_t C) { return layout != MKID_ROW_REFERENCE || C <= 254; }
+
+// Microsecond since PPS of phase row jg (packets.Timebase.microsecond).
+OBS_HD int64_t microsecond(int64_t jg, int64_t N, int64_t fs) { return jg * N % fs * 1000000 / fs; }
+
+// The word stored for wide packet w at microsecond us: the packet with its time field replaced
+// (packets.encode_wire wide), or the reference's fields (packets.encode_wire; p1 as
+// mkid_pack_reference).
+OBS_HD uint64_t row_word(uint64_t w, int64_t us, int32_t layout) {
+    if (layout == MKID_ROW_WIDE) return (w & ~(uint64_t)MKID_PKT_TS_MASK) | (uint64_t)us;
+    const uint64_t ch = (w >> MKID_PKT_CH_SHIFT) & 0xFFF;
+    const int64_t peak = (int64_t)((w >> MKID_PKT_PEAK_SHIFT) & 0xFFF), base = (int64_t)((w >> MKID_PKT_BASE_SHIFT) & 0xFFF);
+    const int64_t d = peak - base + 2048;
+    const uint64_t p1 = (uint64_t)(d < 0 ? 0 : (d > 4095 ? 4095 : d));
+    return ch << 56 | (uint64_t)peak << 44 | p1 << 32 | (uint64_t)base << 20 | ((uint64_t)us & 0xFFFFF);
+}
+
+// Slots of a row that hold a packet, from the cell's count (modulo 2^32, as the image is kept).
+OBS_HD int64_t row_fill(int32_t count, int32_t K) { return (uint32_t)count < (uint32_t)K ? (int64_t)(uint32_t)count : K; }
+
+// Index of stamp jg in the ascending stamps[0 .. m), or -1.
+OBS_HD int64_t find_stamp(const int64_t* stamps, int64_t m, int64_t jg) {
+    int64_t lo = 0, hi = m;
+    while (lo < hi) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (stamps[mid] < jg)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo < m && stamps[lo] == jg ? lo : -1;
+}
+
+inline bool list_args_ok(const uint64_t* events, int64_t n, int64_t j0, int32_t N, double fs, int32_t C,
+                         int32_t n_seconds, int32_t K, int32_t layout, const int32_t* image, const int64_t* outside,
+                         const uint64_t* words, const int64_t* stamps, const int64_t* dropped) {
+    return count_args_ok(events, n, j0, N, fs, C, n_seconds, image, outside) && words && stamps && dropped &&
+           row_slots_ok(K) && layout_ok(layout) && fs_us_ok(fs) && layout_fits(layout, C);
+}
+
+inline void list_host(const uint64_t* events, int64_t n, int64_t j0, int32_t N, double fs, int32_t C,
+                      int32_t n_seconds, int32_t K, int32_t layout, int32_t* image, int64_t* outside,
+                      uint64_t* words, int64_t* stamps, int64_t* dropped) {
+    for (int64_t p = 0; p < n; ++p) {
+        const fit::Stamp st = fit::decode(events[p], j0);
+        const int64_t k = cell(st, C, N, (int64_t)fs, n_seconds);
+        if (k < 0) {
+            ++outside[k == kNonPixel ? 0 : 1];
+            continue;
+        }
+        const uint32_t slot = (uint32_t)image[k];
+        image[k] = (int32_t)(slot + 1);
+        if (slot < (uint32_t)K) {
+            words[k * K + slot] = row_word(events[p], microsecond(st.jg, N, (int64_t)fs), layout);
+            stamps[k * K + slot] = st.jg;
+        } else {
+            ++dropped[0];
+        }
+    }
+}
+
+inline bool fill_args_ok(const uint64_t* events, const float* heights, int64_t n, int64_t j0, int32_t N, double fs,
+                         int32_t C, int32_t n_seconds, int32_t K, const int32_t* image, const int64_t* stamps,
+                         const float* row_height, const int64_t* fill) {
+    return image && stamps && row_height && fill && (n == 0 || (events && heights)) && n >= 0 && C >= 1 && C <= 4096 &&
+           seconds_ok(n_seconds) && row_slots_ok(K) && fs_us_ok(fs) && j0_ok(j0, N);
+}
+
+// A height (and dt) is copied as its 32-bit pattern: a NaN keeps its payload.
+OBS_HD void copy_bits(float* dst, const float* src) { __builtin_memcpy(dst, src, sizeof(float)); }
+
+inline void fill_host(const uint64_t* events, const float* heights, const float* dt, int64_t n, int64_t j0,
+                      int64_t j_defer, int32_t N, double fs, int32_t C, int32_t n_seconds, int32_t K,
+                      const int32_t* image, const int64_t* stamps, float* row_height, float* row_dt, int64_t* fill) {
+    for (int64_t p = 0; p < n; ++p) {
+        const fit::Stamp st = fit::decode(events[p], j0);
+        if (st.ch >= C || deferred(heights[p], st.jg, j_defer)) continue;
+        const int64_t k = cell(st, C, N, (int64_t)fs, n_seconds);
+        const int64_t at = k < 0 ? -1 : find_stamp(stamps + k * K, row_fill(image[k], K), st.jg);
+        if (at < 0) {
+            ++fill[1];
+            continue;
+        }
+        copy_bits(row_height + k * K + at, heights + p);
+        if (dt && row_dt) copy_bits(row_dt + k * K + at, dt + p);
+        ++fill[0];
     }
 }
 

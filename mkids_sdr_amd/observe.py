@@ -3,9 +3,15 @@
 spectra, for every channel at once and across calls, with the heights' deferral protocol
 (include/mkidgpu.h mkid_pulse_heights: the packets of a call's last rows get their height with the
 next call) run on the device too. A step enqueues five calls on the context's stream and makes no
-device-to-host copy and no synchronisation.
+device-to-host copy and no synchronisation. With photon_rows=K it also keeps the product itself:
+PacketMaster's per-pixel, per-second photon rows (/r#/p#/t<obs>, PacketMaster.c:978-1050), K slots a
+row, each photon with its height (and arrival offset) once the deferral protocol has settled it
+(include/mkidgpu.h mkid_list_photons, mkid_fill_photon_heights): six calls a step, still no
+synchronisation.
 """
 import numpy as np
+
+from . import _lib, packets
 
 
 def j_defer(j0, rows, ncoeff, pre, search=0):
@@ -28,9 +34,15 @@ class Observation:
     cap_deferred  capacity of the deferred lists: at least the packets of a call's last
                 ncoeff - pre + search rows
     debug       keep a host copy of every step's joined list and heights (synchronises each step)
+    photon_rows  None: no photon rows, and the calls of a step are exactly those above. K: rows of K
+                slots per pixel and second (PacketMaster keeps 2499), [n_seconds][C][K] words, stamps,
+                heights and arrival offsets on the device, the last two NaN until filled (the
+                offsets stay NaN without fit)
+    row_layout  _lib.ROW_WIDE (any C) or _lib.ROW_REFERENCE (packets.encode_wire's word, C <= 254)
     """
 
-    def __init__(self, chan, n_seconds, nbins, lo, step, cap, cap_deferred, fit=False, debug=False):
+    def __init__(self, chan, n_seconds, nbins, lo, step, cap, cap_deferred, fit=False, debug=False,
+                 photon_rows=None, row_layout=_lib.ROW_WIDE):
         import torch
         if chan.pulse_filter is None:
             raise ValueError('Observation: set the pulse filter first')
@@ -56,6 +68,16 @@ class Observation:
         self.d_join = z(max(self.cap_join, 1), torch.int64)
         self.d_njoin = z(2, torch.int64)
         self.d_heights = z(max(self.cap_join, 1), torch.float32)
+        self.K, self.row_layout = (None if photon_rows is None else int(photon_rows)), int(row_layout)
+        if self.K is not None:
+            if not 1 <= self.K <= 65536:
+                raise ValueError('Observation: photon_rows must be 1 .. 65536')
+            shape = (self.n_seconds, C, self.K)
+            self.d_words, self.d_stamps = z(shape, torch.int64), z(shape, torch.int64)
+            self.d_row_height = torch.full(shape, float('nan'), dtype=torch.float32, device=dev)
+            self.d_row_dt = torch.full(shape, float('nan'), dtype=torch.float32, device=dev)
+            self.d_dt = z(max(self.cap_join, 1), torch.float32) if self.fit else None
+            self.d_dropped, self.d_fill = z(1, torch.int64), z(2, torch.int64)
         self.cur = 0          # d_def[cur], d_ndef[cur]: the packets deferred by the last step
         self.steps = []       # debug: (joined uint64, heights float32, j0, j_defer) of every step
         torch.cuda.synchronize(dev)   # torch's stream made the buffers, the context's stream uses them
@@ -70,15 +92,27 @@ class Observation:
         ncoeff, pre = ch.pulse_filter
         L = ch.pulse_fit_search if self.fit else 0
         jd = j_defer(j0, rows, ncoeff, pre, L)
-        ch.count_photons_counted(d_events, d_n, self.cap, j0, self.n_seconds, self.d_image, self.d_outside)
+        if self.K is None:
+            ch.count_photons_counted(d_events, d_n, self.cap, j0, self.n_seconds, self.d_image, self.d_outside)
+        else:
+            ch.list_photons_counted(d_events, d_n, self.cap, j0, self.n_seconds, self.K, self.row_layout, self.d_image,
+                                    self.d_outside, self.d_words, self.d_stamps, self.d_dropped)
         ch.concat_packets(self.d_def[cur], self.d_ndef[cur][1:], self.cap_def, d_events, d_n, self.cap,
                           self.d_join, self.cap_join, self.d_njoin)
         d_nj = self.d_njoin[1:]
-        heights = ch.pulse_fit_counted if self.fit else ch.pulse_heights_counted
-        heights(d_phase, rows, j0, self.d_join, d_nj, self.cap_join, self.d_heights)
+        d_dt = self.d_dt if self.K is not None else None
+        if self.fit and d_dt is not None:
+            ch.pulse_fit_counted(d_phase, rows, j0, self.d_join, d_nj, self.cap_join, self.d_heights, d_dt)
+        else:
+            heights = ch.pulse_fit_counted if self.fit else ch.pulse_heights_counted
+            heights(d_phase, rows, j0, self.d_join, d_nj, self.cap_join, self.d_heights)
         ch.stream_copy(self.d_ndef[cur ^ 1], self.d_zero, 16)   # on the context's stream: no torch memset
         ch.height_spectra_counted(self.d_join, self.d_heights, d_nj, self.cap_join, j0, jd, self.d_lo, self.d_inv,
                                   self.nbins, self.d_spectra, self.d_def[cur ^ 1], self.cap_def, self.d_ndef[cur ^ 1])
+        if self.K is not None:
+            ch.fill_photon_heights_counted(self.d_join, self.d_heights, d_dt, d_nj, self.cap_join, j0, jd,
+                                           self.n_seconds, self.K, self.d_image, self.d_stamps, self.d_row_height,
+                                           self.d_row_dt, self.d_fill)
         self.cur = cur ^ 1
         if self.debug:
             import torch
@@ -125,3 +159,44 @@ class Observation:
         """uint64: the packets still deferred after the last step, in list order."""
         n = int(self.deferred_counts()[1])
         return self.d_def[self.cur][:n].cpu().numpy().view(np.uint64).copy()
+
+    # ---- photon rows (photon_rows=K) ------------------------------------------------------------
+    def _rows_on(self):
+        if self.K is None:
+            raise ValueError('Observation: made without photon_rows')
+
+    def photons(self, sec, ch):
+        """The photons stored for pixel ch in second sec, the first min(image, K) of that cell in
+        ascending stamp: dict(word uint64, stamp int64 (the unwrapped phase row), us int64
+        (microsecond since PPS), height float32, dt float32 (rows; NaN without fit)); a height is
+        NaN until the photon's window has completed."""
+        self._rows_on()
+        self._sync()
+        m = min(int(self.d_image[sec, ch].item()), self.K)
+        host = lambda t: t[sec, ch, :m].cpu().numpy()
+        stamp = host(self.d_stamps)
+        return dict(word=host(self.d_words).view(np.uint64), stamp=stamp,
+                    us=packets.Timebase(self.chan.cfg.sample_rate, self.chan.N).microsecond(stamp),
+                    height=host(self.d_row_height), dt=host(self.d_row_dt))
+
+    def rows(self, sec):
+        """Second sec as PacketMaster holds it (its rows[(r, p)][sec] for every pixel p): a list
+        of C uint64 arrays, pixel p's the first min(image, K) words of its row."""
+        self._rows_on()
+        self._sync()
+        m = np.minimum(self.d_image[sec].cpu().numpy(), self.K)
+        w = self.d_words[sec].cpu().numpy().view(np.uint64)
+        return [w[p, :m[p]].copy() for p in range(self.chan.C)]
+
+    def dropped(self):
+        """Packets that found their row full (PacketMaster stores none past its 2499th)."""
+        self._rows_on()
+        self._sync()
+        return int(self.d_dropped.item())
+
+    def fill_counts(self):
+        """int64 [2]: heights stored in a row; heights whose photon has no slot (its row was full,
+        or its second is past n_seconds)."""
+        self._rows_on()
+        self._sync()
+        return self.d_fill.cpu().numpy()

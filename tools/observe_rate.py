@@ -13,6 +13,9 @@ the worst case for the count kernel's runs and the spectra kernel's LDS rows).
   spectra_plain_*  the same kernel, one global atomic per packet (MKID_OBS_LDS=0)
   spectra_defer  the shipped form with a deferred list (the packets of the last ncoeff - pre rows wait)
   concat         mkid_concat_packets of 5000 + 690 000 packets
+  list_*         mkid_list_photons (k_photons.hip) into [3][C][--row-slots] rows: the call that replaces
+                 mkid_count_photons in a step that keeps the photon rows
+  fill_*         mkid_fill_photon_heights of the list in that order into the device-order rows
   host_route     what this replaces: device-to-host copy of list and heights, then the numpy restatement
                  (tests/observe_cases.py), wall clock
 
@@ -62,6 +65,7 @@ def main():
     ap.add_argument('--ncoeff', type=int, default=100)
     ap.add_argument('--pre', type=int, default=20)
     ap.add_argument('--nbins', type=int, default=256)
+    ap.add_argument('--row-slots', type=int, default=2499)      # PacketMaster's MAX_EVENTS_PER_SEC - 1
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     import torch
@@ -116,9 +120,37 @@ def main():
     paths += [('spectra_%s_%s' % (f, o), spec(f, o)) for o in ('dev', 'time') for f in ('lds', 'plain')]
     paths += [('spectra_defer', spec_defer),
               ('concat', lambda: ctx['default'].concat_packets(d_a, d_na, n_a, d_ev['dev'], d_nb, n, d_join, n + n_a, d_njoin))]
+
+    # the photon rows: mkid_list_photons in both orders, each into tables of its own whose image is
+    # zeroed before every call (outside the timed interval), so that every round fills the same slots;
+    # mkid_fill_photon_heights of both list orders into the rows the device-order list made
+    # (stamp-ascending rows are its precondition; the order of its own list is free)
+    import photon_cases as pc
+    K = args.row_slots
+    rows = {o: {k: z(shape, dt) for k, shape, dt in (('image', (n_seconds, C), torch.int32), ('outside', 2, torch.int64),
+                                                     ('words', (n_seconds, C, K), torch.int64),
+                                                     ('stamps', (n_seconds, C, K), torch.int64),
+                                                     ('dropped', 1, torch.int64))} for o in ev}
+    row_h = {o: torch.full((n_seconds, C, K), float('nan'), device='cuda') for o in ev}
+    d_fill = {o: z(2, torch.int64) for o in ev}
+
+    def rows_list(o):
+        r = rows[o]
+        return lambda: ctx['default'].list_photons_device(d_ev[o], n, 0, n_seconds, K, pc.WIDE, r['image'], r['outside'],
+                                                          r['words'], r['stamps'], r['dropped'])
+
+    def rows_fill(o):
+        r = rows['dev']
+        return lambda: ctx['default'].fill_photon_heights_device(d_ev[o], d_h[o], None, n, 0, j_defer, n_seconds, K,
+                                                                 r['image'], r['stamps'], row_h[o], None, d_fill[o])
+
+    paths += [('list_' + o, rows_list(o)) for o in ev] + [('fill_' + o, rows_fill(o)) for o in ev]
+    prep = {'list_' + o: rows[o]['image'].zero_ for o in ev}
     times = {name: [] for name, _ in paths}
     for rep in range(args.reps + 2):           # two warm-up rounds: code objects, clocks, caches
         for name, fn in paths:
+            if name in prep:
+                prep[name]()
             t = event_ms(s, fn)
             if rep >= 2:
                 times[name].append(t)
@@ -134,12 +166,36 @@ def main():
         ref_sp, _, _ = oc.spectra_ref(h_ev, h_h, 0, 0, C, lo, inv, nbins)
         host_t.append(((t1 - t0) * 1e3, (time.perf_counter() - t1) * 1e3))
     ref_dsp, ref_def, ref_ndef = oc.spectra_ref(h_ev, h_h, 0, j_defer, C, lo, inv, nbins, defer=True, cap_def=n)
-    for t in list(image.values()) + list(outside.values()) + list(spectra.values()) + [d_ndef]:
+    for t in list(image.values()) + list(outside.values()) + list(spectra.values()) + [d_ndef] + list(d_fill.values()) + \
+            [r[k] for r in rows.values() for k in ('image', 'outside', 'dropped')]:
         t.zero_()
+    for t in row_h.values():
+        t.fill_(float('nan'))
     torch.cuda.synchronize()
     for name, fn in paths[1:]:
-        fn()
+        if not name.startswith('fill_'):
+            fn()
+    for name, fn in paths[1:]:                 # the fills after both lists
+        if name.startswith('fill_'):
+            fn()
     torch.cuda.synchronize()
+    # the rows against the host twins (tests/photon_cases.py): bit for bit in the device's order; by
+    # stamp the counters, and every row as a set (K holds every cell here, or `dropped` would differ)
+    _, want = pc.list_host(h_ev, 0, N, fs, C, n_seconds, K, pc.WIDE)
+    assert pc.fill_host(h_ev, h_h, None, 0, j_defer, N, fs, C, want) == 0
+    live = np.arange(K) < np.minimum(want.image, K)[..., None]
+    got = {o: {k: t.cpu().numpy() for k, t in rows[o].items()} for o in ev}
+    counters = all(np.array_equal(got[o][k], getattr(want, k)) for o in ev for k in ('image', 'outside', 'dropped'))
+    by_row = lambda a: np.sort(np.where(live, a, np.iinfo(np.int64).max), axis=-1)
+    rows_check = dict(
+        rows_counters_equal_host=bool(counters),
+        rows_dev_equal_host=bool(np.array_equal(got['dev']['words'].view(np.uint64)[live], want.words[live]) and
+                                 np.array_equal(got['dev']['stamps'][live], want.stamps[live])),
+        rows_time_same_sets=bool(np.array_equal(by_row(got['time']['stamps']), by_row(want.stamps)) and
+                                 np.array_equal(by_row(got['time']['words']), by_row(want.words.view(np.int64)))),
+        fill_equal_host=bool(all(np.array_equal(row_h[o].cpu().numpy().view(np.uint32), want.height.view(np.uint32)) and
+                                 np.array_equal(d_fill[o].cpu().numpy(), want.fill) for o in ev)),
+        rows_dropped=int(want.dropped[0]), rows_filled=int(want.fill[0]), rows_not_found=int(want.fill[1]))
     nd = d_ndef.cpu().numpy()
     check = dict(
         images_equal_numpy=bool(all(np.array_equal(t.cpu().numpy(), ref_image) for t in image.values())),
@@ -152,6 +208,7 @@ def main():
                     d_njoin.cpu().tolist() == [n + n_a, n + n_a]),
         packets_in_image=int(ref_image.sum()), packets_late=int(ref_out[1]), no_height=int(ref_sp[:, nbins + 2].sum()),
         deferred=int(ref_ndef[0]), channels_with_packets=int((ref_sp.sum(axis=1) > 0).sum()))
+    check.update(rows_check)
     med = {name: float(np.median(t)) for name, t in times.items()}
     out = dict(tool='observe_rate', channels=C, rows=J, ncoeff=nco, pre=pre, packets=n, nbins=nbins, n_seconds=n_seconds,
                reps=args.reps)
@@ -162,7 +219,10 @@ def main():
         l, p = times['spectra_lds_' + o], times['spectra_plain_' + o]
         out['lds_over_plain_' + o] = round(med['spectra_lds_' + o] / med['spectra_plain_' + o], 3)
         out['lds_range_clear_of_plain_' + o] = bool(max(l) < min(p))
-    out['stage_over_heights'] = round((med['count_dev'] + med['concat'] + med['spectra_defer']) / med['heights'], 3)
+    out['row_slots'] = K
+    for o in ev:                               # the list call replaces the count call of a step
+        out['list_over_count_' + o] = round(med['list_' + o] / med['count_' + o], 3)
+    out['stage_over_heights'] =round((med['count_dev'] + med['concat'] + med['spectra_defer']) / med['heights'], 3)
     out['host_route_copy_ms'] = round(float(np.median([a for a, _ in host_t])), 2)
     out['host_route_numpy_ms'] = round(float(np.median([b for _, b in host_t])), 2)
     out['checks'] = check

@@ -4,11 +4,13 @@
 // device code relies on (include/mkidgpu.h); the slot-table writes are replayed into
 // buffers of exactly the planned size, so an undersized plan is an ASan heap overflow, not a
 // silent miscount (the ADVICE r02 scratch-sizing bug is that class).
-// fuzz_observe drives the observing rules and the host twins' loops (csrc/obs_common.h) likewise.
+// fuzz_observe and fuzz_photons drive the observing rules and the host twins' loops
+// (csrc/obs_common.h) likewise.
 //   plan_fuzz [iterations] [seed]
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <algorithm>
 #include <cmath>
@@ -743,6 +745,158 @@ static void fuzz_observe(int iters) {
           "spectra argument checks");
 }
 
+// The photon rows (obs_common.h list_host, fill_host) on random words, stamps near the 28-bit wrap,
+// K = 1, overflowing rows and fs edge values, against a per-packet dictionary; the tables are
+// buffers of exactly the documented sizes, so a slot or cell outside them is an ASan report.
+static void fuzz_photons(int iters) {
+    namespace obs = mkid::obs;
+    CHECK(obs::fs_us_ok(8796093022208.0) && !obs::fs_us_ok(8796093022209.0) && !obs::fs_us_ok(1e6 + 0.5) && obs::fs_us_ok(1.0),
+          "fs_us_ok");
+    CHECK(obs::microsecond(0, 1, 8796093022208) == 0 && obs::microsecond(8796093022207, 1, 8796093022208) == 999999 &&
+              obs::microsecond(3, 128, 1000000) == 384 && obs::microsecond(7813, 128, 1000000) == 64,
+          "microsecond fixed points");
+    CHECK(obs::row_word(((uint64_t)3 << 52) | ((uint64_t)1500 << 40) | ((uint64_t)1900 << 28) | 77, 123456, MKID_ROW_WIDE) ==
+                  (((uint64_t)3 << 52) | ((uint64_t)1500 << 40) | ((uint64_t)1900 << 28) | 123456) &&
+              obs::row_word(((uint64_t)3 << 52) | ((uint64_t)1500 << 40) | ((uint64_t)1900 << 28) | 77, 123456, MKID_ROW_REFERENCE) ==
+                  (((uint64_t)3 << 56) | ((uint64_t)1500 << 44) | ((uint64_t)1648 << 32) | ((uint64_t)1900 << 20) | 123456),
+          "row word fixed points");
+    for (int it = 0; it < iters; ++it) {
+        const int32_t C = (int32_t)rint_(1, 40), N = (int32_t)(1 << rint_(0, 12));
+        const int32_t n_seconds = (int32_t)rint_(1, 4), K = (int32_t)(rint_(0, 2) ? rint_(1, 6) : 1);
+        const int32_t layout = (int32_t)rint_(0, 1);
+        const int64_t edge = rint_(0, 5);
+        // 1 .. 300 rows per second, or the clock's edges: fs = 1, fs = 2^43 (there a second is 2^43 / N rows)
+        const int64_t fs = edge == 0 ? 1 : edge == 1 ? (int64_t)1 << 43 : (int64_t)N * rint_(1, 300);
+        const int64_t wrap = (int64_t)1 << 28;
+        const int64_t j0 = rint_(0, 2) ? rint_(0, 3) * wrap + rint_(-40, 40) + (rint_(0, 1) ? wrap / 2 : 0) : rint_(0, 2000);
+        const int64_t j0c = j0 < 0 ? 0 : j0, n = rint_(0, 400);
+        const int64_t base = j0c > wrap / 2 ? j0c - wrap / 2 : 0;
+        std::vector<uint64_t> ev((size_t)n);
+        std::vector<int64_t> jgs((size_t)n);
+        for (int64_t p = 0; p < n; ++p) {
+            const uint64_t ch = rint_(0, 7) ? (uint64_t)rint_(0, C - 1) : (uint64_t)rint_(0, 4095);
+            int64_t jg = j0c + rint_(-30, 900);
+            if (jg < base) jg = base;
+            jgs[(size_t)p] = jg;
+            ev[(size_t)p] = (ch << MKID_PKT_CH_SHIFT) | ((uint64_t)rint_(0, (1 << 24) - 1) << MKID_PKT_BASE_SHIFT) |
+                            ((uint64_t)jg & MKID_PKT_TS_MASK);
+        }
+        const size_t cells = (size_t)n_seconds * C, slots = cells * K;
+        std::vector<int32_t> image(cells, 0), ref_image(cells, 0);
+        std::vector<uint64_t> words(slots, 0x5A5A), ref_words(slots, 0x5A5A);
+        std::vector<int64_t> stamps(slots, -7), ref_stamps(slots, -7);
+        int64_t outside[2] = {0, 0}, ref_outside[2] = {0, 0}, dropped = 0, ref_dropped = 0;
+        CHECK(obs::list_args_ok(ev.data(), n, j0c, N, (double)fs, C, n_seconds, K, layout, image.data(), outside, words.data(),
+                                stamps.data(), &dropped),
+              "list args");
+        // three calls over the thirds: the tables continue
+        const int64_t cut[4] = {0, n / 3, 2 * n / 3, n};
+        for (int k = 0; k < 3; ++k)
+            obs::list_host(ev.data() + cut[k], cut[k + 1] - cut[k], j0c, N, (double)fs, C, n_seconds, K, layout, image.data(),
+                           outside, words.data(), stamps.data(), &dropped);
+        std::vector<std::vector<std::pair<uint64_t, int64_t>>> dict(cells);
+        for (int64_t p = 0; p < n; ++p) {
+            const uint64_t w = ev[(size_t)p];
+            const int64_t ch = (int64_t)(w >> 52), jg = jgs[(size_t)p];
+            CHECK(mkid::fit::decode(w, j0c).jg == jg, "decode near the wrap");
+            if (ch >= C) {
+                ++ref_outside[0];
+                continue;
+            }
+            const __int128 sample = (__int128)jg * N;
+            const int64_t sec = (int64_t)(sample / fs), us = (int64_t)((sample % fs) * 1000000 / fs);
+            CHECK(us == obs::microsecond(jg, N, fs) && us >= 0 && us < 1000000, "microsecond %lld", (long long)us);
+            if (sec >= n_seconds) {
+                ++ref_outside[1];
+                continue;
+            }
+            const uint64_t peak = (w >> 40) & 0xFFF, bs = (w >> 28) & 0xFFF;
+            const int64_t d = (int64_t)peak - (int64_t)bs + 2048;
+            const uint64_t p1 = (uint64_t)std::min<int64_t>(std::max<int64_t>(d, 0), 4095);
+            const uint64_t word = layout == MKID_ROW_WIDE
+                                      ? ((uint64_t)ch << 52 | peak << 40 | bs << 28 | (uint64_t)us)
+                                      : ((uint64_t)ch << 56 | peak << 44 | p1 << 32 | bs << 20 | ((uint64_t)us & 0xFFFFF));
+            dict[(size_t)(sec * C + ch)].push_back({word, jg});
+        }
+        for (size_t k = 0; k < cells; ++k) {
+            ref_image[k] = (int32_t)dict[k].size();
+            for (size_t s = 0; s < dict[k].size(); ++s) {
+                if (s < (size_t)K)
+                    ref_words[k * K + s] = dict[k][s].first, ref_stamps[k * K + s] = dict[k][s].second;
+                else
+                    ++ref_dropped;
+            }
+        }
+        CHECK(image == ref_image && outside[0] == ref_outside[0] && outside[1] == ref_outside[1], "rows: image");
+        CHECK(words == ref_words && stamps == ref_stamps && dropped == ref_dropped, "rows: words, stamps, dropped");
+        // fill: rows made stamp-ascending with distinct stamps first, as the device's order gives them
+        for (size_t k = 0; k < cells; ++k) {
+            const int64_t m = obs::row_fill(image[k], K);
+            CHECK(m == std::min<int64_t>((int64_t)dict[k].size(), K), "row_fill");
+            std::sort(stamps.begin() + (int64_t)(k * K), stamps.begin() + (int64_t)(k * K) + m);
+            for (int64_t s = 1; s < m; ++s)
+                if (stamps[k * K + s] <= stamps[k * K + s - 1]) stamps[k * K + s] = stamps[k * K + s - 1] + 1;
+        }
+        const bool with_dt = rint_(0, 1) != 0;
+        const int64_t j_defer = j0c + rint_(-10, 900);
+        std::vector<float> h((size_t)n), dt((size_t)n), row_h(slots, NAN), row_dt(slots, NAN), ref_h(slots, NAN), ref_dt(slots, NAN);
+        const float specials[] = {NAN, INFINITY, -INFINITY, -0.0f, 0.0f};
+        for (int64_t p = 0; p < n; ++p) {
+            h[(size_t)p] = rint_(0, 3) ? (float)rint_(-2000, 2000) / 100.f : specials[rint_(0, 4)];
+            dt[(size_t)p] = (float)rint_(-300, 300) / 100.f;
+        }
+        int64_t fill[2] = {0, 0}, ref_fill[2] = {0, 0};
+        CHECK(obs::fill_args_ok(ev.data(), h.data(), n, j0c, N, (double)fs, C, n_seconds, K, image.data(), stamps.data(),
+                                row_h.data(), fill),
+              "fill args");
+        obs::fill_host(ev.data(), h.data(), with_dt ? dt.data() : nullptr, n, j0c, j_defer, N, (double)fs, C, n_seconds, K,
+                       image.data(), stamps.data(), row_h.data(), row_dt.data(), fill);
+        for (int64_t p = 0; p < n; ++p) {
+            const int64_t ch = (int64_t)(ev[(size_t)p] >> 52), jg = jgs[(size_t)p];
+            if (ch >= C || (!std::isfinite(h[(size_t)p]) && jg >= j_defer)) continue;
+            const int64_t sec = (int64_t)((__int128)jg * N / fs);
+            int64_t at = -1;
+            if (sec < n_seconds) {
+                const size_t k = (size_t)(sec * C + ch);
+                for (int64_t s = 0; s < obs::row_fill(image[k], K); ++s)
+                    if (stamps[k * K + s] == jg) at = (int64_t)(k * K) + s;
+            }
+            if (at < 0) {
+                ++ref_fill[1];
+                continue;
+            }
+            ++ref_fill[0];
+            ref_h[(size_t)at] = h[(size_t)p];
+            if (with_dt) ref_dt[(size_t)at] = dt[(size_t)p];
+        }
+        CHECK(fill[0] == ref_fill[0] && fill[1] == ref_fill[1], "fill counters");
+        CHECK(memcmp(row_h.data(), ref_h.data(), slots * 4) == 0 && memcmp(row_dt.data(), ref_dt.data(), slots * 4) == 0,
+              "filled heights");
+    }
+    int32_t i4 = 0;
+    int64_t o2[2] = {0, 0}, s1 = 0;
+    uint64_t w1 = 0;
+    float f1 = 0.f;
+    CHECK(!obs::list_args_ok(&w1, 1, 0, 128, 1e6, 64, 1, 0, 0, &i4, o2, &w1, &s1, o2) &&
+              !obs::list_args_ok(&w1, 1, 0, 128, 1e6, 64, 1, 65537, 0, &i4, o2, &w1, &s1, o2) &&
+              !obs::list_args_ok(&w1, 1, 0, 128, 1e6, 64, 1, 1, 2, &i4, o2, &w1, &s1, o2) &&
+              !obs::list_args_ok(&w1, 1, 0, 128, 1e6, 255, 1, 1, MKID_ROW_REFERENCE, &i4, o2, &w1, &s1, o2) &&
+              !obs::list_args_ok(&w1, 1, 0, 128, 8796093022209.0, 64, 1, 1, 0, &i4, o2, &w1, &s1, o2) &&
+              !obs::list_args_ok(&w1, 1, 0, 128, 1e6, 64, 1, 1, 0, &i4, o2, nullptr, &s1, o2) &&
+              !obs::list_args_ok(&w1, 1, 0, 128, 1e6, 64, 1, 1, 0, &i4, o2, &w1, nullptr, o2) &&
+              !obs::list_args_ok(&w1, 1, 0, 128, 1e6, 64, 1, 1, 0, &i4, o2, &w1, &s1, nullptr) &&
+              obs::list_args_ok(nullptr, 0, 0, 128, 1e6, 254, 1, 65536, MKID_ROW_REFERENCE, &i4, o2, &w1, &s1, o2),
+          "list argument checks");
+    CHECK(!obs::fill_args_ok(&w1, nullptr, 1, 0, 128, 1e6, 64, 1, 1, &i4, &s1, &f1, o2) &&
+              !obs::fill_args_ok(&w1, &f1, 1, 0, 128, 1e6, 64, 1, 1, nullptr, &s1, &f1, o2) &&
+              !obs::fill_args_ok(&w1, &f1, 1, 0, 128, 1e6, 64, 1, 1, &i4, nullptr, &f1, o2) &&
+              !obs::fill_args_ok(&w1, &f1, 1, 0, 128, 1e6, 64, 1, 1, &i4, &s1, nullptr, o2) &&
+              !obs::fill_args_ok(&w1, &f1, 1, 0, 128, 1e6, 64, 1, 1, &i4, &s1, &f1, nullptr) &&
+              !obs::fill_args_ok(&w1, &f1, 1, 0, 128, 1e6, 64, 1, 0, &i4, &s1, &f1, o2) &&
+              obs::fill_args_ok(nullptr, nullptr, 0, 0, 128, 1e6, 64, 1, 1, &i4, &s1, &f1, o2),
+          "fill argument checks");
+}
+
 int main(int argc, char** argv) {
     const int iters = argc > 1 ? atoi(argv[1]) : 300;
     rng.seed(argc > 2 ? strtoull(argv[2], nullptr, 10) : 12345);
@@ -758,6 +912,7 @@ int main(int argc, char** argv) {
     fuzz_noise(iters / 10 + 1);
     fuzz_fit(iters);
     fuzz_observe(iters);
+    fuzz_photons(iters);
     if (failures) {
         fprintf(stderr, "%d failures\n", failures);
         return 1;
