@@ -530,6 +530,92 @@ int mkid_fill_photon_heights_host(const uint64_t* events, const float* heights, 
                                   const int64_t* stamps, float* row_height, float* row_dt /* nullable */,
                                   int64_t* fill);
 
+/* The photon list as a streaming product of bounded memory: PacketMaster hands every finished
+ * second to its writer and reuses the memory (PacketMaster.c:329-368, write_sec_data 978-1050).
+ * Here the tables are a ring of n_slots second slots, [n_slots][C][K], a settled second is packed
+ * into the reference's variable-length form on the device, and its slot is cleared for the second
+ * n_slots later. The rules have one definition, csrc/obs_common.h (ring_cell, pack_host,
+ * clear_host).
+ *
+ * mkid_list_photons_ring / mkid_fill_photon_heights_ring: the calls above with n_seconds replaced
+ * by the window (sec0, n_slots, sec_end). A packet with ch < C and second sec belongs to slot
+ * sec mod n_slots iff sec0 <= sec < min(sec0 + n_slots, sec_end); slot order, K, d_dropped, the
+ * word by `layout` and the stamp are unchanged. d_outside is int64[4] here:
+ *     [0] ch >= C            [1] sec >= sec_end (past the exposure)
+ *     [2] sec < sec0 (its second was already drained)
+ *     [3] sec0 + n_slots <= sec < sec_end (overrun: the ring is too short or was not drained)
+ * and the fill counts a packet of any of the last three kinds in d_fill[1]. With sec0 = 0 and
+ * n_slots = sec_end = n_seconds every output equals the plain call's bit for bit and
+ * d_outside[2 .. 3] stay 0. The caller moves sec0 past a second only after mkid_clear_second of it.
+ * MKID_E_ARG as for the plain calls, with, in place of n_seconds: n_slots outside 1 .. 2^20,
+ * sec0 < 0, sec0 > sec_end, or sec_end so large that (sec_end + 1) sample_rate leaves int64.
+ *
+ * mkid_pack_second: reads slot s = sec mod n_slots and writes none of the tables. With
+ * m_c = min(image[s][c] as uint32, K), the photons row c holds:
+ *     d_counts[c]   int32 [C]      image[s][c], the raw count (PacketMaster's image row)
+ *     d_offsets[c]  int64 [C + 1]  the exclusive prefix sum of m_c; d_offsets[C] is the total
+ *     entry i < m_c of row c of d_words, d_stamps, d_row_height and d_row_dt goes to index
+ *     d_offsets[c] + i of d_out_words, d_out_stamps, d_out_height and d_out_dt, bit for bit (NaN
+ *     payloads included), when that index is < cap_out
+ *     d_total       int64 [2]      {d_offsets[C], min(d_offsets[C], cap_out)}
+ * Output entries at or beyond d_total[1] are never written. d_out_stamps may be NULL (then so may
+ * d_stamps); d_out_dt may be NULL, and must be with a NULL d_row_dt; with cap_out = 0 the four
+ * outputs may be NULL. It also serves the unbounded tables (n_slots = n_seconds). One workgroup
+ * scans the C counts, then a wave copies each (channel, tile of 256 slots) that holds photons; no
+ * atomics, no workspace.
+ * mkid_clear_second: for every c the first m_c entries of row c of d_row_height (and of d_row_dt,
+ * nullable) get the bit pattern 0x7FC00000, the NaN the tables are pre-filled with; then
+ * image[s][c] = 0. Words, stamps and slots at or beyond m_c are not touched.
+ * MKID_E_ARG before any launch: sec < 0, n_slots outside 1 .. 2^20, K outside 1 .. 65536, a
+ * negative cap_out, a null d_image, d_words, d_row_height, d_counts, d_offsets or d_total, null
+ * d_out_words or d_out_height with cap_out > 0, d_out_stamps without d_stamps, d_out_dt without
+ * d_row_dt.
+ *
+ * Common to the six device calls: device pointers only; asynchronous on the context stream; no
+ * device-to-host copy and no synchronisation (the list's workspace as above). Not timed.
+ * The four _host twins: the same rules on host memory through the same definitions; the same
+ * MKID_E_ARG cases, and n_channels outside 1 .. 4096 or fft_len < 1. */
+int mkid_list_photons_ring(mkid_ctx* ctx, const uint64_t* d_events, int64_t n, int64_t j0, int64_t sec0,
+                           int32_t n_slots, int64_t sec_end, int32_t K, int32_t layout, int32_t* d_image,
+                           int64_t* d_outside, uint64_t* d_words, int64_t* d_stamps, int64_t* d_dropped);
+int mkid_list_photons_ring_counted(mkid_ctx* ctx, const uint64_t* d_events, const int64_t* d_count, int64_t cap,
+                                   int64_t j0, int64_t sec0, int32_t n_slots, int64_t sec_end, int32_t K,
+                                   int32_t layout, int32_t* d_image, int64_t* d_outside, uint64_t* d_words,
+                                   int64_t* d_stamps, int64_t* d_dropped);
+int mkid_fill_photon_heights_ring(mkid_ctx* ctx, const uint64_t* d_events, const float* d_heights,
+                                  const float* d_dt /* nullable */, int64_t n, int64_t j0, int64_t j_defer,
+                                  int64_t sec0, int32_t n_slots, int64_t sec_end, int32_t K, const int32_t* d_image,
+                                  const int64_t* d_stamps, float* d_row_height, float* d_row_dt /* nullable */,
+                                  int64_t* d_fill);
+int mkid_fill_photon_heights_ring_counted(mkid_ctx* ctx, const uint64_t* d_events, const float* d_heights,
+                                          const float* d_dt, const int64_t* d_count, int64_t cap, int64_t j0,
+                                          int64_t j_defer, int64_t sec0, int32_t n_slots, int64_t sec_end, int32_t K,
+                                          const int32_t* d_image, const int64_t* d_stamps, float* d_row_height,
+                                          float* d_row_dt, int64_t* d_fill);
+int mkid_pack_second(mkid_ctx* ctx, int64_t sec, int32_t n_slots, int32_t K, const int32_t* d_image,
+                     const uint64_t* d_words, const int64_t* d_stamps, const float* d_row_height,
+                     const float* d_row_dt /* nullable */, int64_t cap_out, int32_t* d_counts, int64_t* d_offsets,
+                     uint64_t* d_out_words, int64_t* d_out_stamps /* nullable */, float* d_out_height,
+                     float* d_out_dt /* nullable with d_row_dt */, int64_t* d_total);
+int mkid_clear_second(mkid_ctx* ctx, int64_t sec, int32_t n_slots, int32_t K, int32_t* d_image, float* d_row_height,
+                      float* d_row_dt /* nullable */);
+int mkid_list_photons_ring_host(const uint64_t* events, int64_t n, int64_t j0, int32_t fft_len, double sample_rate,
+                                int32_t n_channels, int64_t sec0, int32_t n_slots, int64_t sec_end, int32_t K,
+                                int32_t layout, int32_t* image, int64_t* outside, uint64_t* words, int64_t* stamps,
+                                int64_t* dropped);
+int mkid_fill_photon_heights_ring_host(const uint64_t* events, const float* heights, const float* dt /* nullable */,
+                                       int64_t n, int64_t j0, int64_t j_defer, int32_t fft_len, double sample_rate,
+                                       int32_t n_channels, int64_t sec0, int32_t n_slots, int64_t sec_end, int32_t K,
+                                       const int32_t* image, const int64_t* stamps, float* row_height,
+                                       float* row_dt /* nullable */, int64_t* fill);
+int mkid_pack_second_host(int64_t sec, int32_t n_slots, int32_t K, int32_t n_channels, const int32_t* image,
+                          const uint64_t* words, const int64_t* stamps, const float* row_height,
+                          const float* row_dt /* nullable */, int64_t cap_out, int32_t* counts, int64_t* offsets,
+                          uint64_t* out_words, int64_t* out_stamps /* nullable */, float* out_height,
+                          float* out_dt /* nullable with row_dt */, int64_t* total);
+int mkid_clear_second_host(int64_t sec, int32_t n_slots, int32_t K, int32_t n_channels, int32_t* image,
+                           float* row_height, float* row_dt /* nullable */);
+
 /* Pulse capture: the firmware-style capture block between the stream and the template analysis.
  * For every photon packet the phase window around its stamp is copied into a caller-owned,
  * per-channel record bank on the device, for all channels at once and across streamed calls (the

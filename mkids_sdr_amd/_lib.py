@@ -146,6 +146,17 @@ _SIGS = {
     'mkid_fill_photon_heights_counted': [P, P, P, P, P, I64, I64, I64, I32, I32, P, P, P, P, P],
     'mkid_list_photons_host': [P, I64, I64, I32, ctypes.c_double, I32, I32, I32, I32, P, P, P, P, P],
     'mkid_fill_photon_heights_host': [P, P, P, I64, I64, I64, I32, ctypes.c_double, I32, I32, I32, P, P, P, P, P],
+    'mkid_list_photons_ring': [P, P, I64, I64, I64, I32, I64, I32, I32, P, P, P, P, P],
+    'mkid_list_photons_ring_counted': [P, P, P, I64, I64, I64, I32, I64, I32, I32, P, P, P, P, P],
+    'mkid_fill_photon_heights_ring': [P, P, P, P, I64, I64, I64, I64, I32, I64, I32, P, P, P, P, P],
+    'mkid_fill_photon_heights_ring_counted': [P, P, P, P, P, I64, I64, I64, I64, I32, I64, I32, P, P, P, P, P],
+    'mkid_pack_second': [P, I64, I32, I32, P, P, P, P, P, I64, P, P, P, P, P, P, P],
+    'mkid_clear_second': [P, I64, I32, I32, P, P, P],
+    'mkid_list_photons_ring_host': [P, I64, I64, I32, ctypes.c_double, I32, I64, I32, I64, I32, I32, P, P, P, P, P],
+    'mkid_fill_photon_heights_ring_host': [P, P, P, I64, I64, I64, I32, ctypes.c_double, I32, I64, I32, I64, I32, P, P,
+                                           P, P, P],
+    'mkid_pack_second_host': [I64, I32, I32, I32, P, P, P, P, P, I64, P, P, P, P, P, P, P],
+    'mkid_clear_second_host': [I64, I32, I32, I32, P, P, P],
     'mkid_set_capture': [P, I32, I32, I32],
     'mkid_capture_pulses': [P, P, I64, I64, P, I64, P, P, P],
     'mkid_capture_pulses_counted': [P, P, I64, I64, P, P, I64, P, P, P],

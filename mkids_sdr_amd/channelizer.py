@@ -453,6 +453,58 @@ class Channelizer:
                                                            int(n_seconds), int(K), _ptr(d_image), _ptr(d_stamps),
                                                            _ptr(d_row_height), _ptr(d_row_dt), _ptr(d_fill)))
 
+    # ---- the ring of second slots (mkid_list_photons_ring .. mkid_clear_second) ------------------
+    def list_photons_ring_device(self, d_events, n, j0, sec0, n_slots, sec_end, K, layout, d_image, d_outside, d_words,
+                                 d_stamps, d_dropped):
+        """As list_photons_device into tables [n_slots][C][K]: second sec goes to slot sec mod n_slots
+        while sec0 <= sec < min(sec0 + n_slots, sec_end); d_outside is int64 [4] (include/mkidgpu.h
+        mkid_list_photons_ring)."""
+        self._chk(self._L.mkid_list_photons_ring(self._h, _ptr(d_events), int(n), int(j0), int(sec0), int(n_slots),
+                                                 int(sec_end), int(K), int(layout), _ptr(d_image), _ptr(d_outside),
+                                                 _ptr(d_words), _ptr(d_stamps), _ptr(d_dropped)))
+
+    def list_photons_ring_counted(self, d_events, d_count, cap, j0, sec0, n_slots, sec_end, K, layout, d_image,
+                                  d_outside, d_words, d_stamps, d_dropped):
+        """As list_photons_ring_device with the packet count read on the device."""
+        self._chk(self._L.mkid_list_photons_ring_counted(self._h, _ptr(d_events), _ptr(d_count), int(cap), int(j0),
+                                                         int(sec0), int(n_slots), int(sec_end), int(K), int(layout),
+                                                         _ptr(d_image), _ptr(d_outside), _ptr(d_words), _ptr(d_stamps),
+                                                         _ptr(d_dropped)))
+
+    def fill_photon_heights_ring_device(self, d_events, d_heights, d_dt, n, j0, j_defer, sec0, n_slots, sec_end, K,
+                                        d_image, d_stamps, d_row_height, d_row_dt, d_fill):
+        """As fill_photon_heights_device into the ring's tables (include/mkidgpu.h
+        mkid_fill_photon_heights_ring)."""
+        self._chk(self._L.mkid_fill_photon_heights_ring(self._h, _ptr(d_events), _ptr(d_heights), _ptr(d_dt), int(n),
+                                                        int(j0), int(j_defer), int(sec0), int(n_slots), int(sec_end),
+                                                        int(K), _ptr(d_image), _ptr(d_stamps), _ptr(d_row_height),
+                                                        _ptr(d_row_dt), _ptr(d_fill)))
+
+    def fill_photon_heights_ring_counted(self, d_events, d_heights, d_dt, d_count, cap, j0, j_defer, sec0, n_slots,
+                                         sec_end, K, d_image, d_stamps, d_row_height, d_row_dt, d_fill):
+        """As fill_photon_heights_ring_device with the packet count read on the device."""
+        self._chk(self._L.mkid_fill_photon_heights_ring_counted(self._h, _ptr(d_events), _ptr(d_heights), _ptr(d_dt),
+                                                                _ptr(d_count), int(cap), int(j0), int(j_defer),
+                                                                int(sec0), int(n_slots), int(sec_end), int(K),
+                                                                _ptr(d_image), _ptr(d_stamps), _ptr(d_row_height),
+                                                                _ptr(d_row_dt), _ptr(d_fill)))
+
+    def pack_second(self, sec, n_slots, K, d_image, d_words, d_stamps, d_row_height, d_row_dt, cap_out, d_counts,
+                    d_offsets, d_out_words, d_out_stamps, d_out_height, d_out_dt, d_total):
+        """Device pointers; asynchronous on the context stream (include/mkidgpu.h mkid_pack_second):
+        slot sec mod n_slots of the tables as d_counts int32 [C], d_offsets int64 [C + 1], the rows'
+        photons end to end in the four outputs (cut at cap_out) and d_total int64 [2]."""
+        self._chk(self._L.mkid_pack_second(self._h, int(sec), int(n_slots), int(K), _ptr(d_image), _ptr(d_words),
+                                           _ptr(d_stamps), _ptr(d_row_height), _ptr(d_row_dt), int(cap_out),
+                                           _ptr(d_counts), _ptr(d_offsets), _ptr(d_out_words), _ptr(d_out_stamps),
+                                           _ptr(d_out_height), _ptr(d_out_dt), _ptr(d_total)))
+
+    def clear_second(self, sec, n_slots, K, d_image, d_row_height, d_row_dt):
+        """Device pointers; asynchronous on the context stream (include/mkidgpu.h mkid_clear_second):
+        the filled heights (and dt) of slot sec mod n_slots back to NaN and its image row to 0."""
+        self._chk(self._L.mkid_clear_second(self._h, int(sec), int(n_slots), int(K), _ptr(d_image),
+                                            _ptr(d_row_height), _ptr(d_row_dt)))
+
     def height_spectra_device(self, d_events, d_heights, n, j0, j_defer, d_lo, d_inv, nbins, d_spectra,
                               d_deferred=None, cap_def=0, d_ndef=None):
         """Device pointers; asynchronous on the context stream (include/mkidgpu.h mkid_height_spectra):

@@ -21,6 +21,9 @@
 //             cell's row, the height (and dt) copied into the slot found; the two counters of a
 //             workgroup go out as one atomic each.
 // No workgroup waits for another inside a kernel, and no floating-point atomic is used.
+// The ring forms (mkid_list_photons_ring, mkid_fill_photon_heights_ring) are the same kernels built
+// with obs::ring_cell for the cell: a slot's cells are distinct inside the window, so a cell's
+// packets of a call are still one run, and each of the four `outside` kinds is a run of its own.
 #include "mkid_internal.h"
 #include "obs_common.h"
 
@@ -34,8 +37,23 @@ __device__ __forceinline__ int64_t ph_count(const int64_t* d_n, int64_t n) {
     return v < 0 ? 0 : (v < n ? v : n);
 }
 
-__device__ __forceinline__ int64_t ph_cell(const PhotonArgs& a, int64_t i) {
-    return obs::cell(fit::decode(a.events[i], a.j0), a.C, a.N, a.fs, a.n_seconds);
+// The cell of a decoded packet by the form's arguments: the plain forms', or the ring forms' with
+// the window (n_seconds holds n_slots there). Each kernel below is built once for each.
+__device__ __forceinline__ int64_t ph_cell_of(const PhotonArgs& a, const fit::Stamp& st) {
+    return obs::cell(st, a.C, a.N, a.fs, a.n_seconds);
+}
+__device__ __forceinline__ int64_t ph_cell_of(const PhotonRingArgs& a, const fit::Stamp& st) {
+    return obs::ring_cell(st, a.C, a.N, a.fs, obs::Window{a.sec0, a.sec_end, a.n_seconds});
+}
+__device__ __forceinline__ int64_t ph_cell_of(const PhotonFillArgs& a, const fit::Stamp& st) {
+    return obs::cell(st, a.C, a.N, a.fs, a.n_seconds);
+}
+__device__ __forceinline__ int64_t ph_cell_of(const PhotonFillRingArgs& a, const fit::Stamp& st) {
+    return obs::ring_cell(st, a.C, a.N, a.fs, obs::Window{a.sec0, a.sec_end, a.n_seconds});
+}
+template <class A>
+__device__ __forceinline__ int64_t ph_cell(const A& a, int64_t i) {
+    return ph_cell_of(a, fit::decode(a.events[i], a.j0));
 }
 
 ObsPlan plan_photons(int64_t n) {
@@ -47,7 +65,8 @@ ObsPlan plan_photons(int64_t n) {
     return p;
 }
 
-__global__ __launch_bounds__(kPhThreads) void k_ph_heads(PhotonArgs a) {
+template <class A>
+__global__ __launch_bounds__(kPhThreads) void k_ph_heads(A a) {
     __shared__ int64_t wlast[kPhThreads / 64];
     const int64_t n = ph_count(a.d_n, a.n);
     const int64_t b0 = (int64_t)blockIdx.x * a.slice;
@@ -98,7 +117,8 @@ __global__ __launch_bounds__(kObsMaxBlocks) void k_ph_scan(int64_t* carry, int32
     if (t < blocks) carry[t] = ex;
 }
 
-__global__ __launch_bounds__(kPhThreads) void k_ph_base(PhotonArgs a) {
+template <class A>
+__global__ __launch_bounds__(kPhThreads) void k_ph_base(A a) {
     const int64_t n = ph_count(a.d_n, a.n);
     const int64_t b0 = (int64_t)blockIdx.x * a.slice;
     const int64_t b1 = b0 + a.slice < n ? b0 + a.slice : n;
@@ -112,12 +132,12 @@ __global__ __launch_bounds__(kPhThreads) void k_ph_base(PhotonArgs a) {
         if (k >= 0)
             a.base[h] = atomicAdd(reinterpret_cast<unsigned int*>(a.image) + k, (unsigned int)len);
         else
-            atomicAdd(reinterpret_cast<unsigned long long*>(a.outside) + (k == obs::kNonPixel ? 0 : 1),
-                      (unsigned long long)len);
+            atomicAdd(reinterpret_cast<unsigned long long*>(a.outside) + (-1 - k), (unsigned long long)len);
     }
 }
 
-__global__ __launch_bounds__(kPhThreads) void k_ph_rows(PhotonArgs a) {
+template <class A>
+__global__ __launch_bounds__(kPhThreads) void k_ph_rows(A a) {
     __shared__ unsigned int s_drop;
     const int64_t n = ph_count(a.d_n, a.n);
     const int64_t b0 = (int64_t)blockIdx.x * a.slice;
@@ -128,7 +148,7 @@ __global__ __launch_bounds__(kPhThreads) void k_ph_rows(PhotonArgs a) {
     for (int64_t i = b0 + threadIdx.x; i < b1; i += kPhThreads) {
         const uint64_t word = a.events[i];
         const fit::Stamp st = fit::decode(word, a.j0);
-        const int64_t k = obs::cell(st, a.C, a.N, a.fs, a.n_seconds);
+        const int64_t k = ph_cell_of(a, st);
         if (k < 0) continue;
         const int64_t h = a.head[i];
         const uint32_t slot = a.base[h] + (uint32_t)(i - h);   // modulo 2^32, as the image counts
@@ -145,24 +165,31 @@ __global__ __launch_bounds__(kPhThreads) void k_ph_rows(PhotonArgs a) {
         atomicAdd(reinterpret_cast<unsigned long long*>(a.dropped), (unsigned long long)s_drop);
 }
 
-hipError_t launch_list_photons(const PhotonArgs& a0, const ObsPlan& p, hipStream_t s) {
+template <class A>
+static hipError_t launch_list(const A& a0, const ObsPlan& p, hipStream_t s) {
     if (a0.n <= 0) return hipSuccess;
-    PhotonArgs a = a0;
+    A a = a0;
     a.slice = p.slice;
     const dim3 grid((unsigned)p.blocks), wg(kPhThreads);
-    hipLaunchKernelGGL(k_ph_heads, grid, wg, 0, s, a);
+    hipLaunchKernelGGL(k_ph_heads<A>, grid, wg, 0, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_ph_scan, dim3(1), dim3(kObsMaxBlocks), 0, s, a.carry, p.blocks);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_ph_base, grid, wg, 0, s, a);
+    hipLaunchKernelGGL(k_ph_base<A>, grid, wg, 0, s, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_ph_rows, grid, wg, 0, s, a);
+    hipLaunchKernelGGL(k_ph_rows<A>, grid, wg, 0, s, a);
     return hipGetLastError();
 }
 
+hipError_t launch_list_photons(const PhotonArgs& a, const ObsPlan& p, hipStream_t s) { return launch_list(a, p, s); }
+hipError_t launch_list_photons_ring(const PhotonRingArgs& a, const ObsPlan& p, hipStream_t s) {
+    return launch_list(a, p, s);
+}
+
 // ---- heights into the rows ---------------------------------------------------------------------
-__global__ __launch_bounds__(kPhThreads) void k_ph_fill(PhotonFillArgs a) {
+template <class A>
+__global__ __launch_bounds__(kPhThreads) void k_ph_fill(A a) {
     __shared__ unsigned int s_fill[2];
     const int64_t n = ph_count(a.d_n, a.n);
     if (threadIdx.x < 2) s_fill[threadIdx.x] = 0;
@@ -172,7 +199,7 @@ __global__ __launch_bounds__(kPhThreads) void k_ph_fill(PhotonFillArgs a) {
     for (int64_t i = (int64_t)blockIdx.x * kPhThreads + threadIdx.x; i < n; i += stride) {
         const fit::Stamp st = fit::decode(a.events[i], a.j0);
         if (st.ch >= a.C || obs::deferred(a.heights[i], st.jg, a.j_defer)) continue;
-        const int64_t k = obs::cell(st, a.C, a.N, a.fs, a.n_seconds);
+        const int64_t k = ph_cell_of(a, st);
         const int64_t at = k < 0 ? -1 : obs::find_stamp(a.stamps + k * a.K, obs::row_fill(a.image[k], a.K), st.jg);
         if (at < 0) {
             ++missed;
@@ -189,11 +216,15 @@ __global__ __launch_bounds__(kPhThreads) void k_ph_fill(PhotonFillArgs a) {
         atomicAdd(reinterpret_cast<unsigned long long*>(a.fill) + threadIdx.x, (unsigned long long)s_fill[threadIdx.x]);
 }
 
-hipError_t launch_fill_photon_heights(const PhotonFillArgs& a, hipStream_t s) {
+template <class A>
+static hipError_t launch_fill(const A& a, hipStream_t s) {
     if (a.n <= 0) return hipSuccess;
     const int64_t need = (a.n + kPhThreads - 1) / kPhThreads, cap = (int64_t)(a.ncu > 0 ? a.ncu : 256) * 8;
-    hipLaunchKernelGGL(k_ph_fill, dim3((unsigned)(need < cap ? need : cap)), dim3(kPhThreads), 0, s, a);
+    hipLaunchKernelGGL(k_ph_fill<A>, dim3((unsigned)(need < cap ? need : cap)), dim3(kPhThreads), 0, s, a);
     return hipGetLastError();
 }
+
+hipError_t launch_fill_photon_heights(const PhotonFillArgs& a, hipStream_t s) { return launch_fill(a, s); }
+hipError_t launch_fill_photon_heights_ring(const PhotonFillRingArgs& a, hipStream_t s) { return launch_fill(a, s); }
 
 }  // namespace mkid

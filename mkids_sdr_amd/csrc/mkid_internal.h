@@ -257,8 +257,14 @@ inline void photon_ws_carve(PhotonArgs& a, char* ws) {
     a.carry = a.head + a.n;
     a.base = reinterpret_cast<uint32_t*>(a.carry + kObsMaxBlocks);
 }
+// the ring forms: the tables are [n_slots][C][K] with n_seconds holding n_slots, outside is [4]
+// (obs_common.h ring_cell); the plain forms keep the kernels without the window
+struct PhotonRingArgs : PhotonArgs {
+    int64_t sec0, sec_end;
+};
 ObsPlan plan_photons(int64_t n);
 hipError_t launch_list_photons(const PhotonArgs& a, const ObsPlan& p, hipStream_t s);
+hipError_t launch_list_photons_ring(const PhotonRingArgs& a, const ObsPlan& p, hipStream_t s);
 struct PhotonFillArgs {
     const uint64_t* events;  // [n] wide packets
     const float* heights;    // [n]
@@ -272,7 +278,40 @@ struct PhotonFillArgs {
     int64_t n, j0, j_defer, N, fs;
     int32_t C, n_seconds, K, ncu;
 };
+struct PhotonFillRingArgs : PhotonFillArgs {
+    int64_t sec0, sec_end;
+};
 hipError_t launch_fill_photon_heights(const PhotonFillArgs& a, hipStream_t s);
+hipError_t launch_fill_photon_heights_ring(const PhotonFillRingArgs& a, hipStream_t s);
+
+// mkid_pack_second and mkid_clear_second (k_pack.hip): slot sec mod n_slots of the [n_slots][C][K]
+// tables. A wave takes one (channel, tile of kPackTile slots) of the copy and of the clear.
+constexpr int kPackTile = 256;
+struct PackArgs {
+    const int32_t* image;      // [n_slots][C]
+    const uint64_t* words;     // [n_slots][C][K]
+    const int64_t* stamps;     // nullable without out_stamps
+    const float* row_height;
+    const float* row_dt;       // nullable without out_dt
+    int32_t* counts;           // [C]
+    int64_t* offsets;          // [C + 1]
+    uint64_t* out_words;       // [cap_out]
+    int64_t* out_stamps;       // nullable
+    float* out_height;
+    float* out_dt;             // nullable
+    int64_t* total;            // [2] {entries of the second, entries written}
+    int64_t row0, cap_out;     // row0 = (sec mod n_slots) C
+    int32_t C, K;
+};
+hipError_t launch_pack_second(const PackArgs& a, hipStream_t s);
+struct ClearArgs {
+    int32_t* image;
+    float* row_height;
+    float* row_dt;             // nullable
+    int64_t row0;
+    int32_t C, K;
+};
+hipError_t launch_clear_second(const ClearArgs& a, hipStream_t s);
 
 // Pulse capture (k_capture.hip; the contract is in its header comment)
 struct CaptureArgs {

@@ -1,8 +1,9 @@
 // C ABI of libmkidgpu.so (include/mkidgpu.h): the observing products after the heights — the
 // per-second count image, the per-channel pulse-height spectra with the list of packets that still
 // wait for their height, joining two counted lists, the per-pixel, per-second photon rows and the
-// heights filled into them, and the host twins of all but the join. The rules are obs_common.h; the
-// kernels k_observe.hip and k_photons.hip.
+// heights filled into them, their ring forms, a settled second packed out of its slot and the slot
+// cleared, and the host twins of all but the join. The rules are obs_common.h; the kernels
+// k_observe.hip, k_photons.hip and k_pack.hip.
 #include "mkid_ctx.h"
 #include "obs_common.h"
 
@@ -86,15 +87,23 @@ int mkid_concat_packets(mkid_ctx* c, const uint64_t* d_a, const int64_t* d_na, i
     return MKID_OK;
 }
 
+// The plain forms (w == nullptr: n_seconds, the kernels without the window) and the ring forms
+// (n_seconds holds n_slots) share everything but the argument check and the kernels' cell.
 static int list_photons(mkid_ctx* c, const uint64_t* d_events, const int64_t* d_n, int64_t n, int64_t j0,
-                        int32_t n_seconds, int32_t K, int32_t layout, int32_t* d_image, int64_t* d_outside,
-                        uint64_t* d_words, int64_t* d_stamps, int64_t* d_dropped) {
+                        int32_t n_seconds, const obs::Window* w, int32_t K, int32_t layout, int32_t* d_image,
+                        int64_t* d_outside, uint64_t* d_words, int64_t* d_stamps, int64_t* d_dropped) {
     if (!c) return MKID_E_ARG;
-    if (!obs::list_args_ok(d_events, n, j0, c->N, c->cfg.sample_rate, c->C, n_seconds, K, layout, d_image, d_outside,
-                           d_words, d_stamps, d_dropped))
+    if (!w && !obs::list_args_ok(d_events, n, j0, c->N, c->cfg.sample_rate, c->C, n_seconds, K, layout, d_image, d_outside,
+                                 d_words, d_stamps, d_dropped))
         FAIL(c, MKID_E_ARG,
              "list photons: need pointers, n, j0 >= 0 (j0 N inside int64), 1 <= n_seconds <= 2^20, 1 <= K <= 65536, "
              "a known layout (REFERENCE: C <= 254), an integer sample rate <= 2^43");
+    if (w && !obs::list_ring_args_ok(d_events, n, j0, c->N, c->cfg.sample_rate, c->C, *w, K, layout, d_image, d_outside,
+                                     d_words, d_stamps, d_dropped))
+        FAIL(c, MKID_E_ARG,
+             "list photons ring: need pointers, n, j0 >= 0 (j0 N inside int64), 1 <= n_slots <= 2^20, "
+             "0 <= sec0 <= sec_end ((sec_end + 1) sample_rate inside int64), 1 <= K <= 65536, a known layout "
+             "(REFERENCE: C <= 254), an integer sample rate <= 2^43");
     HIPCHK(c, hipSetDevice(c->device));
     if (n == 0) return MKID_OK;
     const size_t bytes = photon_ws_bytes(n);
@@ -104,55 +113,88 @@ static int list_photons(mkid_ctx* c, const uint64_t* d_events, const int64_t* d_
         HIPCHK(c, hipStreamSynchronize(c->stream));   // an earlier call may still use the old one
         c->d_phws = std::move(ws), c->phws_n = bytes;
     }
-    PhotonArgs a{};
+    PhotonRingArgs a{};
     a.events = d_events, a.d_n = d_n, a.image = d_image, a.outside = d_outside, a.words = d_words, a.stamps = d_stamps;
     a.dropped = d_dropped, a.n = n, a.j0 = j0, a.N = c->N, a.fs = (int64_t)c->cfg.sample_rate;
-    a.C = c->C, a.n_seconds = n_seconds, a.K = K, a.layout = layout;
+    a.C = c->C, a.n_seconds = w ? w->n_slots : n_seconds, a.K = K, a.layout = layout;
     photon_ws_carve(a, c->d_phws.get());
-    HIPCHK(c, launch_list_photons(a, plan_photons(n), c->stream));
+    if (w) {
+        a.sec0 = w->sec0, a.sec_end = w->sec_end;
+        HIPCHK(c, launch_list_photons_ring(a, plan_photons(n), c->stream));
+    } else {
+        HIPCHK(c, launch_list_photons(a, plan_photons(n), c->stream));
+    }
     return MKID_OK;
 }
 
 int mkid_list_photons(mkid_ctx* c, const uint64_t* d_events, int64_t n, int64_t j0, int32_t n_seconds, int32_t K,
                       int32_t layout, int32_t* d_image, int64_t* d_outside, uint64_t* d_words, int64_t* d_stamps,
                       int64_t* d_dropped) {
-    return list_photons(c, d_events, nullptr, n, j0, n_seconds, K, layout, d_image, d_outside, d_words, d_stamps,
-                        d_dropped);
+    return list_photons(c, d_events, nullptr, n, j0, n_seconds, nullptr, K, layout, d_image, d_outside, d_words,
+                        d_stamps, d_dropped);
 }
 
 int mkid_list_photons_counted(mkid_ctx* c, const uint64_t* d_events, const int64_t* d_count, int64_t cap, int64_t j0,
                               int32_t n_seconds, int32_t K, int32_t layout, int32_t* d_image, int64_t* d_outside,
                               uint64_t* d_words, int64_t* d_stamps, int64_t* d_dropped) {
     if (!d_count) return MKID_E_ARG;
-    return list_photons(c, d_events, d_count, cap, j0, n_seconds, K, layout, d_image, d_outside, d_words, d_stamps,
+    return list_photons(c, d_events, d_count, cap, j0, n_seconds, nullptr, K, layout, d_image, d_outside, d_words,
+                        d_stamps, d_dropped);
+}
+
+int mkid_list_photons_ring(mkid_ctx* c, const uint64_t* d_events, int64_t n, int64_t j0, int64_t sec0, int32_t n_slots,
+                           int64_t sec_end, int32_t K, int32_t layout, int32_t* d_image, int64_t* d_outside,
+                           uint64_t* d_words, int64_t* d_stamps, int64_t* d_dropped) {
+    const obs::Window w{sec0, sec_end, n_slots};
+    return list_photons(c, d_events, nullptr, n, j0, 0, &w, K, layout, d_image, d_outside, d_words, d_stamps, d_dropped);
+}
+
+int mkid_list_photons_ring_counted(mkid_ctx* c, const uint64_t* d_events, const int64_t* d_count, int64_t cap,
+                                   int64_t j0, int64_t sec0, int32_t n_slots, int64_t sec_end, int32_t K, int32_t layout,
+                                   int32_t* d_image, int64_t* d_outside, uint64_t* d_words, int64_t* d_stamps,
+                                   int64_t* d_dropped) {
+    if (!d_count) return MKID_E_ARG;
+    const obs::Window w{sec0, sec_end, n_slots};
+    return list_photons(c, d_events, d_count, cap, j0, 0, &w, K, layout, d_image, d_outside, d_words, d_stamps,
                         d_dropped);
 }
 
 static int fill_photon_heights(mkid_ctx* c, const uint64_t* d_events, const float* d_heights, const float* d_dt,
-                               const int64_t* d_n, int64_t n, int64_t j0, int64_t j_defer, int32_t n_seconds, int32_t K,
-                               const int32_t* d_image, const int64_t* d_stamps, float* d_row_height, float* d_row_dt,
-                               int64_t* d_fill) {
+                               const int64_t* d_n, int64_t n, int64_t j0, int64_t j_defer, int32_t n_seconds,
+                               const obs::Window* w, int32_t K, const int32_t* d_image, const int64_t* d_stamps,
+                               float* d_row_height, float* d_row_dt, int64_t* d_fill) {
     if (!c) return MKID_E_ARG;
-    if (!obs::fill_args_ok(d_events, d_heights, n, j0, c->N, c->cfg.sample_rate, c->C, n_seconds, K, d_image, d_stamps,
-                           d_row_height, d_fill))
+    if (!w && !obs::fill_args_ok(d_events, d_heights, n, j0, c->N, c->cfg.sample_rate, c->C, n_seconds, K, d_image,
+                                 d_stamps, d_row_height, d_fill))
         FAIL(c, MKID_E_ARG,
              "fill photon heights: need pointers, n, j0 >= 0 (j0 N inside int64), 1 <= n_seconds <= 2^20, "
              "1 <= K <= 65536, an integer sample rate <= 2^43");
+    if (w && !obs::fill_ring_args_ok(d_events, d_heights, n, j0, c->N, c->cfg.sample_rate, c->C, *w, K, d_image, d_stamps,
+                                     d_row_height, d_fill))
+        FAIL(c, MKID_E_ARG,
+             "fill photon heights ring: need pointers, n, j0 >= 0 (j0 N inside int64), 1 <= n_slots <= 2^20, "
+             "0 <= sec0 <= sec_end ((sec_end + 1) sample_rate inside int64), 1 <= K <= 65536, an integer sample rate "
+             "<= 2^43");
     HIPCHK(c, hipSetDevice(c->device));
-    PhotonFillArgs a{};
+    PhotonFillRingArgs a{};
     a.events = d_events, a.heights = d_heights, a.dt = d_dt, a.d_n = d_n, a.image = d_image, a.stamps = d_stamps;
     a.row_height = d_row_height, a.row_dt = d_row_dt, a.fill = d_fill;
     a.n = n, a.j0 = j0, a.j_defer = j_defer, a.N = c->N, a.fs = (int64_t)c->cfg.sample_rate;
-    a.C = c->C, a.n_seconds = n_seconds, a.K = K, a.ncu = c->ncu;
-    HIPCHK(c, launch_fill_photon_heights(a, c->stream));
+    a.C = c->C, a.n_seconds = w ? w->n_slots : n_seconds, a.K = K, a.ncu = c->ncu;
+    if (w) {
+        a.sec0 = w->sec0, a.sec_end = w->sec_end;
+        HIPCHK(c, launch_fill_photon_heights_ring(a, c->stream));
+    } else {
+        HIPCHK(c, launch_fill_photon_heights(a, c->stream));
+    }
     return MKID_OK;
 }
 
 int mkid_fill_photon_heights(mkid_ctx* c, const uint64_t* d_events, const float* d_heights, const float* d_dt, int64_t n,
                              int64_t j0, int64_t j_defer, int32_t n_seconds, int32_t K, const int32_t* d_image,
                              const int64_t* d_stamps, float* d_row_height, float* d_row_dt, int64_t* d_fill) {
-    return fill_photon_heights(c, d_events, d_heights, d_dt, nullptr, n, j0, j_defer, n_seconds, K, d_image, d_stamps,
-                               d_row_height, d_row_dt, d_fill);
+    return fill_photon_heights(c, d_events, d_heights, d_dt, nullptr, n, j0, j_defer, n_seconds, nullptr, K, d_image,
+                               d_stamps, d_row_height, d_row_dt, d_fill);
 }
 
 int mkid_fill_photon_heights_counted(mkid_ctx* c, const uint64_t* d_events, const float* d_heights, const float* d_dt,
@@ -160,8 +202,57 @@ int mkid_fill_photon_heights_counted(mkid_ctx* c, const uint64_t* d_events, cons
                                      int32_t K, const int32_t* d_image, const int64_t* d_stamps, float* d_row_height,
                                      float* d_row_dt, int64_t* d_fill) {
     if (!d_count) return MKID_E_ARG;
-    return fill_photon_heights(c, d_events, d_heights, d_dt, d_count, cap, j0, j_defer, n_seconds, K, d_image, d_stamps,
+    return fill_photon_heights(c, d_events, d_heights, d_dt, d_count, cap, j0, j_defer, n_seconds, nullptr, K, d_image,
+                               d_stamps, d_row_height, d_row_dt, d_fill);
+}
+
+int mkid_fill_photon_heights_ring(mkid_ctx* c, const uint64_t* d_events, const float* d_heights, const float* d_dt,
+                                  int64_t n, int64_t j0, int64_t j_defer, int64_t sec0, int32_t n_slots, int64_t sec_end,
+                                  int32_t K, const int32_t* d_image, const int64_t* d_stamps, float* d_row_height,
+                                  float* d_row_dt, int64_t* d_fill) {
+    const obs::Window w{sec0, sec_end, n_slots};
+    return fill_photon_heights(c, d_events, d_heights, d_dt, nullptr, n, j0, j_defer, 0, &w, K, d_image, d_stamps,
                                d_row_height, d_row_dt, d_fill);
+}
+
+int mkid_fill_photon_heights_ring_counted(mkid_ctx* c, const uint64_t* d_events, const float* d_heights,
+                                          const float* d_dt, const int64_t* d_count, int64_t cap, int64_t j0,
+                                          int64_t j_defer, int64_t sec0, int32_t n_slots, int64_t sec_end, int32_t K,
+                                          const int32_t* d_image, const int64_t* d_stamps, float* d_row_height,
+                                          float* d_row_dt, int64_t* d_fill) {
+    if (!d_count) return MKID_E_ARG;
+    const obs::Window w{sec0, sec_end, n_slots};
+    return fill_photon_heights(c, d_events, d_heights, d_dt, d_count, cap, j0, j_defer, 0, &w, K, d_image, d_stamps,
+                               d_row_height, d_row_dt, d_fill);
+}
+
+int mkid_pack_second(mkid_ctx* c, int64_t sec, int32_t n_slots, int32_t K, const int32_t* d_image,
+                     const uint64_t* d_words, const int64_t* d_stamps, const float* d_row_height, const float* d_row_dt,
+                     int64_t cap_out, int32_t* d_counts, int64_t* d_offsets, uint64_t* d_out_words,
+                     int64_t* d_out_stamps, float* d_out_height, float* d_out_dt, int64_t* d_total) {
+    if (!c) return MKID_E_ARG;
+    if (!obs::pack_args_ok(sec, n_slots, K, c->C, d_image, d_words, d_stamps, d_row_height, d_row_dt, cap_out, d_counts,
+                           d_offsets, d_out_words, d_out_stamps, d_out_height, d_out_dt, d_total))
+        FAIL(c, MKID_E_ARG,
+             "pack second: need the tables, counts, offsets and total, sec >= 0, 1 <= n_slots <= 2^20, 1 <= K <= 65536, "
+             "cap_out >= 0 (with it, out words and heights), d_stamps with out stamps, d_row_dt with out dt");
+    HIPCHK(c, hipSetDevice(c->device));
+    const PackArgs a{d_image,     d_words,      d_stamps,     d_row_height, d_row_dt, d_counts,
+                     d_offsets,   d_out_words,  d_out_stamps, d_out_height, d_out_dt, d_total,
+                     obs::slot_of(sec, n_slots) * c->C, cap_out, c->C, K};
+    HIPCHK(c, launch_pack_second(a, c->stream));
+    return MKID_OK;
+}
+
+int mkid_clear_second(mkid_ctx* c, int64_t sec, int32_t n_slots, int32_t K, int32_t* d_image, float* d_row_height,
+                      float* d_row_dt) {
+    if (!c) return MKID_E_ARG;
+    if (!obs::clear_args_ok(sec, n_slots, K, c->C, d_image, d_row_height))
+        FAIL(c, MKID_E_ARG, "clear second: need d_image and d_row_height, sec >= 0, 1 <= n_slots <= 2^20, 1 <= K <= 65536");
+    HIPCHK(c, hipSetDevice(c->device));
+    const ClearArgs a{d_image, d_row_height, d_row_dt, obs::slot_of(sec, n_slots) * c->C, c->C, K};
+    HIPCHK(c, launch_clear_second(a, c->stream));
+    return MKID_OK;
 }
 
 // The CPU statements of the device calls: the loops of obs_common.h.
@@ -185,6 +276,52 @@ int mkid_fill_photon_heights_host(const uint64_t* events, const float* heights, 
         return MKID_E_ARG;
     obs::fill_host(events, heights, dt, n, j0, j_defer, fft_len, sample_rate, n_channels, n_seconds, K, image, stamps,
                    row_height, row_dt, fill);
+    return MKID_OK;
+}
+
+int mkid_list_photons_ring_host(const uint64_t* events, int64_t n, int64_t j0, int32_t fft_len, double sample_rate,
+                                int32_t n_channels, int64_t sec0, int32_t n_slots, int64_t sec_end, int32_t K,
+                                int32_t layout, int32_t* image, int64_t* outside, uint64_t* words, int64_t* stamps,
+                                int64_t* dropped) {
+    const obs::Window w{sec0, sec_end, n_slots};
+    if (!obs::list_ring_args_ok(events, n, j0, fft_len, sample_rate, n_channels, w, K, layout, image, outside, words,
+                                stamps, dropped))
+        return MKID_E_ARG;
+    obs::list_ring_host(events, n, j0, fft_len, sample_rate, n_channels, w, K, layout, image, outside, words, stamps,
+                        dropped);
+    return MKID_OK;
+}
+
+int mkid_fill_photon_heights_ring_host(const uint64_t* events, const float* heights, const float* dt, int64_t n,
+                                       int64_t j0, int64_t j_defer, int32_t fft_len, double sample_rate,
+                                       int32_t n_channels, int64_t sec0, int32_t n_slots, int64_t sec_end, int32_t K,
+                                       const int32_t* image, const int64_t* stamps, float* row_height, float* row_dt,
+                                       int64_t* fill) {
+    const obs::Window w{sec0, sec_end, n_slots};
+    if (!obs::fill_ring_args_ok(events, heights, n, j0, fft_len, sample_rate, n_channels, w, K, image, stamps, row_height,
+                                fill))
+        return MKID_E_ARG;
+    obs::fill_ring_host(events, heights, dt, n, j0, j_defer, fft_len, sample_rate, n_channels, w, K, image, stamps,
+                        row_height, row_dt, fill);
+    return MKID_OK;
+}
+
+int mkid_pack_second_host(int64_t sec, int32_t n_slots, int32_t K, int32_t n_channels, const int32_t* image,
+                          const uint64_t* words, const int64_t* stamps, const float* row_height, const float* row_dt,
+                          int64_t cap_out, int32_t* counts, int64_t* offsets, uint64_t* out_words, int64_t* out_stamps,
+                          float* out_height, float* out_dt, int64_t* total) {
+    if (!obs::pack_args_ok(sec, n_slots, K, n_channels, image, words, stamps, row_height, row_dt, cap_out, counts, offsets,
+                           out_words, out_stamps, out_height, out_dt, total))
+        return MKID_E_ARG;
+    obs::pack_host(sec, n_slots, K, n_channels, image, words, stamps, row_height, row_dt, cap_out, counts, offsets,
+                   out_words, out_stamps, out_height, out_dt, total);
+    return MKID_OK;
+}
+
+int mkid_clear_second_host(int64_t sec, int32_t n_slots, int32_t K, int32_t n_channels, int32_t* image,
+                           float* row_height, float* row_dt) {
+    if (!obs::clear_args_ok(sec, n_slots, K, n_channels, image, row_height)) return MKID_E_ARG;
+    obs::clear_host(sec, n_slots, K, n_channels, image, row_height, row_dt);
     return MKID_OK;
 }
 

@@ -3,7 +3,8 @@
 // entry points mkid_count_photons_host / mkid_height_spectra_host: the second of a packet on the
 // 1 PPS timebase (packets.Timebase.second), where a packet is counted, the spectrum column of a
 // height, and which packets wait for their height; and, further down, the photon rows of
-// mkid_list_photons / mkid_fill_photon_heights (k_photons.hip) with their host entry points. A
+// mkid_list_photons / mkid_fill_photon_heights (k_photons.hip), their ring forms, and the packed
+// second of mkid_pack_second / mkid_clear_second (k_pack.hip), with their host entry points. A
 // packet's channel and unwrapped stamp are fit::decode's. The host loops below are the whole of the host entry points, so that the CPU
 // sanitizer build (tools/plan_fuzz.cpp) runs them without HIP.
 #pragma once
@@ -147,21 +148,46 @@ OBS_HD int64_t find_stamp(const int64_t* stamps, int64_t m, int64_t jg) {
     return lo < m && stamps[lo] == jg ? lo : -1;
 }
 
-inline bool list_args_ok(const uint64_t* events, int64_t n, int64_t j0, int32_t N, double fs, int32_t C,
-                         int32_t n_seconds, int32_t K, int32_t layout, const int32_t* image, const int64_t* outside,
-                         const uint64_t* words, const int64_t* stamps, const int64_t* dropped) {
-    return count_args_ok(events, n, j0, N, fs, C, n_seconds, image, outside) && words && stamps && dropped &&
+// ---- the ring of second slots (the _ring forms; mkid_pack_second, mkid_clear_second) -------------
+// The tables are [n_slots][C][K], and second sec lives in slot sec mod n_slots while it is inside
+// the window sec0 <= sec < min(sec0 + n_slots, sec_end). The unbounded tables are the window
+// sec0 = 0, n_slots = sec_end = n_seconds, where ring_cell is cell.
+constexpr int32_t kMaxSlots = 1 << 20;
+constexpr int64_t kEarly = -3, kOverrun = -4;   // outside[2], outside[3]; a cell k < 0 counts in outside[-1 - k]
+struct Window {
+    int64_t sec0, sec_end;
+    int32_t n_slots;
+};
+OBS_HD Window whole(int32_t n_seconds) { return Window{0, n_seconds, n_seconds}; }
+// (sec_end + 1) fs, the first sample after the exposure's last second, stays inside int64
+OBS_HD bool window_ok(const Window& w, double fs) {
+    return w.n_slots >= 1 && w.n_slots <= kMaxSlots && w.sec0 >= 0 && w.sec0 <= w.sec_end && fs_ok(fs) &&
+           w.sec_end <= INT64_MAX / (int64_t)fs - 1;
+}
+OBS_HD int64_t ring_cell(const fit::Stamp& st, int32_t C, int64_t N, int64_t fs, const Window& w) {
+    if (st.ch >= C) return kNonPixel;
+    const int64_t sec = second(st.jg, N, fs);
+    if (sec >= w.sec_end) return kLate;
+    if (sec < w.sec0) return kEarly;
+    if (sec - w.sec0 >= w.n_slots) return kOverrun;
+    return sec % w.n_slots * C + st.ch;
+}
+
+inline bool list_ring_args_ok(const uint64_t* events, int64_t n, int64_t j0, int32_t N, double fs, int32_t C,
+                              const Window& w, int32_t K, int32_t layout, const int32_t* image, const int64_t* outside,
+                              const uint64_t* words, const int64_t* stamps, const int64_t* dropped) {
+    return count_args_ok(events, n, j0, N, fs, C, 1, image, outside) && window_ok(w, fs) && words && stamps && dropped &&
            row_slots_ok(K) && layout_ok(layout) && fs_us_ok(fs) && layout_fits(layout, C);
 }
 
-inline void list_host(const uint64_t* events, int64_t n, int64_t j0, int32_t N, double fs, int32_t C,
-                      int32_t n_seconds, int32_t K, int32_t layout, int32_t* image, int64_t* outside,
-                      uint64_t* words, int64_t* stamps, int64_t* dropped) {
+inline void list_ring_host(const uint64_t* events, int64_t n, int64_t j0, int32_t N, double fs, int32_t C,
+                           const Window& w, int32_t K, int32_t layout, int32_t* image, int64_t* outside,
+                           uint64_t* words, int64_t* stamps, int64_t* dropped) {
     for (int64_t p = 0; p < n; ++p) {
         const fit::Stamp st = fit::decode(events[p], j0);
-        const int64_t k = cell(st, C, N, (int64_t)fs, n_seconds);
+        const int64_t k = ring_cell(st, C, N, (int64_t)fs, w);
         if (k < 0) {
-            ++outside[k == kNonPixel ? 0 : 1];
+            ++outside[-1 - k];
             continue;
         }
         const uint32_t slot = (uint32_t)image[k];
@@ -175,23 +201,44 @@ inline void list_host(const uint64_t* events, int64_t n, int64_t j0, int32_t N, 
     }
 }
 
+inline bool list_args_ok(const uint64_t* events, int64_t n, int64_t j0, int32_t N, double fs, int32_t C,
+                         int32_t n_seconds, int32_t K, int32_t layout, const int32_t* image, const int64_t* outside,
+                         const uint64_t* words, const int64_t* stamps, const int64_t* dropped) {
+    return seconds_ok(n_seconds) &&
+           list_ring_args_ok(events, n, j0, N, fs, C, whole(n_seconds), K, layout, image, outside, words, stamps, dropped);
+}
+
+inline void list_host(const uint64_t* events, int64_t n, int64_t j0, int32_t N, double fs, int32_t C,
+                      int32_t n_seconds, int32_t K, int32_t layout, int32_t* image, int64_t* outside,
+                      uint64_t* words, int64_t* stamps, int64_t* dropped) {
+    list_ring_host(events, n, j0, N, fs, C, whole(n_seconds), K, layout, image, outside, words, stamps, dropped);
+}
+
+inline bool fill_ring_args_ok(const uint64_t* events, const float* heights, int64_t n, int64_t j0, int32_t N,
+                              double fs, int32_t C, const Window& w, int32_t K, const int32_t* image,
+                              const int64_t* stamps, const float* row_height, const int64_t* fill) {
+    return image && stamps && row_height && fill && (n == 0 || (events && heights)) && n >= 0 && C >= 1 && C <= 4096 &&
+           window_ok(w, fs) && row_slots_ok(K) && fs_us_ok(fs) && j0_ok(j0, N);
+}
+
 inline bool fill_args_ok(const uint64_t* events, const float* heights, int64_t n, int64_t j0, int32_t N, double fs,
                          int32_t C, int32_t n_seconds, int32_t K, const int32_t* image, const int64_t* stamps,
                          const float* row_height, const int64_t* fill) {
-    return image && stamps && row_height && fill && (n == 0 || (events && heights)) && n >= 0 && C >= 1 && C <= 4096 &&
-           seconds_ok(n_seconds) && row_slots_ok(K) && fs_us_ok(fs) && j0_ok(j0, N);
+    return seconds_ok(n_seconds) &&
+           fill_ring_args_ok(events, heights, n, j0, N, fs, C, whole(n_seconds), K, image, stamps, row_height, fill);
 }
 
 // A height (and dt) is copied as its 32-bit pattern: a NaN keeps its payload.
 OBS_HD void copy_bits(float* dst, const float* src) { __builtin_memcpy(dst, src, sizeof(float)); }
 
-inline void fill_host(const uint64_t* events, const float* heights, const float* dt, int64_t n, int64_t j0,
-                      int64_t j_defer, int32_t N, double fs, int32_t C, int32_t n_seconds, int32_t K,
-                      const int32_t* image, const int64_t* stamps, float* row_height, float* row_dt, int64_t* fill) {
+inline void fill_ring_host(const uint64_t* events, const float* heights, const float* dt, int64_t n, int64_t j0,
+                           int64_t j_defer, int32_t N, double fs, int32_t C, const Window& w, int32_t K,
+                           const int32_t* image, const int64_t* stamps, float* row_height, float* row_dt,
+                           int64_t* fill) {
     for (int64_t p = 0; p < n; ++p) {
         const fit::Stamp st = fit::decode(events[p], j0);
         if (st.ch >= C || deferred(heights[p], st.jg, j_defer)) continue;
-        const int64_t k = cell(st, C, N, (int64_t)fs, n_seconds);
+        const int64_t k = ring_cell(st, C, N, (int64_t)fs, w);
         const int64_t at = k < 0 ? -1 : find_stamp(stamps + k * K, row_fill(image[k], K), st.jg);
         if (at < 0) {
             ++fill[1];
@@ -200,6 +247,69 @@ inline void fill_host(const uint64_t* events, const float* heights, const float*
         copy_bits(row_height + k * K + at, heights + p);
         if (dt && row_dt) copy_bits(row_dt + k * K + at, dt + p);
         ++fill[0];
+    }
+}
+
+inline void fill_host(const uint64_t* events, const float* heights, const float* dt, int64_t n, int64_t j0,
+                      int64_t j_defer, int32_t N, double fs, int32_t C, int32_t n_seconds, int32_t K,
+                      const int32_t* image, const int64_t* stamps, float* row_height, float* row_dt, int64_t* fill) {
+    fill_ring_host(events, heights, dt, n, j0, j_defer, N, fs, C, whole(n_seconds), K, image, stamps, row_height,
+                   row_dt, fill);
+}
+
+// ---- a settled second out of its slot (mkid_pack_second) and the slot made free (mkid_clear_second)
+// PacketMaster's hand-over of a finished second (PacketMaster.c:329-368, write_sec_data 978-1050):
+// the rows of slot sec mod n_slots, each cut to its row_fill, laid end to end in pixel order.
+constexpr uint32_t kNanBits = 0x7FC00000u;   // the NaN the height and dt tables are pre-filled with
+OBS_HD int64_t slot_of(int64_t sec, int32_t n_slots) { return sec % n_slots; }
+
+inline bool clear_args_ok(int64_t sec, int32_t n_slots, int32_t K, int32_t C, const int32_t* image,
+                          const float* row_height) {
+    return image && row_height && sec >= 0 && n_slots >= 1 && n_slots <= kMaxSlots && row_slots_ok(K) && C >= 1 &&
+           C <= 4096;
+}
+
+inline bool pack_args_ok(int64_t sec, int32_t n_slots, int32_t K, int32_t C, const int32_t* image,
+                         const uint64_t* words, const int64_t* stamps, const float* row_height, const float* row_dt,
+                         int64_t cap_out, const int32_t* counts, const int64_t* offsets, const uint64_t* out_words,
+                         const int64_t* out_stamps, const float* out_height, const float* out_dt, const int64_t* total) {
+    return clear_args_ok(sec, n_slots, K, C, image, row_height) && words && counts && offsets && total && cap_out >= 0 &&
+           (cap_out == 0 || (out_words && out_height)) && (!out_stamps || stamps) && (!out_dt || row_dt);
+}
+
+inline void pack_host(int64_t sec, int32_t n_slots, int32_t K, int32_t C, const int32_t* image, const uint64_t* words,
+                      const int64_t* stamps, const float* row_height, const float* row_dt, int64_t cap_out,
+                      int32_t* counts, int64_t* offsets, uint64_t* out_words, int64_t* out_stamps, float* out_height,
+                      float* out_dt, int64_t* total) {
+    const int64_t row0 = slot_of(sec, n_slots) * C;
+    int64_t off = 0;
+    for (int32_t c = 0; c < C; ++c) {
+        const int64_t m = row_fill(image[row0 + c], K), src = (row0 + c) * K;
+        counts[c] = image[row0 + c];
+        offsets[c] = off;
+        for (int64_t i = 0; i < m && off + i < cap_out; ++i) {
+            out_words[off + i] = words[src + i];
+            if (out_stamps) out_stamps[off + i] = stamps[src + i];
+            copy_bits(out_height + off + i, row_height + src + i);
+            if (out_dt) copy_bits(out_dt + off + i, row_dt + src + i);
+        }
+        off += m;
+    }
+    offsets[C] = off;
+    total[0] = off;
+    total[1] = off < cap_out ? off : cap_out;
+}
+
+inline void clear_host(int64_t sec, int32_t n_slots, int32_t K, int32_t C, int32_t* image, float* row_height,
+                       float* row_dt) {
+    const int64_t row0 = slot_of(sec, n_slots) * C;
+    for (int32_t c = 0; c < C; ++c) {
+        const int64_t m = row_fill(image[row0 + c], K), at = (row0 + c) * K;
+        for (int64_t i = 0; i < m; ++i) {
+            __builtin_memcpy(row_height + at + i, &kNanBits, 4);
+            if (row_dt) __builtin_memcpy(row_dt + at + i, &kNanBits, 4);
+        }
+        image[row0 + c] = 0;
     }
 }
 

@@ -7,7 +7,11 @@ device-to-host copy and no synchronisation. With photon_rows=K it also keeps the
 PacketMaster's per-pixel, per-second photon rows (/r#/p#/t<obs>, PacketMaster.c:978-1050), K slots a
 row, each photon with its height (and arrival offset) once the deferral protocol has settled it
 (include/mkidgpu.h mkid_list_photons, mkid_fill_photon_heights): six calls a step, still no
-synchronisation.
+synchronisation. With ring=R the rows are a ring of R second slots of bounded memory: ready() says
+which seconds are settled, and drain() packs each into PacketMaster's variable-length form on the
+device (mkid_pack_second), copies only the photons to the host as a Second, and clears the slot for
+reuse (mkid_clear_second), as PacketMaster hands a finished second to its writer
+(PacketMaster.c:329-368).
 """
 import numpy as np
 
@@ -19,6 +23,47 @@ def j_defer(j0, rows, ncoeff, pre, search=0):
     j0 .. j0 + rows - 1: a window is inside while (jg - j0 - pre) + search + ncoeff <= rows
     (csrc/fit_common.h inside; search = 0 for the plain heights)."""
     return int(j0) + int(rows) + int(pre) - int(ncoeff) - int(search) + 1
+
+
+def settled_bound(j0, rows, jd):
+    """After a step over rows j0 .. j0 + rows - 1 with deferral point jd, every packet stamped below
+    min(jd, j0 + rows - 1) is final: a later call stamps no packet below its own j0 - 1 (the trigger
+    stamps the packet it emits at row j with j - 1, csrc/k_trigger.hip make_packet), so every such
+    packet has been listed; and a packet stamped below jd is not deferred by this step, so it has
+    been filled or counted in fill[1]."""
+    return min(int(jd), int(j0) + int(rows) - 1)
+
+
+def ready_seconds(tb, sec0, n_slots, sec_end, settled, last=-1):
+    """The seconds of the window [sec0, min(sec0 + n_slots, sec_end)) that are ready, in order: second
+    s when every stamp of it lies below the settled bound, tb.first_row(s + 1) <= settled, or when
+    s <= last (a final drain)."""
+    out, s = [], int(sec0)
+    while s < min(int(sec_end), int(sec0) + int(n_slots)) and (tb.first_row(s + 1) <= settled or s <= last):
+        out.append(s)
+        s += 1
+    return out
+
+
+class Second:
+    """One second of photon rows in PacketMaster's variable-length form (include/mkidgpu.h
+    mkid_pack_second): counts int32 [C] (the raw counts, the image row), offsets int64 [C + 1]
+    (pixel p's photons are entries offsets[p] .. offsets[p + 1]), and per photon word uint64, stamp
+    int64, us int64, height and dt float32 (NaN where the height never settled)."""
+
+    def __init__(self, sec, counts, offsets, word, stamp, us, height, dt):
+        self.sec, self.counts, self.offsets = int(sec), counts, offsets
+        self.word, self.stamp, self.us, self.height, self.dt = word, stamp, us, height, dt
+
+    def row(self, p):
+        """Pixel p's photons as Observation.photons(sec, p) gives them."""
+        a, b = int(self.offsets[p]), int(self.offsets[p + 1])
+        return dict(word=self.word[a:b], stamp=self.stamp[a:b], us=self.us[a:b], height=self.height[a:b],
+                    dt=self.dt[a:b])
+
+    def rows(self):
+        """The second as Observation.rows(sec) gives it: a list of C uint64 arrays."""
+        return [self.word[int(a):int(b)].copy() for a, b in zip(self.offsets[:-1], self.offsets[1:])]
 
 
 class Observation:
@@ -39,10 +84,15 @@ class Observation:
                 heights and arrival offsets on the device, the last two NaN until filled (the
                 offsets stay NaN without fit)
     row_layout  _lib.ROW_WIDE (any C) or _lib.ROW_REFERENCE (packets.encode_wire's word, C <= 254)
+    ring        None: the tables above. R (with photon_rows): the tables are [R][C][K], second sec in slot
+                sec mod R while it is one of the R seconds from the first undrained one on, and
+                n_seconds, the exposure, may be any positive value; drain() takes the settled
+                seconds out as Second objects and frees their slots. image(), rows() and photons()
+                then raise: the data leave through Second. outside() is int64 [4] there.
     """
 
     def __init__(self, chan, n_seconds, nbins, lo, step, cap, cap_deferred, fit=False, debug=False,
-                 photon_rows=None, row_layout=_lib.ROW_WIDE):
+                 photon_rows=None, row_layout=_lib.ROW_WIDE, ring=None):
         import torch
         if chan.pulse_filter is None:
             raise ValueError('Observation: set the pulse filter first')
@@ -58,9 +108,14 @@ class Observation:
             self.inv = np.float32(1) / self.step_width
         self.d_lo, self.d_inv = torch.from_numpy(self.lo).to(dev), torch.from_numpy(self.inv).to(dev)
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
-        self.d_image = z((self.n_seconds, C), torch.int32)
+        self.R = None if ring is None else int(ring)
+        if self.R is not None and (photon_rows is None or not 1 <= self.R <= 1 << 20 or self.n_seconds < 1):
+            raise ValueError('Observation(ring=R): needs photon_rows, 1 <= R <= 2^20 and n_seconds >= 1')
+        self.sec0 = 0                      # ring: the first second not yet drained
+        self.settled, self.j_end = 0, 0    # every packet stamped below `settled` is final; rows processed
+        self.d_image = z((self.n_seconds if self.R is None else self.R, C), torch.int32)
         self.d_spectra = z((C, self.nbins + 3), torch.int32)
-        self.d_outside = z(2, torch.int64)
+        self.d_outside = z(2 if self.R is None else 4, torch.int64)
         self.d_def = [z(max(self.cap_def, 1), torch.int64) for _ in range(2)]
         self.d_ndef = [z(2, torch.int64) for _ in range(2)]
         self.d_zero = z(2, torch.int64)
@@ -72,12 +127,15 @@ class Observation:
         if self.K is not None:
             if not 1 <= self.K <= 65536:
                 raise ValueError('Observation: photon_rows must be 1 .. 65536')
-            shape = (self.n_seconds, C, self.K)
+            shape = (self.n_seconds if self.R is None else self.R, C, self.K)
             self.d_words, self.d_stamps = z(shape, torch.int64), z(shape, torch.int64)
             self.d_row_height = torch.full(shape, float('nan'), dtype=torch.float32, device=dev)
             self.d_row_dt = torch.full(shape, float('nan'), dtype=torch.float32, device=dev)
             self.d_dt = z(max(self.cap_join, 1), torch.float32) if self.fit else None
             self.d_dropped, self.d_fill = z(1, torch.int64), z(2, torch.int64)
+            self.d_pack = None             # the packed second's buffers: a ring's now, else with the first packed()
+            if self.R is not None:
+                self._pack_buffers()
         self.cur = 0          # d_def[cur], d_ndef[cur]: the packets deferred by the last step
         self.steps = []       # debug: (joined uint64, heights float32, j0, j_defer) of every step
         torch.cuda.synchronize(dev)   # torch's stream made the buffers, the context's stream uses them
@@ -94,6 +152,10 @@ class Observation:
         jd = j_defer(j0, rows, ncoeff, pre, L)
         if self.K is None:
             ch.count_photons_counted(d_events, d_n, self.cap, j0, self.n_seconds, self.d_image, self.d_outside)
+        elif self.R is not None:
+            ch.list_photons_ring_counted(d_events, d_n, self.cap, j0, self.sec0, self.R, self.n_seconds, self.K,
+                                         self.row_layout, self.d_image, self.d_outside, self.d_words, self.d_stamps,
+                                         self.d_dropped)
         else:
             ch.list_photons_counted(d_events, d_n, self.cap, j0, self.n_seconds, self.K, self.row_layout, self.d_image,
                                     self.d_outside, self.d_words, self.d_stamps, self.d_dropped)
@@ -109,11 +171,17 @@ class Observation:
         ch.stream_copy(self.d_ndef[cur ^ 1], self.d_zero, 16)   # on the context's stream: no torch memset
         ch.height_spectra_counted(self.d_join, self.d_heights, d_nj, self.cap_join, j0, jd, self.d_lo, self.d_inv,
                                   self.nbins, self.d_spectra, self.d_def[cur ^ 1], self.cap_def, self.d_ndef[cur ^ 1])
-        if self.K is not None:
+        if self.R is not None:
+            ch.fill_photon_heights_ring_counted(self.d_join, self.d_heights, d_dt, d_nj, self.cap_join, j0, jd,
+                                                self.sec0, self.R, self.n_seconds, self.K, self.d_image,
+                                                self.d_stamps, self.d_row_height, self.d_row_dt, self.d_fill)
+        elif self.K is not None:
             ch.fill_photon_heights_counted(self.d_join, self.d_heights, d_dt, d_nj, self.cap_join, j0, jd,
                                            self.n_seconds, self.K, self.d_image, self.d_stamps, self.d_row_height,
                                            self.d_row_dt, self.d_fill)
         self.cur = cur ^ 1
+        self.j_end = int(j0) + int(rows)
+        self.settled = max(self.settled, settled_bound(j0, rows, jd))
         if self.debug:
             import torch
             torch.cuda.synchronize(ch.torch_device())
@@ -125,8 +193,14 @@ class Observation:
         import torch
         torch.cuda.synchronize(self.chan.torch_device())
 
+    def _not_ring(self, what):
+        if self.R is not None:
+            raise ValueError('Observation(ring=R).%s: a ring keeps no whole table; take the seconds as Second '
+                             'objects from drain()' % what)
+
     def image(self):
         """int32 [n_seconds][C]: packets per second and channel."""
+        self._not_ring('image')
         self._sync()
         return self.d_image.cpu().numpy()
 
@@ -146,7 +220,8 @@ class Observation:
         return float(self.lo[c]) + np.arange(self.nbins + 1) * float(self.step_width[c])
 
     def outside(self):
-        """int64 [2]: packets of channels >= C, packets of seconds >= n_seconds."""
+        """int64 [2]: packets of channels >= C, packets of seconds >= n_seconds; with ring=R int64 [4]:
+        then those of seconds already drained, and those the ring had no slot for."""
         self._sync()
         return self.d_outside.cpu().numpy()
 
@@ -171,6 +246,7 @@ class Observation:
         (microsecond since PPS), height float32, dt float32 (rows; NaN without fit)); a height is
         NaN until the photon's window has completed."""
         self._rows_on()
+        self._not_ring('photons')
         self._sync()
         m = min(int(self.d_image[sec, ch].item()), self.K)
         host = lambda t: t[sec, ch, :m].cpu().numpy()
@@ -183,6 +259,7 @@ class Observation:
         """Second sec as PacketMaster holds it (its rows[(r, p)][sec] for every pixel p): a list
         of C uint64 arrays, pixel p's the first min(image, K) words of its row."""
         self._rows_on()
+        self._not_ring('rows')
         self._sync()
         m = np.minimum(self.d_image[sec].cpu().numpy(), self.K)
         w = self.d_words[sec].cpu().numpy().view(np.uint64)
@@ -200,3 +277,84 @@ class Observation:
         self._rows_on()
         self._sync()
         return self.d_fill.cpu().numpy()
+
+    # ---- a second in packed form; the ring (ring=R) ----------------------------------------------
+    def _pack_buffers(self):
+        """Room for any second in packed form: C K entries, one more slot's worth of memory."""
+        import torch
+        C, dev = self.chan.C, self.chan.torch_device()
+        cap = C * self.K
+        e = lambda dt: torch.empty(cap, dtype=dt, device=dev)
+        self.d_pack = dict(cap=cap, counts=torch.empty(C, dtype=torch.int32, device=dev),
+                           offsets=torch.empty(C + 1, dtype=torch.int64, device=dev), word=e(torch.int64),
+                           stamp=e(torch.int64), height=e(torch.float32), dt=e(torch.float32),
+                           total=torch.empty(2, dtype=torch.int64, device=dev))
+
+    def _packed(self, sec, n_slots, clear):
+        """Pack second sec on the device, clear its slot when asked, synchronise once, and copy
+        counts, offsets and the second's photons (nothing of the padding) to the host."""
+        ch, C = self.chan, self.chan.C
+        if self.d_pack is None:
+            self._pack_buffers()
+            self._sync()                   # torch's stream made the buffers, the context's stream uses them
+        b = self.d_pack
+        ch.pack_second(sec, n_slots, self.K, self.d_image, self.d_words, self.d_stamps, self.d_row_height,
+                       self.d_row_dt, b['cap'], b['counts'], b['offsets'], b['word'], b['stamp'], b['height'], b['dt'],
+                       b['total'])
+        if clear:
+            ch.clear_second(sec, n_slots, self.K, self.d_image, self.d_row_height, self.d_row_dt)
+        self._sync()
+        offsets = b['offsets'].cpu().numpy()
+        m = int(offsets[C])                # cap = C K holds any second
+        host = lambda k: b[k][:m].cpu().numpy()
+        stamp = host('stamp')
+        return Second(sec, b['counts'].cpu().numpy(), offsets, host('word').view(np.uint64), stamp,
+                      packets.Timebase(ch.cfg.sample_rate, ch.N).microsecond(stamp), host('height'), host('dt'))
+
+    def packed(self, sec):
+        """Second sec of the unbounded tables (ring=None) as a Second; the tables stay as they are."""
+        self._rows_on()
+        self._not_ring('packed')
+        if not 0 <= int(sec) < self.n_seconds:
+            raise ValueError('Observation.packed: second outside 0 .. n_seconds - 1')
+        return self._packed(int(sec), self.n_seconds, False)
+
+    def _ring_on(self):
+        if self.R is None:
+            raise ValueError('Observation: made without ring')
+
+    def ready(self, final=False):
+        """The seconds from the first undrained one on that are settled, by host arithmetic alone:
+        second s is ready when every stamp of it lies below the settled bound,
+        Timebase.first_row(s + 1) <= min(j_defer, j0 + rows - 1) of the last step. With final, also
+        the seconds up to the last processed row. At most R, and none past the exposure."""
+        self._ring_on()
+        tb = packets.Timebase(self.chan.cfg.sample_rate, self.chan.N)
+        last = int(tb.second(self.j_end - 1)) if final and self.j_end > 0 else -1
+        return ready_seconds(tb, self.sec0, self.R, self.n_seconds, self.settled, last)
+
+    def drain(self, final=False):
+        """Take every ready second out of the ring, in order -> a list of Second. Each is packed,
+        its slot cleared, and the window moved on by one; one synchronisation per second, none
+        when nothing is ready. With final the seconds up to the last processed row leave too, the
+        heights that never settled NaN."""
+        out = []
+        while True:                        # a final drain of more than R seconds frees slots as it goes
+            todo = self.ready(final)
+            if not todo:
+                return out
+            for s in todo:
+                out.append(self._packed(s, self.R, True))
+                self.sec0 = s + 1
+
+    def overrun(self):
+        """Packets whose second had no slot: the ring is too short, or was not drained in time."""
+        self._ring_on()
+        self._sync()
+        return int(self.d_outside[3].item())
+
+    def early(self):
+        """Packets of a second that was already drained."""
+        self._ring_on()
+        self._sync()
+        return int(self.d_outside[2].item())

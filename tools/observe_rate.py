@@ -18,6 +18,14 @@ the worst case for the count kernel's runs and the spectra kernel's LDS rows).
   fill_*         mkid_fill_photon_heights of the list in that order into the device-order rows
   host_route     what this replaces: device-to-host copy of list and heights, then the numpy restatement
                  (tests/observe_cases.py), wall clock
+  pack / drain   with --ring (k_pack.hip): list_ring_* and fill_ring_* (the ring forms over the same window,
+                 beside list_* and fill_*), pack, clear and pack_clear of second 1 of the device-order rows
+                 (mkid_pack_second, mkid_clear_second), and, wall clock, a whole drain of that second
+                 (observe.Observation's: pack, clear, one synchronisation, the photons copied) against the
+                 route without it (Observation.rows(sec) plus the padded stamp, height and dt tables of the
+                 second), with the bytes each moves to the host
+  *_parent       with --parent-lib PATH: list_* and fill_* through a library built from the parent commit,
+                 alternating with this tree's in the same rounds
 
 Every device path is one HIP-event interval on a stream shared with torch; the paths alternate inside
 each of --reps rounds after two warm-up rounds, and the median, minimum and maximum over the rounds
@@ -56,6 +64,79 @@ def context(C, stream, lds=None):
     return ch
 
 
+def ring_section(args, chan, s, rows, row_h, want, n_seconds, K, sec=1):
+    """Second `sec` of the device-order rows (filled, as the checks left them): pack, clear and both as
+    HIP-event intervals, then a whole drain against the route without it as wall clock, the paths
+    alternating inside each round after two warm-up rounds. The drain and the other route are
+    observe.Observation's own code, run on an Observation that is handed these tables."""
+    import torch
+    import ring_cases as rc_
+    from mkids_sdr_amd import observe
+    C = chan.C
+    row_dt = torch.full((n_seconds, C, K), float('nan'), device='cuda')
+    obs = object.__new__(observe.Observation)      # no step() is run: only the readouts' fields
+    obs.chan, obs.K, obs.R, obs.n_seconds, obs.d_pack = chan, K, None, n_seconds, None
+    obs.d_image, obs.d_words, obs.d_stamps = rows['image'], rows['words'], rows['stamps']
+    obs.d_row_height, obs.d_row_dt = row_h, row_dt
+    obs._pack_buffers()
+    torch.cuda.synchronize()
+    b = obs.d_pack
+    keep_image, keep_h = rows['image'][sec].clone(), row_h[sec].clone()
+
+    def restore():
+        rows['image'][sec].copy_(keep_image)
+        row_h[sec].copy_(keep_h)
+
+    def pack():
+        chan.pack_second(sec, n_seconds, K, obs.d_image, obs.d_words, obs.d_stamps, row_h, row_dt, b['cap'], b['counts'],
+                         b['offsets'], b['word'], b['stamp'], b['height'], b['dt'], b['total'])
+
+    def clear():
+        chan.clear_second(sec, n_seconds, K, obs.d_image, row_h, row_dt)
+
+    def parent_route():                            # Observation.rows(sec) and the three other padded tables of the second
+        r = obs.rows(sec)
+        return r, obs.d_stamps[sec].cpu().numpy(), row_h[sec].cpu().numpy(), row_dt[sec].cpu().numpy()
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = fn()
+        return (time.perf_counter() - t0) * 1e3, r
+
+    ev_paths = [('pack', pack), ('clear', clear), ('pack_clear', lambda: (pack(), clear()))]
+    times = {k: [] for k in ('pack', 'clear', 'pack_clear', 'drain_wall', 'parent_route_wall')}
+    for rep in range(args.reps + 2):
+        for name, fn in ev_paths:
+            restore()
+            t = event_ms(s, fn)
+            if rep >= 2:
+                times[name].append(t)
+        restore()
+        t_d, second = wall(lambda: obs._packed(sec, n_seconds, True))
+        restore()
+        t_p, padded = wall(parent_route)
+        if rep >= 2:
+            times['drain_wall'].append(t_d)
+            times['parent_route_wall'].append(t_p)
+    restore()
+    torch.cuda.synchronize()
+    ref = rc_.pack_ref(want, sec)                  # the numpy restatement of the packed second
+    m = int(ref.total[0])
+    same = (np.array_equal(second.counts, ref.counts) and np.array_equal(second.offsets, ref.offsets) and
+            np.array_equal(second.word, ref.words[:m]) and np.array_equal(second.stamp, ref.stamps[:m]) and
+            np.array_equal(second.height.view(np.uint32), ref.height[:m].view(np.uint32)))
+    same_rows = all(np.array_equal(a, c) for a, c in zip(second.rows(), padded[0]))
+    out = {}
+    for name, t in times.items():
+        out.update(stats(name, t))
+    out.update(drain_second=sec, drain_photons=m, drain_bytes=4 * C + 8 * (C + 1) + 24 * m,
+               parent_route_bytes=4 * C + 24 * C * K,
+               drain_over_parent_route=round(float(np.median(times['drain_wall']) / np.median(times['parent_route_wall'])), 3),
+               checks=dict(packed_equal_numpy=bool(same), packed_rows_equal_rows=bool(same_rows)))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=20)
@@ -66,6 +147,8 @@ def main():
     ap.add_argument('--pre', type=int, default=20)
     ap.add_argument('--nbins', type=int, default=256)
     ap.add_argument('--row-slots', type=int, default=2499)      # PacketMaster's MAX_EVENTS_PER_SEC - 1
+    ap.add_argument('--ring', action='store_true', help='also time the ring forms, pack, clear and a whole drain')
+    ap.add_argument('--parent-lib', default=None, help='a libmkidgpu.so of the parent commit: list_* / fill_* A/B')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     import torch
@@ -146,6 +229,39 @@ def main():
 
     paths += [('list_' + o, rows_list(o)) for o in ev] + [('fill_' + o, rows_fill(o)) for o in ev]
     prep = {'list_' + o: rows[o]['image'].zero_ for o in ev}
+    if args.parent_lib:                        # the same calls through the parent's library, same tables
+        from mkids_sdr_amd.channelizer import Channelizer
+        ctx['parent'] = Channelizer(C, max_chunk=1 << 20, lib_path=args.parent_lib)
+        ctx['parent'].set_stream(s.cuda_stream)
+
+        def parent_list(o):
+            r = rows[o]
+            return lambda: ctx['parent'].list_photons_device(d_ev[o], n, 0, n_seconds, K, pc.WIDE, r['image'], r['outside'],
+                                                             r['words'], r['stamps'], r['dropped'])
+
+        def parent_fill(o):
+            r = rows['dev']
+            return lambda: ctx['parent'].fill_photon_heights_device(d_ev[o], d_h[o], None, n, 0, j_defer, n_seconds, K,
+                                                                    r['image'], r['stamps'], row_h[o], None, d_fill[o])
+
+        paths += [('list_%s_parent' % o, parent_list(o)) for o in ev] + [('fill_%s_parent' % o, parent_fill(o)) for o in ev]
+        prep.update({'list_%s_parent' % o: rows[o]['image'].zero_ for o in ev})
+    if args.ring:                              # the ring forms over the same window: the same work
+        out4 = z(4, torch.int64)
+
+        def ring_list(o):
+            r = rows[o]
+            return lambda: ctx['default'].list_photons_ring_device(d_ev[o], n, 0, 0, n_seconds, n_seconds, K, pc.WIDE,
+                                                                   r['image'], out4, r['words'], r['stamps'], r['dropped'])
+
+        def ring_fill(o):
+            r = rows['dev']
+            return lambda: ctx['default'].fill_photon_heights_ring_device(d_ev[o], d_h[o], None, n, 0, j_defer, 0, n_seconds,
+                                                                          n_seconds, K, r['image'], r['stamps'], row_h[o],
+                                                                          None, d_fill[o])
+
+        paths += [('list_ring_' + o, ring_list(o)) for o in ev] + [('fill_ring_' + o, ring_fill(o)) for o in ev]
+        prep.update({'list_ring_' + o: rows[o]['image'].zero_ for o in ev})
     times = {name: [] for name, _ in paths}
     for rep in range(args.reps + 2):           # two warm-up rounds: code objects, clocks, caches
         for name, fn in paths:
@@ -172,10 +288,11 @@ def main():
     for t in row_h.values():
         t.fill_(float('nan'))
     torch.cuda.synchronize()
-    for name, fn in paths[1:]:
+    once = [(name, fn) for name, fn in paths[1:] if '_parent' not in name and '_ring_' not in name]
+    for name, fn in once:
         if not name.startswith('fill_'):
             fn()
-    for name, fn in paths[1:]:                 # the fills after both lists
+    for name, fn in once:                      # the fills after both lists
         if name.startswith('fill_'):
             fn()
     torch.cuda.synchronize()
@@ -209,6 +326,8 @@ def main():
         packets_in_image=int(ref_image.sum()), packets_late=int(ref_out[1]), no_height=int(ref_sp[:, nbins + 2].sum()),
         deferred=int(ref_ndef[0]), channels_with_packets=int((ref_sp.sum(axis=1) > 0).sum()))
     check.update(rows_check)
+    ring_out = ring_section(args, ctx['default'], s, rows['dev'], row_h['dev'], want, n_seconds, K) if args.ring else {}
+    check.update(ring_out.pop('checks', {}))
     med = {name: float(np.median(t)) for name, t in times.items()}
     out = dict(tool='observe_rate', channels=C, rows=J, ncoeff=nco, pre=pre, packets=n, nbins=nbins, n_seconds=n_seconds,
                reps=args.reps)
@@ -225,6 +344,13 @@ def main():
     out['stage_over_heights'] =round((med['count_dev'] + med['concat'] + med['spectra_defer']) / med['heights'], 3)
     out['host_route_copy_ms'] = round(float(np.median([a for a, _ in host_t])), 2)
     out['host_route_numpy_ms'] = round(float(np.median([b for _, b in host_t])), 2)
+    if args.parent_lib:                        # this tree's median against the parent's, and the parent's own spread
+        for name in ('list_dev', 'list_time', 'fill_dev', 'fill_time'):
+            t = times[name + '_parent']
+            out[name + '_minus_parent_ms'] = round(med[name] - med[name + '_parent'], 4)
+            out[name + '_parent_spread_ms'] = round(max(t) - min(t), 4)
+            out[name + '_within_parent_spread'] = bool(abs(med[name] - med[name + '_parent']) <= max(t) - min(t))
+    out.update(ring_out)
     out['checks'] = check
     line = json.dumps(out)
     print(line, flush=True)

@@ -4,7 +4,7 @@
 // device code relies on (include/mkidgpu.h); the slot-table writes are replayed into
 // buffers of exactly the planned size, so an undersized plan is an ASan heap overflow, not a
 // silent miscount (the ADVICE r02 scratch-sizing bug is that class).
-// fuzz_observe and fuzz_photons drive the observing rules and the host twins' loops
+// fuzz_observe, fuzz_photons and fuzz_pack drive the observing rules and the host twins' loops
 // (csrc/obs_common.h) likewise.
 //   plan_fuzz [iterations] [seed]
 #include <stdint.h>
@@ -897,6 +897,182 @@ static void fuzz_photons(int iters) {
           "fill argument checks");
 }
 
+// The ring forms and the packed second (obs_common.h list_ring_host, fill_ring_host, pack_host,
+// clear_host) on random lists: windows with sec0 at and around the edges of the seconds the list
+// holds, K = 1, overflowing rows, cap_out below, at and above the total; every table and every
+// output is a buffer of exactly the documented size, so an access outside one is an ASan report.
+static void fuzz_pack(int iters) {
+    namespace obs = mkid::obs;
+    CHECK(obs::window_ok(obs::Window{0, 0, 1}, 1.0) && obs::window_ok(obs::Window{5, 5, 1 << 20}, 1e6) &&
+              !obs::window_ok(obs::Window{0, 1, 0}, 1e6) && !obs::window_ok(obs::Window{0, 1, (1 << 20) + 1}, 1e6) &&
+              !obs::window_ok(obs::Window{-1, 1, 1}, 1e6) && !obs::window_ok(obs::Window{2, 1, 1}, 1e6) &&
+              obs::window_ok(obs::Window{0, INT64_MAX / 1000000 - 1, 1}, 1e6) &&
+              !obs::window_ok(obs::Window{0, INT64_MAX / 1000000, 1}, 1e6) && !obs::window_ok(obs::Window{0, 1, 1}, 0.5),
+          "window_ok");
+    for (int it = 0; it < iters; ++it) {
+        const int32_t C = (int32_t)rint_(1, 24), N = (int32_t)(1 << rint_(0, 8));
+        const int32_t R = (int32_t)rint_(1, 4), K = (int32_t)(rint_(0, 2) ? rint_(1, 5) : 1);
+        const int32_t layout = (int32_t)rint_(0, 1);
+        const int64_t per = rint_(1, 60), fs = (int64_t)N * per;   // rows per second
+        const int64_t j0 = rint_(0, 3000), first = j0 * N / fs;    // the list spans seconds first .. first + 6
+        const int64_t sec0 = std::max<int64_t>(0, first + rint_(-2, 6)), sec_end = sec0 + rint_(0, 6);
+        const obs::Window w{sec0, sec_end, R};
+        const int64_t n = rint_(0, 300);
+        std::vector<uint64_t> ev((size_t)n);
+        std::vector<int64_t> jgs((size_t)n);
+        for (int64_t p = 0; p < n; ++p) {
+            const uint64_t ch = rint_(0, 7) ? (uint64_t)rint_(0, C - 1) : (uint64_t)rint_(0, 4095);
+            jgs[(size_t)p] = j0 + rint_(0, 6 * per);
+            ev[(size_t)p] = (ch << MKID_PKT_CH_SHIFT) | ((uint64_t)rint_(0, (1 << 24) - 1) << MKID_PKT_BASE_SHIFT) |
+                            ((uint64_t)jgs[(size_t)p] & MKID_PKT_TS_MASK);
+        }
+        const size_t cells = (size_t)R * C, slots = cells * K;
+        std::vector<int32_t> image(cells, 0);
+        std::vector<uint64_t> words(slots, 0x5A5A);
+        std::vector<int64_t> stamps(slots, -7);
+        int64_t outside[4] = {0, 0, 0, 0}, ref_outside[4] = {0, 0, 0, 0}, dropped = 0, ref_dropped = 0;
+        CHECK(obs::list_ring_args_ok(ev.data(), n, j0, N, (double)fs, C, w, K, layout, image.data(), outside, words.data(),
+                                     stamps.data(), &dropped),
+              "ring list args");
+        obs::list_ring_host(ev.data(), n, j0, N, (double)fs, C, w, K, layout, image.data(), outside, words.data(),
+                            stamps.data(), &dropped);
+        std::vector<std::vector<std::pair<uint64_t, int64_t>>> dict(cells);
+        for (int64_t p = 0; p < n; ++p) {
+            const int64_t ch = (int64_t)(ev[(size_t)p] >> 52), jg = jgs[(size_t)p], sec = jg * N / fs;
+            if (ch >= C)
+                ++ref_outside[0];
+            else if (sec >= sec_end)
+                ++ref_outside[1];
+            else if (sec < sec0)
+                ++ref_outside[2];
+            else if (sec >= sec0 + R)
+                ++ref_outside[3];
+            else
+                dict[(size_t)(sec % R * C + ch)].push_back({obs::row_word(ev[(size_t)p], obs::microsecond(jg, N, fs), layout), jg});
+        }
+        CHECK(memcmp(outside, ref_outside, sizeof outside) == 0, "ring: outside");
+        bool same = true;
+        for (size_t k = 0; k < cells; ++k) {
+            same = same && image[k] == (int32_t)dict[k].size();
+            for (size_t s = 0; s < dict[k].size(); ++s) {
+                if (s < (size_t)K)
+                    same = same && words[k * K + s] == dict[k][s].first && stamps[k * K + s] == dict[k][s].second;
+                else
+                    ++ref_dropped;
+            }
+            for (size_t s = dict[k].size(); s < (size_t)K; ++s) same = same && words[k * K + s] == 0x5A5A && stamps[k * K + s] == -7;
+        }
+        CHECK(same && dropped == ref_dropped, "ring: rows");
+        // fill: rows made stamp-ascending with distinct stamps, as the device's order gives them
+        for (size_t k = 0; k < cells; ++k) {
+            const int64_t m = obs::row_fill(image[k], K);
+            std::sort(stamps.begin() + (int64_t)(k * K), stamps.begin() + (int64_t)(k * K) + m);
+            for (int64_t s = 1; s < m; ++s)
+                if (stamps[k * K + s] <= stamps[k * K + s - 1]) stamps[k * K + s] = stamps[k * K + s - 1] + 1;
+        }
+        const bool with_dt = rint_(0, 1) != 0;
+        const int64_t j_defer = j0 + rint_(-5, 6 * per);
+        std::vector<float> h((size_t)n), dt((size_t)n), row_h(slots, NAN), row_dt(slots, NAN), ref_h(slots, NAN), ref_dt(slots, NAN);
+        for (int64_t p = 0; p < n; ++p) {
+            h[(size_t)p] = rint_(0, 3) ? (float)rint_(-2000, 2000) / 100.f : NAN;
+            dt[(size_t)p] = (float)rint_(-300, 300) / 100.f;
+        }
+        int64_t fill[2] = {0, 0}, ref_fill[2] = {0, 0};
+        CHECK(obs::fill_ring_args_ok(ev.data(), h.data(), n, j0, N, (double)fs, C, w, K, image.data(), stamps.data(),
+                                     row_h.data(), fill),
+              "ring fill args");
+        obs::fill_ring_host(ev.data(), h.data(), with_dt ? dt.data() : nullptr, n, j0, j_defer, N, (double)fs, C, w, K,
+                            image.data(), stamps.data(), row_h.data(), with_dt ? row_dt.data() : nullptr, fill);
+        for (int64_t p = 0; p < n; ++p) {
+            const int64_t ch = (int64_t)(ev[(size_t)p] >> 52), jg = jgs[(size_t)p], sec = jg * N / fs;
+            if (ch >= C || (!std::isfinite(h[(size_t)p]) && jg >= j_defer)) continue;
+            int64_t at = -1;
+            if (sec >= sec0 && sec < sec_end && sec < sec0 + R) {
+                const size_t k = (size_t)(sec % R * C + ch);
+                for (int64_t s = 0; s < obs::row_fill(image[k], K); ++s)
+                    if (stamps[k * K + s] == jg) at = (int64_t)(k * K) + s;
+            }
+            ++ref_fill[at < 0 ? 1 : 0];
+            if (at < 0) continue;
+            ref_h[(size_t)at] = h[(size_t)p];
+            if (with_dt) ref_dt[(size_t)at] = dt[(size_t)p];
+        }
+        CHECK(fill[0] == ref_fill[0] && fill[1] == ref_fill[1], "ring: fill counters");
+        CHECK(memcmp(row_h.data(), ref_h.data(), slots * 4) == 0 && memcmp(row_dt.data(), ref_dt.data(), slots * 4) == 0,
+              "ring: filled heights");
+        // pack every slot at a cap_out below, at and above its total, then clear it
+        if (rint_(0, 3) == 0) image[(size_t)rint_(0, (int64_t)cells - 1)] = (int32_t)rint_(INT32_MIN, -1);   // a wrapped count
+        for (int32_t slot = 0; slot < R; ++slot) {
+            const int64_t sec = slot + (int64_t)R * rint_(0, 1000);
+            int64_t total = 0;
+            for (int32_t c = 0; c < C; ++c) total += obs::row_fill(image[(size_t)slot * C + c], K);
+            const int64_t caps[5] = {0, std::max<int64_t>(total - 1, 0), total, total + 1, rint_(0, total + 3)};
+            for (const int64_t cap : caps) {
+                std::vector<int32_t> counts((size_t)C, -1);
+                std::vector<int64_t> offsets((size_t)C + 1, -1), ostamps((size_t)cap, -9);
+                std::vector<uint64_t> owords((size_t)cap, 0xA5A5);
+                std::vector<float> oh((size_t)cap, -1.f), odt((size_t)cap, -1.f);
+                int64_t tot[2] = {-1, -1};
+                const bool st = rint_(0, 1) != 0;
+                CHECK(obs::pack_args_ok(sec, R, K, C, image.data(), words.data(), stamps.data(), row_h.data(),
+                                        with_dt ? row_dt.data() : nullptr, cap, counts.data(), offsets.data(),
+                                        cap ? owords.data() : nullptr, st ? ostamps.data() : nullptr,
+                                        cap ? oh.data() : nullptr, with_dt ? odt.data() : nullptr, tot),
+                      "pack args");
+                obs::pack_host(sec, R, K, C, image.data(), words.data(), stamps.data(), row_h.data(),
+                               with_dt ? row_dt.data() : nullptr, cap, counts.data(), offsets.data(), owords.data(),
+                               st ? ostamps.data() : nullptr, oh.data(), with_dt ? odt.data() : nullptr, tot);
+                CHECK(tot[0] == total && tot[1] == std::min(total, cap) && offsets[(size_t)C] == total, "pack: total");
+                int64_t at = 0;
+                bool ok = true;
+                for (int32_t c = 0; c < C; ++c) {
+                    const size_t k = (size_t)slot * C + c;
+                    ok = ok && counts[(size_t)c] == image[k] && offsets[(size_t)c] == at;
+                    for (int64_t i = 0; i < obs::row_fill(image[k], K); ++i, ++at) {
+                        if (at >= cap) continue;
+                        ok = ok && owords[(size_t)at] == words[k * K + i] && (!st || ostamps[(size_t)at] == stamps[k * K + i]) &&
+                             memcmp(&oh[(size_t)at], &row_h[k * K + i], 4) == 0 &&
+                             (!with_dt || memcmp(&odt[(size_t)at], &row_dt[k * K + i], 4) == 0);
+                    }
+                }
+                for (int64_t i = tot[1]; i < cap; ++i) ok = ok && owords[(size_t)i] == 0xA5A5 && oh[(size_t)i] == -1.f;
+                CHECK(ok, "pack: entries");
+            }
+            std::vector<int32_t> image0 = image;
+            std::vector<float> h0 = row_h, dt0 = row_dt;
+            CHECK(obs::clear_args_ok(sec, R, K, C, image.data(), row_h.data()), "clear args");
+            obs::clear_host(sec, R, K, C, image.data(), row_h.data(), with_dt ? row_dt.data() : nullptr);
+            bool ok = true;
+            for (size_t k = 0; k < cells; ++k) {
+                const bool mine = k / C == (size_t)slot;
+                ok = ok && image[k] == (mine ? 0 : image0[k]);
+                for (int64_t i = 0; i < K; ++i) {
+                    const bool hit = mine && i < obs::row_fill(image0[k], K);
+                    uint32_t a, b;
+                    memcpy(&a, &row_h[k * K + i], 4), memcpy(&b, &row_dt[k * K + i], 4);
+                    ok = ok && (hit ? a == obs::kNanBits : memcmp(&a, &h0[k * K + i], 4) == 0);
+                    ok = ok && (hit && with_dt ? b == obs::kNanBits : memcmp(&b, &dt0[k * K + i], 4) == 0);
+                }
+            }
+            CHECK(ok, "clear");
+        }
+    }
+    int32_t i4 = 0;
+    int64_t o2[2] = {0, 0}, s1 = 0;
+    uint64_t w1 = 0;
+    float f1 = 0.f;
+    CHECK(!obs::pack_args_ok(-1, 1, 1, 1, &i4, &w1, &s1, &f1, &f1, 1, &i4, o2, &w1, &s1, &f1, &f1, o2) &&
+              !obs::pack_args_ok(0, 0, 1, 1, &i4, &w1, &s1, &f1, &f1, 1, &i4, o2, &w1, &s1, &f1, &f1, o2) &&
+              !obs::pack_args_ok(0, 1, 0, 1, &i4, &w1, &s1, &f1, &f1, 1, &i4, o2, &w1, &s1, &f1, &f1, o2) &&
+              !obs::pack_args_ok(0, 1, 1, 4097, &i4, &w1, &s1, &f1, &f1, 1, &i4, o2, &w1, &s1, &f1, &f1, o2) &&
+              !obs::pack_args_ok(0, 1, 1, 1, &i4, &w1, &s1, &f1, &f1, -1, &i4, o2, &w1, &s1, &f1, &f1, o2) &&
+              !obs::pack_args_ok(0, 1, 1, 1, &i4, &w1, &s1, &f1, &f1, 1, &i4, o2, nullptr, &s1, &f1, &f1, o2) &&
+              !obs::pack_args_ok(0, 1, 1, 1, &i4, &w1, nullptr, &f1, &f1, 1, &i4, o2, &w1, &s1, &f1, &f1, o2) &&
+              !obs::pack_args_ok(0, 1, 1, 1, &i4, &w1, &s1, &f1, nullptr, 1, &i4, o2, &w1, &s1, &f1, &f1, o2) &&
+              obs::pack_args_ok(0, 1, 1, 1, &i4, &w1, nullptr, &f1, nullptr, 0, &i4, o2, nullptr, nullptr, nullptr, nullptr, o2),
+          "pack argument checks");
+}
+
 int main(int argc, char** argv) {
     const int iters = argc > 1 ? atoi(argv[1]) : 300;
     rng.seed(argc > 2 ? strtoull(argv[2], nullptr, 10) : 12345);
@@ -913,6 +1089,7 @@ int main(int argc, char** argv) {
     fuzz_fit(iters);
     fuzz_observe(iters);
     fuzz_photons(iters);
+    fuzz_pack(iters);
     if (failures) {
         fprintf(stderr, "%d failures\n", failures);
         return 1;
