@@ -616,6 +616,117 @@ int mkid_pack_second_host(int64_t sec, int32_t n_slots, int32_t K, int32_t n_cha
 int mkid_clear_second_host(int64_t sec, int32_t n_slots, int32_t K, int32_t n_channels, int32_t* image,
                            float* row_height, float* row_dt /* nullable */);
 
+/* Energy calibration from laser spectra, and the energy cube. A pulse height is in the units of its
+ * channel's filter output; the laser box (ArconsDashboard.py toggle_laser / do_cal) puts P <= 3 lines
+ * of known energy into every channel's pulse-height spectrum, and their positions give the channel's
+ * height -> energy polynomial and its resolving power. The quick-look (ArconsDashboard.py
+ * image_Worker, :1282-1505) consumes ten energy or wavelength slices per pixel (data.bin). The rules
+ * have one definition, csrc/wavecal_common.h; the kernels are csrc/k_wavecal.hip.
+ *
+ * mkid_spectrum_lines: every channel's lines found and fitted in one call. d_spectra int32
+ * [nch][nbins + 3] is the table of mkid_height_spectra, of which only columns 1 .. nbins are read, a
+ * count n[b] taken as (int64)(uint32); it is never written. d_lo, d_step float32 [nch]: bin b of a
+ * channel starts at lo + b step. nbins 1 .. 16384; n_lines P 1 .. 3; energies (host memory, double
+ * [P], eV): energies[p] belongs to the p-th chosen line in ascending bin order (give them descending
+ * where heights are negative); smooth w 0 .. 64; min_sep >= 1 bins; min_peak any int64; fit_half g
+ * 1 .. 64. Per channel, from its own row and these parameters alone:
+ *   Integer part (exact: device, host twin and any restatement agree bit for bit).
+ *     s[b] = sum_{k = -w .. w} (w + 1 - |k|) n[b + k] in int64, n = 0 outside 0 .. nbins - 1 and
+ *     s = 0 outside too. Bin b is a candidate when s[b] >= min_peak, s[b] > s[b - 1] and
+ *     s[b] >= s[b + 1] (a plateau's lowest bin). Lines are chosen greedily by descending s, ties to
+ *     the lower bin, skipping a candidate with |b - b'| < min_sep of a chosen b', until P are chosen
+ *     or no candidate is left; the chosen lines are then sorted by ascending bin. The fit window of
+ *     line p at bin m is max(m - g, L) .. min(m + g, H), L = floor((m_prev + m) / 2) + 1 (0 for the
+ *     first line), H = floor((m + m_next) / 2) (nbins - 1 for the last found line); only its bins
+ *     with n >= 1 are used. mkid_line_fit: bin = m, peak_s = s[m], nfit = bins used, counts = sum of
+ *     n over the window.
+ *   Float64 part (Caruana's log-parabola with n^2 weights). Per used bin x = (double)(b - m),
+ *     W = (double)n (double)n, y = log((double)n); with W x^k built as ((W x) x) .., the sums
+ *     S_k = sum W x^k (k = 0 .. 4) and T_k = sum (W x^k) y (k = 0 .. 2) are accumulated in ascending
+ *     b by one thread, every product and sum one IEEE operation, never fused. The normal system
+ *     [S0 S1 S2; S1 S2 S3; S2 S3 S4] a = T is solved by the cofactor expansion written in
+ *     wavecal_common.h solve3. With a2 < 0: mu_x = -a1 / (2 a2), sigma_x = sqrt(-1 / (2 a2)),
+ *     amp = exp(a0 - a1^2 / (4 a2)); in height units mu = (double)lo + ((double)m + 0.5 + mu_x)
+ *     (double)step and sigma = sigma_x |step|. A line's fit failed when nfit < 3, a2 >= 0 (or NaN),
+ *     a value is not finite, or |mu_x| > g: mu, sigma and amp are then NaN. Device, host twin and
+ *     a float64 restatement differ only through log (and exp, in amp).
+ *   Calibration, only when all P lines were found and fitted: E(h) = c0 + c1 h + c2 h^2 through
+ *     the points (mu_p, energies[p]): P = 1 c1 = E1 / mu1; P = 2 the line through both; P = 3 the
+ *     parabola by Newton's divided differences expanded in the order written in wavecal_common.h
+ *     calibrate. Resolving power R_p = E_p / (2.3548200450309493 |c1 + 2 c2 mu_p| sigma_p).
+ *   status (mkid_energy_cal): MKID_CAL_FEW_LINES fewer than P lines found; MKID_CAL_FIT_FAILED << p
+ *     the fit of found line p failed; MKID_CAL_BAD_SLOPE dE/dh = c1 + 2 c2 mu changes sign between
+ *     the first and the last line, or is zero or not finite at a line (or c0 is not finite). With any
+ *     bit set c[] and r[] are NaN; r[p] is NaN for p >= P as well. A line not found has bin = -1,
+ *     nfit = counts = peak_s = 0 and NaN floats. n_found = lines found.
+ *   Outputs: d_lines mkid_line_fit [nch][P]; d_cal mkid_energy_cal [nch]; d_cal_f float32 [nch][4] =
+ *     (float)c0, (float)c1, (float)c2, and 1.0f (status 0) or 0.0f: the table mkid_energy_cube reads.
+ * One workgroup per channel with the row staged in LDS (4 nbins bytes), s recomputed from it, the
+ * selection P rounds of a workgroup arg-max without atomics, the fits on one lane per line. Device
+ * pointers only (energies excepted); asynchronous on the context stream; no device-to-host copy, no
+ * synchronisation, no workspace; nch >= 1 need not equal C. Not timed. MKID_E_ARG before any launch:
+ * a null pointer, nch < 1, a parameter outside the ranges above, energies that are not finite and
+ * positive or not distinct.
+ * mkid_spectrum_lines_host: the same rules on host memory through the same definitions; no device,
+ * no context. The same MKID_E_ARG cases.
+ *
+ * mkid_energy_cube: the list, j0, j_defer and d_heights are exactly those of mkid_height_spectra.
+ * d_cal_f float32 [C][4] as above; mode MKID_CUBE_ENERGY or MKID_CUBE_WAVELENGTH; hc, vlo, vinv
+ * float32; nb 1 .. 16384 bins; d_cube int32 [C][nb + 3], caller-owned, zeroed by the caller to start
+ * and continued across calls; d_energy float32 [n], nullable. Per packet with ch < C:
+ *     e = c0 + h (c1 + h c2), each operation rounded once in fp32; the NaN 0x7FC00000 where the
+ *         channel's fourth entry is 0.0f, where h is not finite, or where the arithmetic gives NaN
+ *     d_energy[p] = e (packets with ch >= C leave their entry untouched)
+ *     a packet whose height is not finite and whose jg >= j_defer is skipped here (it comes again
+ *         with the next call's list; j_defer = INT64_MAX skips none)
+ *     otherwise v = e (energy mode) or hc / e rounded once in fp32 (wavelength mode), and
+ *         cube[ch][column(v, vlo, vinv, nb)] += 1 with the column rule of mkid_height_spectra
+ *         (t = v - vlo, u = t vinv): +-inf and NaN (no energy, e = 0 in wavelength mode) land in
+ *         column nb + 2, values below vlo (a negative wavelength among them) in column 0.
+ * The list is only read, so the call composes with mkid_height_spectra over the same list in either
+ * order; every packet with ch < C ends in exactly one cube column over the stream, and a row's total
+ * equals the spectra row's total. Run-length form as mkid_count_photons: two atomics per run of
+ * equal cells in the device's order, correct for any order; only integers are accumulated, so the
+ * cube does not depend on order, chunking or run. Device pointers only; asynchronous on the context
+ * stream; no copy, no synchronisation, no workspace; n == 0 is valid; the counted form reads
+ * min(*d_count, cap) packets. Not timed. MKID_E_ARG before any launch: a null d_cal_f or d_cube, null
+ * d_events or d_heights with n > 0, a null d_count, a negative n, cap or j0, an unknown mode, nb
+ * outside 1 .. 16384.
+ * mkid_energy_cube_host: the same rules on host memory; the same MKID_E_ARG cases, and n_channels
+ * outside 1 .. 4096. */
+#define MKID_CAL_MAX_LINES 3
+#define MKID_CAL_FEW_LINES 1
+#define MKID_CAL_FIT_FAILED 2   /* << p for line p: 2, 4, 8 */
+#define MKID_CAL_BAD_SLOPE 16
+#define MKID_CUBE_ENERGY 0
+#define MKID_CUBE_WAVELENGTH 1
+typedef struct mkid_line_fit {
+    int32_t bin, nfit;
+    int64_t peak_s, counts;
+    double mu, sigma, amp;
+} mkid_line_fit;
+typedef struct mkid_energy_cal {
+    double c[3], r[3];
+    int32_t n_found, status;
+} mkid_energy_cal;
+int mkid_spectrum_lines(mkid_ctx* ctx, const int32_t* d_spectra, const float* d_lo, const float* d_step, int32_t nch,
+                        int32_t nbins, int32_t n_lines, const double* energies /* host */, int32_t smooth,
+                        int32_t min_sep, int64_t min_peak, int32_t fit_half, mkid_line_fit* d_lines,
+                        mkid_energy_cal* d_cal, float* d_cal_f);
+int mkid_spectrum_lines_host(const int32_t* spectra, const float* lo, const float* step, int32_t nch, int32_t nbins,
+                             int32_t n_lines, const double* energies, int32_t smooth, int32_t min_sep,
+                             int64_t min_peak, int32_t fit_half, mkid_line_fit* lines, mkid_energy_cal* cal,
+                             float* cal_f);
+int mkid_energy_cube(mkid_ctx* ctx, const uint64_t* d_events, const float* d_heights, int64_t n, int64_t j0,
+                     int64_t j_defer, const float* d_cal_f, int32_t mode, float hc, float vlo, float vinv, int32_t nb,
+                     int32_t* d_cube, float* d_energy /* nullable */);
+int mkid_energy_cube_counted(mkid_ctx* ctx, const uint64_t* d_events, const float* d_heights, const int64_t* d_count,
+                             int64_t cap, int64_t j0, int64_t j_defer, const float* d_cal_f, int32_t mode, float hc,
+                             float vlo, float vinv, int32_t nb, int32_t* d_cube, float* d_energy /* nullable */);
+int mkid_energy_cube_host(const uint64_t* events, const float* heights, int64_t n, int64_t j0, int64_t j_defer,
+                          int32_t n_channels, const float* cal_f, int32_t mode, float hc, float vlo, float vinv,
+                          int32_t nb, int32_t* cube, float* energy /* nullable */);
+
 /* Pulse capture: the firmware-style capture block between the stream and the template analysis.
  * For every photon packet the phase window around its stamp is copied into a caller-owned,
  * per-channel record bank on the device, for all channels at once and across streamed calls (the

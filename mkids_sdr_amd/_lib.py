@@ -25,6 +25,9 @@ FRONT_AUTO, FRONT_SPLIT = 0, 1
 PKT_CH_SHIFT, PKT_PEAK_SHIFT, PKT_BASE_SHIFT = 52, 40, 28
 PKT_TS_MASK = (1 << 28) - 1
 ROW_WIDE, ROW_REFERENCE = 0, 1       # mkid_list_photons' row word layouts
+CAL_MAX_LINES = 3                    # mkid_spectrum_lines
+CAL_FEW_LINES, CAL_FIT_FAILED, CAL_BAD_SLOPE = 1, 2, 16   # status bits; CAL_FIT_FAILED << p for line p
+CUBE_ENERGY, CUBE_WAVELENGTH = 0, 1  # mkid_energy_cube's modes
 
 
 class MkidError(RuntimeError):
@@ -74,6 +77,23 @@ class ThrStats(ctypes.Structure):
     """mkid_thr_stats: the median and 5 % edges behind a channel's threshold and its raw range."""
     _fields_ = [('med', ctypes.c_double), ('p05', ctypes.c_double), ('lo', ctypes.c_int32), ('hi', ctypes.c_int32)]
 
+
+class LineFit(ctypes.Structure):
+    """mkid_line_fit: one laser line of one channel's pulse-height spectrum."""
+    _fields_ = [('bin', ctypes.c_int32), ('nfit', ctypes.c_int32), ('peak_s', ctypes.c_int64),
+                ('counts', ctypes.c_int64), ('mu', ctypes.c_double), ('sigma', ctypes.c_double),
+                ('amp', ctypes.c_double)]
+
+
+class EnergyCal(ctypes.Structure):
+    """mkid_energy_cal: a channel's height -> energy polynomial, resolving powers and status."""
+    _fields_ = [('c', ctypes.c_double * 3), ('r', ctypes.c_double * 3), ('n_found', ctypes.c_int32),
+                ('status', ctypes.c_int32)]
+
+
+LINE_FIT_DTYPE = [('bin', '<i4'), ('nfit', '<i4'), ('peak_s', '<i8'), ('counts', '<i8'), ('mu', '<f8'),
+                  ('sigma', '<f8'), ('amp', '<f8')]
+ENERGY_CAL_DTYPE = [('c', '<f8', (3,)), ('r', '<f8', (3,)), ('n_found', '<i4'), ('status', '<i4')]
 
 BANK_USED, BANK_FEW_RECORDS, BANK_NONE_PASS1, BANK_NONE_PASS2 = range(4)
 
@@ -157,6 +177,13 @@ _SIGS = {
                                            P, P, P],
     'mkid_pack_second_host': [I64, I32, I32, I32, P, P, P, P, P, I64, P, P, P, P, P, P, P],
     'mkid_clear_second_host': [I64, I32, I32, I32, P, P, P],
+    'mkid_spectrum_lines': [P, P, P, P, I32, I32, I32, P, I32, I32, I64, I32, P, P, P],
+    'mkid_spectrum_lines_host': [P, P, P, I32, I32, I32, P, I32, I32, I64, I32, P, P, P],
+    'mkid_energy_cube': [P, P, P, I64, I64, I64, P, I32, ctypes.c_float, ctypes.c_float, ctypes.c_float, I32, P, P],
+    'mkid_energy_cube_counted': [P, P, P, P, I64, I64, I64, P, I32, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                 I32, P, P],
+    'mkid_energy_cube_host': [P, P, I64, I64, I64, I32, P, I32, ctypes.c_float, ctypes.c_float, ctypes.c_float, I32,
+                              P, P],
     'mkid_set_capture': [P, I32, I32, I32],
     'mkid_capture_pulses': [P, P, I64, I64, P, I64, P, P, P],
     'mkid_capture_pulses_counted': [P, P, I64, I64, P, P, I64, P, P, P],

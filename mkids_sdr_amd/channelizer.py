@@ -521,6 +521,32 @@ class Channelizer:
                                                       int(j0), int(j_defer), _ptr(d_lo), _ptr(d_inv), int(nbins),
                                                       _ptr(d_spectra), _ptr(d_deferred), int(cap_def), _ptr(d_ndef)))
 
+    # ---- laser lines, the energy calibration and the energy cube (include/mkidgpu.h) ---------------
+    def spectrum_lines_device(self, d_spectra, d_lo, d_step, nch, nbins, energies, smooth, min_sep, min_peak,
+                              fit_half, d_lines, d_cal, d_cal_f):
+        """Device pointers; asynchronous on the context stream (mkid_spectrum_lines): the laser lines
+        of channels 0..nch-1 of d_spectra int32 [nch][nbins + 3] into d_lines (_lib.LineFit [nch][P]),
+        d_cal (_lib.EnergyCal [nch]) and d_cal_f float32 [nch][4]; energies: P host values in eV."""
+        e = np.ascontiguousarray(energies, np.float64).ravel()
+        self._chk(self._L.mkid_spectrum_lines(self._h, _ptr(d_spectra), _ptr(d_lo), _ptr(d_step), int(nch), int(nbins),
+                                              int(e.size), _ptr(e), int(smooth), int(min_sep), int(min_peak),
+                                              int(fit_half), _ptr(d_lines), _ptr(d_cal), _ptr(d_cal_f)))
+
+    def energy_cube_device(self, d_events, d_heights, n, j0, j_defer, d_cal_f, mode, hc, vlo, vinv, nb, d_cube,
+                           d_energy=None):
+        """Device pointers; asynchronous on the context stream (mkid_energy_cube): d_cube int32
+        [C][nb + 3] is added to, d_energy float32 [n] (optional) takes every pixel packet's energy."""
+        self._chk(self._L.mkid_energy_cube(self._h, _ptr(d_events), _ptr(d_heights), int(n), int(j0), int(j_defer),
+                                           _ptr(d_cal_f), int(mode), float(hc), float(vlo), float(vinv), int(nb),
+                                           _ptr(d_cube), _ptr(d_energy)))
+
+    def energy_cube_counted(self, d_events, d_heights, d_count, cap, j0, j_defer, d_cal_f, mode, hc, vlo, vinv, nb,
+                            d_cube, d_energy=None):
+        """As energy_cube_device with the packet count read on the device."""
+        self._chk(self._L.mkid_energy_cube_counted(self._h, _ptr(d_events), _ptr(d_heights), _ptr(d_count), int(cap),
+                                                   int(j0), int(j_defer), _ptr(d_cal_f), int(mode), float(hc),
+                                                   float(vlo), float(vinv), int(nb), _ptr(d_cube), _ptr(d_energy)))
+
     def concat_packets(self, d_a, d_na, cap_a, d_b, d_nb, cap_b, d_out, cap_out, d_nout):
         """d_out = the first min(*d_na, cap_a) packets of d_a, then the first min(*d_nb, cap_b) of d_b,
         cut at cap_out; d_nout int64 [2] = {produced, written}. Both counts are read on the device."""

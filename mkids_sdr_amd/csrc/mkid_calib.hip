@@ -1,6 +1,7 @@
 // C ABI of libmkidgpu.so (include/mkidgpu.h): calibration and pulse analysis — replay trigger,
 // template, optimal filter, bank filters, pulse heights, the pulse-height fit, pulse capture, phase thresholds, phase-noise
-// spectra, the synthetic ADC stream, stream copy.
+// spectra, the laser lines of the pulse-height spectra with the energy calibration, the synthetic ADC
+// stream, stream copy.
 // Every entry point that replaces buffers of the context allocates the new ones into locals and
 // moves them in, with the scalars that describe them, only once every allocation has succeeded.
 #include <cmath>
@@ -9,6 +10,7 @@
 #include "mkid_ctx.h"
 #include "noise_common.h"
 #include "thr_common.h"
+#include "wavecal_common.h"
 
 using namespace mkid;
 
@@ -495,6 +497,41 @@ int mkid_phase_noise_spectra_host(const int16_t* raw, int64_t rows, int64_t ld, 
         for (int32_t pos = 0; pos < n; ++pos)
             spec[(int64_t)ch * n + p.bin_of_pos[(size_t)pos]] = noise::finish(acc[(size_t)pos], mul, add);
     }
+    return MKID_OK;
+}
+
+// ---- laser lines and the energy calibration from the pulse-height spectra (wavecal_common.h) -----
+#define LINES_ARGS_MSG                                                                                               \
+    "need pointers, nch >= 1, 1 <= nbins <= 16384, 1 <= n_lines <= 3, finite, positive, distinct energies, "        \
+    "0 <= smooth <= 64, min_sep >= 1, 1 <= fit_half <= 64"
+
+int mkid_spectrum_lines(mkid_ctx* c, const int32_t* d_spectra, const float* d_lo, const float* d_step, int32_t nch,
+                        int32_t nbins, int32_t n_lines, const double* energies, int32_t smooth, int32_t min_sep,
+                        int64_t min_peak, int32_t fit_half, mkid_line_fit* d_lines, mkid_energy_cal* d_cal,
+                        float* d_cal_f) {
+    if (!c) return MKID_E_ARG;
+    if (!wcal::lines_args_ok(d_spectra, d_lo, d_step, nch, nbins, n_lines, energies, smooth, min_sep, fit_half, d_lines,
+                             d_cal, d_cal_f))
+        FAIL(c, MKID_E_ARG, "spectrum_lines: " LINES_ARGS_MSG);
+    HIPCHK(c, hipSetDevice(c->device));
+    WcalLinesArgs a{};
+    a.spectra = d_spectra, a.lo = d_lo, a.step = d_step, a.lines = d_lines, a.cal = d_cal, a.cal_f = d_cal_f;
+    a.min_peak = min_peak, a.nbins = nbins, a.P = n_lines, a.w = smooth, a.min_sep = min_sep, a.g = fit_half;
+    for (int32_t p = 0; p < MKID_CAL_MAX_LINES; ++p) a.E[p] = p < n_lines ? energies[p] : NAN;
+    HIPCHK(c, launch_spectrum_lines(a, nch, c->stream));
+    return MKID_OK;
+}
+
+// The CPU statement of the device call: the loops of wavecal_common.h.
+int mkid_spectrum_lines_host(const int32_t* spectra, const float* lo, const float* step, int32_t nch, int32_t nbins,
+                             int32_t n_lines, const double* energies, int32_t smooth, int32_t min_sep,
+                             int64_t min_peak, int32_t fit_half, mkid_line_fit* lines, mkid_energy_cal* cal,
+                             float* cal_f) {
+    if (!wcal::lines_args_ok(spectra, lo, step, nch, nbins, n_lines, energies, smooth, min_sep, fit_half, lines, cal,
+                             cal_f))
+        return MKID_E_ARG;
+    wcal::lines_host(spectra, lo, step, nch, wcal::make_params(nbins, n_lines, energies, smooth, min_sep, min_peak, fit_half),
+                     lines, cal, cal_f);
     return MKID_OK;
 }
 

@@ -413,6 +413,34 @@ struct NoisePlan;
 hipError_t launch_noise(const int16_t* raw, int64_t ld, int32_t nch, int32_t n_averages, double mul, double add,
                         const plan::NoisePlan& p, const char* tab, double* spec, hipStream_t s);
 
+// mkid_spectrum_lines and mkid_energy_cube (k_wavecal.hip; the rules are wavecal_common.h). The
+// calibration runs one workgroup per channel with the row in dynamic LDS (4 nbins bytes); the cube
+// is a grid-stride pass as k_obs_count's.
+struct WcalLinesArgs {
+    const int32_t* spectra;  // [nch][nbins + 3]
+    const float* lo;         // [nch]
+    const float* step;       // [nch]
+    mkid_line_fit* lines;    // [nch][P]
+    mkid_energy_cal* cal;    // [nch]
+    float* cal_f;            // [nch][4]
+    int64_t min_peak;
+    double E[MKID_CAL_MAX_LINES];
+    int32_t nbins, P, w, min_sep, g, pad;
+};
+hipError_t launch_spectrum_lines(const WcalLinesArgs& a, int32_t nch, hipStream_t s);
+struct WcalCubeArgs {
+    const uint64_t* events;  // [n] wide packets
+    const float* heights;    // [n]
+    const int64_t* d_n;      // nullable: device packet count (min(*d_n, n) packets are read)
+    const float* cal_f;      // [C][4]
+    int32_t* cube;           // [C][nb + 3]
+    float* energy;           // nullable [n]
+    int64_t n, j0, j_defer;
+    int32_t C, nb, mode, ncu;
+    float hc, vlo, vinv, pad;
+};
+hipError_t launch_energy_cube(const WcalCubeArgs& a, hipStream_t s);
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device), thread-safe: the
 // attribute is per device, and several contexts (devices, host threads) may launch concurrently.
 // `mask` is one static per kernel instantiation; the call is idempotent, so a race only repeats it.

@@ -2,10 +2,11 @@
 // per-second count image, the per-channel pulse-height spectra with the list of packets that still
 // wait for their height, joining two counted lists, the per-pixel, per-second photon rows and the
 // heights filled into them, their ring forms, a settled second packed out of its slot and the slot
-// cleared, and the host twins of all but the join. The rules are obs_common.h; the kernels
-// k_observe.hip, k_photons.hip and k_pack.hip.
+// cleared, the energy cube, and the host twins of all but the join. The rules are obs_common.h (the
+// cube's: wavecal_common.h); the kernels k_observe.hip, k_photons.hip, k_pack.hip and k_wavecal.hip.
 #include "mkid_ctx.h"
 #include "obs_common.h"
+#include "wavecal_common.h"
 
 using namespace mkid;
 
@@ -252,6 +253,46 @@ int mkid_clear_second(mkid_ctx* c, int64_t sec, int32_t n_slots, int32_t K, int3
     HIPCHK(c, hipSetDevice(c->device));
     const ClearArgs a{d_image, d_row_height, d_row_dt, obs::slot_of(sec, n_slots) * c->C, c->C, K};
     HIPCHK(c, launch_clear_second(a, c->stream));
+    return MKID_OK;
+}
+
+// ---- the energy cube (wavecal_common.h) -----------------------------------------------------------
+static int energy_cube(mkid_ctx* c, const uint64_t* d_events, const float* d_heights, const int64_t* d_n, int64_t n,
+                       int64_t j0, int64_t j_defer, const float* d_cal_f, int32_t mode, float hc, float vlo, float vinv,
+                       int32_t nb, int32_t* d_cube, float* d_energy) {
+    if (!c) return MKID_E_ARG;
+    if (!wcal::cube_args_ok(d_events, d_heights, n, j0, c->C, d_cal_f, mode, nb, d_cube))
+        FAIL(c, MKID_E_ARG, "energy cube: need pointers, n, j0 >= 0, a known mode, 1 <= nb <= 16384");
+    HIPCHK(c, hipSetDevice(c->device));
+    WcalCubeArgs a{};
+    a.events = d_events, a.heights = d_heights, a.d_n = d_n, a.cal_f = d_cal_f, a.cube = d_cube, a.energy = d_energy;
+    a.n = n, a.j0 = j0, a.j_defer = j_defer, a.C = c->C, a.nb = nb, a.mode = mode, a.ncu = c->ncu;
+    a.hc = hc, a.vlo = vlo, a.vinv = vinv;
+    HIPCHK(c, launch_energy_cube(a, c->stream));
+    return MKID_OK;
+}
+
+int mkid_energy_cube(mkid_ctx* c, const uint64_t* d_events, const float* d_heights, int64_t n, int64_t j0,
+                     int64_t j_defer, const float* d_cal_f, int32_t mode, float hc, float vlo, float vinv, int32_t nb,
+                     int32_t* d_cube, float* d_energy) {
+    return energy_cube(c, d_events, d_heights, nullptr, n, j0, j_defer, d_cal_f, mode, hc, vlo, vinv, nb, d_cube,
+                       d_energy);
+}
+
+int mkid_energy_cube_counted(mkid_ctx* c, const uint64_t* d_events, const float* d_heights, const int64_t* d_count,
+                             int64_t cap, int64_t j0, int64_t j_defer, const float* d_cal_f, int32_t mode, float hc,
+                             float vlo, float vinv, int32_t nb, int32_t* d_cube, float* d_energy) {
+    if (!d_count) return MKID_E_ARG;
+    return energy_cube(c, d_events, d_heights, d_count, cap, j0, j_defer, d_cal_f, mode, hc, vlo, vinv, nb, d_cube,
+                       d_energy);
+}
+
+int mkid_energy_cube_host(const uint64_t* events, const float* heights, int64_t n, int64_t j0, int64_t j_defer,
+                          int32_t n_channels, const float* cal_f, int32_t mode, float hc, float vlo, float vinv,
+                          int32_t nb, int32_t* cube, float* energy) {
+    if (!wcal::cube_args_ok(events, heights, n, j0, n_channels, cal_f, mode, nb, cube)) return MKID_E_ARG;
+    const wcal::CubeRule r{j0, j_defer, n_channels, nb, mode, hc, vlo, vinv};
+    wcal::cube_host(events, heights, n, cal_f, r, cube, energy);
     return MKID_OK;
 }
 

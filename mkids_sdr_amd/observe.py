@@ -11,11 +11,14 @@ synchronisation. With ring=R the rows are a ring of R second slots of bounded me
 which seconds are settled, and drain() packs each into PacketMaster's variable-length form on the
 device (mkid_pack_second), copies only the photons to the host as a Second, and clears the slot for
 reuse (mkid_clear_second), as PacketMaster hands a finished second to its writer
-(PacketMaster.c:329-368).
+(PacketMaster.c:329-368). calibrate() reads the laser lines out of the spectra (wavecal.py), and with
+energy=cal a step also bins every settled photon's energy into the energy or wavelength cube that the
+reference's quick-look consumes (include/mkidgpu.h mkid_energy_cube; quicklook.py): one more call a
+step, between the heights and the spectra.
 """
 import numpy as np
 
-from . import _lib, packets
+from . import _lib, packets, quicklook, wavecal
 
 
 def j_defer(j0, rows, ncoeff, pre, search=0):
@@ -89,10 +92,17 @@ class Observation:
                 n_seconds, the exposure, may be any positive value; drain() takes the settled
                 seconds out as Second objects and frees their slots. image(), rows() and photons()
                 then raise: the data leave through Second. outside() is int64 [4] there.
+    energy      None: no cube, and the calls of a step are exactly those above. A wavecal.EnergyCal
+                for the C channels: every step adds one energy_cube_counted call over the joined
+                list, after the heights and before the spectra, into the cube int32 [C][nb + 3]
+    energy_bins (mode, lo, hi, nb): _lib.CUBE_ENERGY (eV) or _lib.CUBE_WAVELENGTH (hc / e), nb bins
+                from lo to hi, bin width float32((hi - lo) / nb) and vinv its float32 reciprocal;
+                default: the quick-look's ten wavelength slices (quicklook.slice_bins)
+    hc          float32 h c in the units of e times those of the wavelength (default quicklook.H * quicklook.C)
     """
 
     def __init__(self, chan, n_seconds, nbins, lo, step, cap, cap_deferred, fit=False, debug=False,
-                 photon_rows=None, row_layout=_lib.ROW_WIDE, ring=None):
+                 photon_rows=None, row_layout=_lib.ROW_WIDE, ring=None, energy=None, energy_bins=None, hc=None):
         import torch
         if chan.pulse_filter is None:
             raise ValueError('Observation: set the pulse filter first')
@@ -136,6 +146,22 @@ class Observation:
             self.d_pack = None             # the packed second's buffers: a ring's now, else with the first packed()
             if self.R is not None:
                 self._pack_buffers()
+        self.energy = energy
+        if energy is not None:
+            if energy.cal_f.shape != (C, 4):
+                raise ValueError('Observation(energy=cal): the calibration must cover the C channels')
+            self.hc = np.float32(quicklook.H * quicklook.C if hc is None else hc)
+            mode, vlo, vhi, nb = energy_bins if energy_bins is not None else quicklook.slice_bins()
+            self.cube_mode, self.nb = int(mode), int(nb)
+            if self.cube_mode not in (_lib.CUBE_ENERGY, _lib.CUBE_WAVELENGTH) or not 1 <= self.nb <= 16384:
+                raise ValueError('Observation(energy_bins=...): a known mode and 1 <= nb <= 16384')
+            self.vlo = np.float32(vlo)
+            with np.errstate(divide='ignore', invalid='ignore'):
+                self.vinv = np.float32(1) / np.float32((np.float32(vhi) - self.vlo) / np.float32(self.nb))
+            self.d_cal_f = energy.device_table(chan)
+            self.d_cube = z((C, self.nb + 3), torch.int32)
+            self.d_energy = z(max(self.cap_join, 1), torch.float32)
+        self.step_energies = []   # debug with energy: float32 energies of every step's joined list
         self.cur = 0          # d_def[cur], d_ndef[cur]: the packets deferred by the last step
         self.steps = []       # debug: (joined uint64, heights float32, j0, j_defer) of every step
         torch.cuda.synchronize(dev)   # torch's stream made the buffers, the context's stream uses them
@@ -168,6 +194,9 @@ class Observation:
         else:
             heights = ch.pulse_fit_counted if self.fit else ch.pulse_heights_counted
             heights(d_phase, rows, j0, self.d_join, d_nj, self.cap_join, self.d_heights)
+        if self.energy is not None:
+            ch.energy_cube_counted(self.d_join, self.d_heights, d_nj, self.cap_join, j0, jd, self.d_cal_f,
+                                   self.cube_mode, self.hc, self.vlo, self.vinv, self.nb, self.d_cube, self.d_energy)
         ch.stream_copy(self.d_ndef[cur ^ 1], self.d_zero, 16)   # on the context's stream: no torch memset
         ch.height_spectra_counted(self.d_join, self.d_heights, d_nj, self.cap_join, j0, jd, self.d_lo, self.d_inv,
                                   self.nbins, self.d_spectra, self.d_def[cur ^ 1], self.cap_def, self.d_ndef[cur ^ 1])
@@ -188,6 +217,8 @@ class Observation:
             n = int(self.d_njoin[1].item())
             self.steps.append((self.d_join[:n].cpu().numpy().view(np.uint64).copy(),
                                self.d_heights[:n].cpu().numpy().copy(), int(j0), jd))
+            if self.energy is not None:
+                self.step_energies.append(self.d_energy[:n].cpu().numpy().copy())
 
     def _sync(self):
         import torch
@@ -213,6 +244,20 @@ class Observation:
         """int32 [C][nbins + 3]: under, the nbins bins, over, no height."""
         self._sync()
         return self.d_spectra.cpu().numpy()
+
+    def calibrate(self, energies, smooth=2, min_sep=32, min_peak=10, fit_half=12):
+        """The laser lines of the observation's own spectra, found and fitted on the device
+        (wavecal.spectrum_lines) -> wavecal.EnergyCal, whose table a later Observation takes as
+        energy=cal. energies: the line energies in eV in ascending bin order."""
+        return wavecal.spectrum_lines(self.chan, self.d_spectra, self.lo, self.step_width, self.nbins, energies, smooth,
+                                      min_sep, min_peak, fit_half)
+
+    def cube(self):
+        """int32 [C][nb + 3]: under, the nb energy or wavelength bins, over, no energy."""
+        if self.energy is None:
+            raise ValueError('Observation: made without energy')
+        self._sync()
+        return self.d_cube.cpu().numpy()
 
     def edges(self, c):
         """The nbins + 1 nominal bin edges of channel c (float64 from the fp32 lo and step; the

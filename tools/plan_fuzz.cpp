@@ -5,7 +5,8 @@
 // buffers of exactly the planned size, so an undersized plan is an ASan heap overflow, not a
 // silent miscount (the ADVICE r02 scratch-sizing bug is that class).
 // fuzz_observe, fuzz_photons and fuzz_pack drive the observing rules and the host twins' loops
-// (csrc/obs_common.h) likewise.
+// (csrc/obs_common.h) likewise, fuzz_wavecal those of the laser-line calibration and the energy cube
+// (csrc/wavecal_common.h).
 //   plan_fuzz [iterations] [seed]
 #include <stdint.h>
 #include <stdio.h>
@@ -20,6 +21,7 @@
 #include "fit_common.h"
 #include "mkid_plan.h"
 #include "obs_common.h"
+#include "wavecal_common.h"
 
 extern "C" {
 typedef struct {
@@ -1073,6 +1075,156 @@ static void fuzz_pack(int iters) {
           "pack argument checks");
 }
 
+// The laser lines, the calibration and the energy cube (wavecal_common.h lines_host, cube_host) on
+// random rows (empty, single bins, plateaus, Gaussian lines, counts past 2^31), every parameter range's
+// ends, and random packets, heights and calibration tables (NaN, +-inf, not usable); the rows, the
+// result tables and the cube are buffers of exactly the documented sizes, so a bin, line or column
+// outside them is an ASan report. Checked besides: the chosen bins ascend, keep min_sep, are local
+// maxima of the smoothed row at or above min_peak, windows stay inside the row and apart, a status of
+// 0 goes with finite coefficients and resolving powers and the usable flag, any other with NaN, the
+// spectrum is not written, and a row's cube total is its packets that are neither deferred nor of a
+// channel >= C.
+static void fuzz_wavecal(int iters) {
+    namespace obs = mkid::obs;
+    namespace wcal = mkid::wcal;
+    const double E3[3] = {1.26, 1.88, 3.06};
+    const double bad1[2] = {1.0, 1.0}, bad2[1] = {-1.0}, bad3[1] = {NAN}, bad4[1] = {INFINITY}, bad5[1] = {0.0};
+    CHECK(wcal::energies_ok(E3, 3) && wcal::energies_ok(E3, 1) && !wcal::energies_ok(E3, 0) && !wcal::energies_ok(E3, 4) &&
+              !wcal::energies_ok(nullptr, 1) && !wcal::energies_ok(bad1, 2) && !wcal::energies_ok(bad2, 1) &&
+              !wcal::energies_ok(bad3, 1) && !wcal::energies_ok(bad4, 1) && !wcal::energies_ok(bad5, 1),
+          "energies_ok");
+    for (int it = 0; it < iters; ++it) {
+        const int32_t nbins = (int32_t)(rint_(0, 5) == 0 ? (rint_(0, 1) ? obs::kMaxBins : rint_(1, 3)) : rint_(1, 700));
+        const int32_t nch = (int32_t)rint_(1, 4), P = (int32_t)rint_(1, 3);
+        const int32_t w = (int32_t)(rint_(0, 3) == 0 ? (rint_(0, 1) ? 0 : wcal::kMaxSmooth) : rint_(0, 6));
+        const int32_t g = (int32_t)(rint_(0, 3) == 0 ? (rint_(0, 1) ? 1 : wcal::kMaxFitHalf) : rint_(1, 20));
+        const int32_t min_sep = (int32_t)(rint_(0, 4) == 0 ? rint_(1, 2 * (int64_t)nbins) : rint_(1, 40));
+        const int64_t min_peak = rint_(0, 5) == 0 ? rint_(-5, 5) : rint_(1, 200);
+        const int32_t cols = nbins + obs::kExtraCols;
+        std::vector<int32_t> sp((size_t)nch * cols, -7);
+        for (int32_t c = 0; c < nch; ++c) {
+            int32_t* n = sp.data() + (size_t)c * cols + 1;
+            const int kind = (int)rint_(0, 5);
+            for (int32_t b = 0; b < nbins; ++b) n[b] = kind == 0 ? 0 : (kind == 1 ? (int32_t)rint_(0, 6) : 0);
+            if (kind == 2) n[rint_(0, nbins - 1)] = (int32_t)rint_(1, 100000);
+            if (kind == 3)
+                for (int k = 0; k < 3; ++k) {
+                    const int64_t b0 = rint_(0, nbins - 1), len = rint_(1, 9);
+                    for (int64_t b = b0; b < std::min<int64_t>(b0 + len, nbins); ++b) n[b] = 50;
+                }
+            if (kind == 4)
+                for (int k = 0; k < 3; ++k) {
+                    const double mu = (double)rint_(0, nbins - 1), sg = (double)rint_(1, 12), amp = (double)rint_(5, 5000);
+                    for (int32_t b = 0; b < nbins; ++b)
+                        n[b] += (int32_t)(amp * std::exp(-0.5 * (b + 0.5 - mu) * (b + 0.5 - mu) / (sg * sg)) + (double)rint_(0, 3));
+                }
+            if (kind == 5)
+                for (int32_t b = 0; b < nbins; ++b) n[b] = (int32_t)(uint32_t)rint_(0xFFFFF000ll, 0xFFFFFFFFll);
+        }
+        const std::vector<int32_t> sp0 = sp;
+        std::vector<float> lo((size_t)nch), step((size_t)nch);
+        for (auto& x : lo) x = (float)rint_(-300, 300) / 100.f;
+        for (auto& x : step) x = rint_(0, 9) ? (float)rint_(-400, 400) / 1000.f : 0.f;
+        std::vector<mkid_line_fit> lines((size_t)nch * P);
+        std::vector<mkid_energy_cal> cal((size_t)nch);
+        std::vector<float> cal_f((size_t)nch * 4);
+        CHECK(wcal::lines_args_ok(sp.data(), lo.data(), step.data(), nch, nbins, P, E3, w, min_sep, g, lines.data(), cal.data(),
+                                  cal_f.data()),
+              "lines args");
+        wcal::lines_host(sp.data(), lo.data(), step.data(), nch, wcal::make_params(nbins, P, E3, w, min_sep, min_peak, g),
+                         lines.data(), cal.data(), cal_f.data());
+        CHECK(sp == sp0, "the spectrum was written");
+        for (int32_t c = 0; c < nch; ++c) {
+            const int32_t* n = sp.data() + (size_t)c * cols + 1;
+            const mkid_energy_cal& k = cal[(size_t)c];
+            const mkid_line_fit* f = lines.data() + (size_t)c * P;
+            CHECK(k.n_found >= 0 && k.n_found <= P && ((k.status & MKID_CAL_FEW_LINES) != 0) == (k.n_found < P), "n_found %d status %d",
+                  k.n_found, k.status);
+            int32_t bins[3] = {0, 0, 0};
+            for (int32_t p = 0; p < P; ++p) {
+                if (p >= k.n_found) {
+                    CHECK(f[p].bin == -1 && f[p].nfit == 0 && std::isnan(f[p].mu), "a line that was not found");
+                    continue;
+                }
+                bins[p] = f[p].bin;
+                const int64_t s = wcal::smooth_at(n, nbins, w, f[p].bin);
+                CHECK(f[p].bin >= 0 && f[p].bin < nbins && f[p].peak_s == s && s >= min_peak && s > wcal::smooth_at(n, nbins, w, f[p].bin - 1) &&
+                          s >= wcal::smooth_at(n, nbins, w, f[p].bin + 1),
+                      "line %d at bin %d is no candidate", p, f[p].bin);
+                CHECK(p == 0 || f[p].bin - f[p - 1].bin >= min_sep, "lines %d and %d closer than min_sep", p - 1, p);
+                CHECK(std::isnan(f[p].mu) == ((k.status & (MKID_CAL_FIT_FAILED << p)) != 0), "fit bit of line %d", p);
+                CHECK(std::isnan(f[p].mu) == std::isnan(f[p].sigma) && std::isnan(f[p].mu) == std::isnan(f[p].amp), "a fit's NaNs");
+                CHECK(f[p].nfit >= 0 && f[p].nfit <= 2 * g + 1 && f[p].counts >= 0, "nfit %d", f[p].nfit);
+            }
+            for (int32_t p = 0; p < k.n_found; ++p) {
+                const wcal::Window win = wcal::window(bins, k.n_found, p, g, nbins);
+                CHECK(win.b0 >= 0 && win.b1 < nbins && win.b0 <= bins[p] && bins[p] <= win.b1, "window of line %d", p);
+                if (p + 1 < k.n_found) CHECK(win.b1 < wcal::window(bins, k.n_found, p + 1, g, nbins).b0, "windows overlap");
+            }
+            const float* cf = cal_f.data() + (size_t)c * 4;
+            if (k.status == 0) {
+                CHECK(std::isfinite(k.c[0]) && std::isfinite(k.c[1]) && std::isfinite(k.c[2]) && cf[3] == 1.0f, "status 0 without coefficients");
+                for (int32_t p = 0; p < 3; ++p) CHECK(p < P ? k.r[p] >= 0.0 : std::isnan(k.r[p]), "resolving power %d", p);
+            } else {
+                CHECK(std::isnan(k.c[0]) && std::isnan(k.c[1]) && std::isnan(k.c[2]) && std::isnan(k.r[0]) && cf[3] == 0.0f &&
+                          std::isnan(cf[0]),
+                      "a status with coefficients");
+            }
+        }
+        // the cube over random packets with this table (the first C of its rows) and odd ones
+        const int32_t C = nch, nb = (int32_t)(rint_(0, 3) ? rint_(1, 40) : rint_(1, obs::kMaxBins));
+        const int32_t mode = (int32_t)rint_(0, 1);
+        const int64_t n = rint_(0, 200), j0 = rint_(0, 5000), j_defer = rint_(0, 2) ? j0 + rint_(0, 3000) : INT64_MAX;
+        const float specials[] = {NAN, INFINITY, -INFINITY, -0.0f, 0.0f, 1e38f, -1e38f, 3.4e38f};
+        if (rint_(0, 2) == 0)
+            for (auto& x : cal_f) x = rint_(0, 3) ? (float)rint_(-300, 300) / 100.f : specials[rint_(0, 7)];
+        std::vector<uint64_t> ev((size_t)n);
+        std::vector<float> h((size_t)n), energy((size_t)n, -5.f);
+        int64_t want = 0;
+        for (int64_t p = 0; p < n; ++p) {
+            const uint64_t ch = rint_(0, 5) ? (uint64_t)rint_(0, C - 1) : (uint64_t)rint_(0, 4095);
+            const int64_t jg = j0 + rint_(j0 > 0 ? -1 : 0, 6000);
+            ev[(size_t)p] = (ch << MKID_PKT_CH_SHIFT) | ((uint64_t)jg & MKID_PKT_TS_MASK);
+            h[(size_t)p] = rint_(0, 6) ? (float)rint_(-3000, 3000) / 1000.f : specials[rint_(0, 7)];
+            want += (int64_t)ch < C && !obs::deferred(h[(size_t)p], jg, j_defer);
+        }
+        const float hc = 1240.7f, vlo = (float)rint_(-100, 500), vinv = rint_(0, 9) ? (float)rint_(1, 400) / 100.f : specials[rint_(0, 7)];
+        std::vector<int32_t> cube((size_t)C * (nb + obs::kExtraCols), 0);
+        CHECK(wcal::cube_args_ok(ev.data(), h.data(), n, j0, C, cal_f.data(), mode, nb, cube.data()), "cube args");
+        const wcal::CubeRule rule{j0, j_defer, C, nb, mode, hc, vlo, vinv};
+        wcal::cube_host(ev.data(), h.data(), n / 2, cal_f.data(), rule, cube.data(), energy.data());
+        wcal::cube_host(ev.data() + n / 2, h.data() + n / 2, n - n / 2, cal_f.data(), rule, cube.data(), energy.data() + n / 2);
+        int64_t got = 0;
+        for (int32_t v : cube) got += v;
+        CHECK(got == want, "cube total %lld of %lld packets", (long long)got, (long long)want);
+        for (int64_t p = 0; p < n; ++p) {
+            const bool pixel = (int64_t)(ev[(size_t)p] >> MKID_PKT_CH_SHIFT) < C;
+            uint32_t bits;
+            memcpy(&bits, &energy[(size_t)p], 4);
+            CHECK(pixel ? (!std::isnan(energy[(size_t)p]) || bits == obs::kNanBits) : energy[(size_t)p] == -5.f, "energy of packet %lld",
+                  (long long)p);
+        }
+    }
+    int32_t i4 = 0;
+    float f1 = 0.f;
+    uint64_t w1 = 0;
+    mkid_line_fit l1{};
+    mkid_energy_cal c1{};
+    CHECK(!wcal::lines_args_ok(&i4, &f1, &f1, 0, 4, 1, E3, 0, 1, 1, &l1, &c1, &f1) && !wcal::lines_args_ok(&i4, &f1, &f1, 1, 0, 1, E3, 0, 1, 1, &l1, &c1, &f1) &&
+              !wcal::lines_args_ok(&i4, &f1, &f1, 1, 16385, 1, E3, 0, 1, 1, &l1, &c1, &f1) && !wcal::lines_args_ok(&i4, &f1, &f1, 1, 4, 1, E3, 65, 1, 1, &l1, &c1, &f1) &&
+              !wcal::lines_args_ok(&i4, &f1, &f1, 1, 4, 1, E3, -1, 1, 1, &l1, &c1, &f1) && !wcal::lines_args_ok(&i4, &f1, &f1, 1, 4, 1, E3, 0, 0, 1, &l1, &c1, &f1) &&
+              !wcal::lines_args_ok(&i4, &f1, &f1, 1, 4, 1, E3, 0, 1, 0, &l1, &c1, &f1) && !wcal::lines_args_ok(&i4, &f1, &f1, 1, 4, 1, E3, 0, 1, 65, &l1, &c1, &f1) &&
+              !wcal::lines_args_ok(nullptr, &f1, &f1, 1, 4, 1, E3, 0, 1, 1, &l1, &c1, &f1) && !wcal::lines_args_ok(&i4, &f1, &f1, 1, 4, 1, E3, 0, 1, 1, &l1, &c1, nullptr) &&
+              wcal::lines_args_ok(&i4, &f1, &f1, 1, 4, 3, E3, 64, 1, 64, &l1, &c1, &f1),
+          "lines argument checks");
+    CHECK(!wcal::cube_args_ok(&w1, &f1, 1, 0, 64, &f1, 2, 4, &i4) && !wcal::cube_args_ok(&w1, &f1, 1, 0, 64, &f1, 0, 0, &i4) &&
+              !wcal::cube_args_ok(&w1, &f1, 1, 0, 64, &f1, 0, 16385, &i4) && !wcal::cube_args_ok(&w1, &f1, -1, 0, 64, &f1, 0, 4, &i4) &&
+              !wcal::cube_args_ok(&w1, &f1, 1, -1, 64, &f1, 0, 4, &i4) && !wcal::cube_args_ok(nullptr, &f1, 1, 0, 64, &f1, 0, 4, &i4) &&
+              !wcal::cube_args_ok(&w1, &f1, 1, 0, 64, nullptr, 0, 4, &i4) && !wcal::cube_args_ok(&w1, &f1, 1, 0, 4097, &f1, 0, 4, &i4) &&
+              wcal::cube_args_ok(nullptr, nullptr, 0, 0, 64, &f1, 1, 4, &i4),
+          "cube argument checks");
+}
+
 int main(int argc, char** argv) {
     const int iters = argc > 1 ? atoi(argv[1]) : 300;
     rng.seed(argc > 2 ? strtoull(argv[2], nullptr, 10) : 12345);
@@ -1090,6 +1242,7 @@ int main(int argc, char** argv) {
     fuzz_observe(iters);
     fuzz_photons(iters);
     fuzz_pack(iters);
+    fuzz_wavecal(iters / 3 + 1);
     if (failures) {
         fprintf(stderr, "%d failures\n", failures);
         return 1;
