@@ -727,6 +727,90 @@ int mkid_energy_cube_host(const uint64_t* events, const float* heights, int64_t 
                           int32_t n_channels, const float* cal_f, int32_t mode, float hc, float vlo, float vinv,
                           int32_t nb, int32_t* cube, float* energy /* nullable */);
 
+/* Resonator loop fits: every channel's swept IQ loop fitted with the ten-parameter model of the
+ * reference's IQsweep.FitLoopMP (lib/iqsweep.py:141-291, RESDIFF :824-858) in one call, giving Q, f0,
+ * the loop centre (p[8], p[9]), Qc, Qi and the dip depth per channel. Kept from the reference: the
+ * model, the window, the guesses, the bounds, the start recipe, "the lowest chi^2 of S starts wins"
+ * and the derived quantities. The optimiser is this library's own definition, not mpfit (finite
+ * differences, an unseeded generator) and not FitLoopMP's slips (:231 raises, :211 re-slices the
+ * windowed array). The rules have one definition, csrc/loopfit_common.h; the kernel is
+ * csrc/k_loopfit.hip. All data are float64.
+ *
+ * mkid_fit_loops. d_freq, d_i, d_q [nch][fsteps]: a channel's frequencies in Hz and its I and Q with
+ * the zero point already subtracted. d_isd, d_qsd [nch][fsteps], both or neither: weights wI = 1 /
+ * isd, wQ = 1 / qsd (1 when null). d_draws [nch][S][5]: the random numbers of :236-244 for start s, g
+ * (standard normal), u2, u3, u4 in [0, 1), u5 in [-1, 1); the caller supplies them, so the call is a
+ * pure function of its arguments. d_qguess [nch], nullable: a Q from elsewhere (FitMagMP's).
+ * fsteps 12 .. 1024, n_starts S 1 .. 16, max_iter >= 1, ftol > 0. Per channel, integer division:
+ *   Window (bit-identical on device, host twin and any restatement: +, -, x, sqrt, comparisons).
+ *     v[i] = sqrt((I[i] - I[i+1])^2 + (Q[i] - Q[i+1])^2), i = 0 .. nv - 1, nv = fsteps - 2 (the last
+ *     difference is dropped, as the reference does). The smoothed velocity is smooth() of :919-971:
+ *     with top = min(10, nv - 1) the padded signal is s = [2 v[0] - v[top - t] (t = 0 .. top - 2), v,
+ *     2 v[nv-1] - v[nv-1-t] (t = 0 .. 8)] and sv[i] = sum_{j = 0 .. 9} wn[j] s[i + 13 - j], added in
+ *     ascending j from 0.0, i = 0 .. top + nv - 11; wn = hanning(10) / sum is made by the host entry
+ *     (w[j] = 0.5 + 0.5 cos(pi (2 j - 9) / 9), the sum ascending) and handed to the kernel. cidx =
+ *     the first index of the maximum of sv (found with > from sv[0]); low = max(cidx - fsteps / 4,
+ *     0), high = min(cidx + fsteps / 4, fsteps), n = high - low points low .. high - 1.
+ *   Guesses over the window, by one thread in ascending order: Iceng = (max I - min I) / 2 + min I,
+ *     Qceng alike; gI = max I - min I and gQ alike over the whole window (the reference's :211
+ *     re-slice is not kept); ang = atan2(Q[cidx] - Qceng, I[cidx] - Iceng), then ang - pi / 2 when
+ *     ang >= 0, else ang + pi / 2.
+ *   Bounds: Q [5e3, 1e6]; f0 [min x, max x]; aleak [1e-4, 1e2]; ph1 [1, 4e4]; da [-5e3, 5e3]; ang1
+ *     +-1.1 pi; Igain gI -+ 0.5 gI; Qgain [gQ - 0.5 gQ, gQ + 0.5 gI] (:215 as written); Ioff Iceng -+
+ *     0.5 |Iceng|; Qoff Qceng -+ 0.5 |Qceng|. A parameter with lo == hi is held fixed.
+ *   Start s: Q = max(q_s + 20000 g, 5000) with q_s = d_qguess[c], else 10000 s; aleak = 1.1e-4 + 90
+ *     u2; ph1 = 1 + 3e4 u3; da = 9000 u4 - 4500; ang1 = ang for s <= 5, else pi u5; f0 = (sum of x,
+ *     ascending) / n; gains and offsets the guesses; every value clipped into its bounds.
+ *   Model at x: dx = (x - f0) / f0, t = 2 Q dx, den = 1 + t^2, ph = dx ph1,
+ *     re = (da dx + (t^2 / den - 0.5)) + aleak (1 - cos ph), im = t / den - aleak sin ph,
+ *     Ix = re Igain, Qx = im Qgain, mI = (Ix cos ang1 + Qx sin ang1) + Ioff,
+ *     mQ = (Qx cos ang1 - Ix sin ang1) + Qoff. Residuals rI = (I - mI) wI, rQ = (Q - mQ) wQ; chi^2 =
+ *     sum r^2; J = w d(model)/dp analytic, written once in loopfit_common.h point_terms.
+ *   Sums: the 55 entries of A = J^T J (lower triangle), the 10 of g = J^T r and chi^2 are 64 lane
+ *     partials, lane l taking points l, l + 64, .. in ascending order, I half then Q half of each
+ *     point; they combine by the butterfly p[l] = p[l] + p[l ^ m], m = 32, 16, .., 1. Every product
+ *     and sum is one IEEE operation, never fused.
+ *   Solver per start: lambda = 1e-3; D = diag A. The free set is the parameters with hi > lo and D >
+ *     0; (A + lambda diag D) delta = g on the free set by the Cholesky written in loopfit_common.h
+ *     step; a pivot that is not positive and finite: lambda x= 10 and retry. trial = clip(p + delta).
+ *     Accept when chi^2(trial) is finite and smaller: lambda = max(lambda / 10, 1e-12), and stop when
+ *     (chi^2 - chi^2(trial)) / chi^2 <= ftol. Otherwise lambda x= 10. Stop when lambda > 1e12, when
+ *     the free set is empty, or when the start has made max_iter model evaluations (the first, at
+ *     the start itself, included). A start whose first chi^2 is not finite ends there.
+ *   Result: the start with the lowest finite chi^2, ties to the lower s. rad = |p6 + p7| / 4, diam = 2
+ *     rad / (sqrt(p8^2 + p9^2) + rad), qc = p0 / diam, qi = p0 / (1 - diam), dipdb = 20 log10(1 -
+ *     diam). evals = the best start's model evaluations. status bits: MKID_LOOP_NONFINITE a value of
+ *     x, I, Q, wI or wQ in the window is not finite; MKID_LOOP_FLAT gI or gQ is 0; MKID_LOOP_NO_FIT no
+ *     start reached a finite chi^2; MKID_LOOP_MAX_ITER the best start stopped on max_iter. With any
+ *     of the first three every float is NaN, best_start = -1 and evals = 0. cidx, low, high and n are
+ *     always set. d_chisq_all [nch][S], nullable: every start's final chi^2 (NaN for a channel with
+ *     one of the first two bits).
+ * Device, host twin and a float64 restatement differ only through sin, cos, atan2 and log10. One
+ * workgroup of 256 threads per channel, the window staged in LDS once, one wave per start, the
+ * butterfly by __shfl_xor, the Cholesky on one lane, the best start chosen through LDS without
+ * atomics. Device pointers only; asynchronous on the context stream; no copy, no synchronisation, no
+ * workspace. Not timed. MKID_E_ARG before any launch: a null pointer (d_qguess and d_chisq_all
+ * excepted), only one of d_isd and d_qsd, a parameter outside the ranges above.
+ * mkid_fit_loops_host: the same rules on host memory through the same definitions; no device, no
+ * context. The same MKID_E_ARG cases. */
+#define MKID_LOOP_NPAR 10
+#define MKID_LOOP_NONFINITE 1
+#define MKID_LOOP_FLAT 2
+#define MKID_LOOP_NO_FIT 4
+#define MKID_LOOP_MAX_ITER 8
+typedef struct mkid_loop_fit {
+    double p[MKID_LOOP_NPAR];   /* Q, f0, aleak, ph1, da, ang1, Igain, Qgain, Ioff, Qoff */
+    double chisq, qc, qi, dipdb;
+    int32_t cidx, low, high, n, best_start, evals, status, pad;
+} mkid_loop_fit;
+int mkid_fit_loops(mkid_ctx* ctx, const double* d_freq, const double* d_i, const double* d_q,
+                   const double* d_isd /* nullable with d_qsd */, const double* d_qsd, const double* d_draws,
+                   const double* d_qguess /* nullable */, int32_t nch, int32_t fsteps, int32_t n_starts,
+                   int32_t max_iter, double ftol, mkid_loop_fit* d_fits, double* d_chisq_all /* nullable */);
+int mkid_fit_loops_host(const double* freq, const double* i, const double* q, const double* isd, const double* qsd,
+                        const double* draws, const double* qguess, int32_t nch, int32_t fsteps, int32_t n_starts,
+                        int32_t max_iter, double ftol, mkid_loop_fit* fits, double* chisq_all);
+
 /* Pulse capture: the firmware-style capture block between the stream and the template analysis.
  * For every photon packet the phase window around its stamp is copied into a caller-owned,
  * per-channel record bank on the device, for all channels at once and across streamed calls (the

@@ -28,6 +28,8 @@ ROW_WIDE, ROW_REFERENCE = 0, 1       # mkid_list_photons' row word layouts
 CAL_MAX_LINES = 3                    # mkid_spectrum_lines
 CAL_FEW_LINES, CAL_FIT_FAILED, CAL_BAD_SLOPE = 1, 2, 16   # status bits; CAL_FIT_FAILED << p for line p
 CUBE_ENERGY, CUBE_WAVELENGTH = 0, 1  # mkid_energy_cube's modes
+LOOP_NPAR = 10                       # mkid_fit_loops
+LOOP_NONFINITE, LOOP_FLAT, LOOP_NO_FIT, LOOP_MAX_ITER = 1, 2, 4, 8   # its status bits
 
 
 class MkidError(RuntimeError):
@@ -91,9 +93,21 @@ class EnergyCal(ctypes.Structure):
                 ('status', ctypes.c_int32)]
 
 
+class LoopFit(ctypes.Structure):
+    """mkid_loop_fit: one channel's fitted resonator loop."""
+    _fields_ = [('p', ctypes.c_double * 10), ('chisq', ctypes.c_double), ('qc', ctypes.c_double),
+                ('qi', ctypes.c_double), ('dipdb', ctypes.c_double), ('cidx', ctypes.c_int32),
+                ('low', ctypes.c_int32), ('high', ctypes.c_int32), ('n', ctypes.c_int32),
+                ('best_start', ctypes.c_int32), ('evals', ctypes.c_int32), ('status', ctypes.c_int32),
+                ('pad', ctypes.c_int32)]
+
+
 LINE_FIT_DTYPE = [('bin', '<i4'), ('nfit', '<i4'), ('peak_s', '<i8'), ('counts', '<i8'), ('mu', '<f8'),
                   ('sigma', '<f8'), ('amp', '<f8')]
 ENERGY_CAL_DTYPE = [('c', '<f8', (3,)), ('r', '<f8', (3,)), ('n_found', '<i4'), ('status', '<i4')]
+LOOP_FIT_DTYPE = [('p', '<f8', (10,)), ('chisq', '<f8'), ('qc', '<f8'), ('qi', '<f8'), ('dipdb', '<f8'), ('cidx', '<i4'),
+                  ('low', '<i4'), ('high', '<i4'), ('n', '<i4'), ('best_start', '<i4'), ('evals', '<i4'),
+                  ('status', '<i4'), ('pad', '<i4')]
 
 BANK_USED, BANK_FEW_RECORDS, BANK_NONE_PASS1, BANK_NONE_PASS2 = range(4)
 
@@ -184,6 +198,8 @@ _SIGS = {
                                  I32, P, P],
     'mkid_energy_cube_host': [P, P, I64, I64, I64, I32, P, I32, ctypes.c_float, ctypes.c_float, ctypes.c_float, I32,
                               P, P],
+    'mkid_fit_loops': [P, P, P, P, P, P, P, P, I32, I32, I32, I32, ctypes.c_double, P, P],
+    'mkid_fit_loops_host': [P, P, P, P, P, P, P, I32, I32, I32, I32, ctypes.c_double, P, P],
     'mkid_set_capture': [P, I32, I32, I32],
     'mkid_capture_pulses': [P, P, I64, I64, P, I64, P, P, P],
     'mkid_capture_pulses_counted': [P, P, I64, I64, P, P, I64, P, P, P],

@@ -547,6 +547,21 @@ class Channelizer:
                                                    int(j0), int(j_defer), _ptr(d_cal_f), int(mode), float(hc),
                                                    float(vlo), float(vinv), int(nb), _ptr(d_cube), _ptr(d_energy)))
 
+    # ---- resonator loop fits (include/mkidgpu.h mkid_fit_loops) --------------------------------------
+    def fit_loops_device(self, d_freq, d_i, d_q, d_isd, d_qsd, d_draws, d_qguess, nch, fsteps, n_starts, max_iter,
+                         ftol, d_fits, d_chisq_all=None):
+        """Device pointers; asynchronous on the context stream (mkid_fit_loops): float64 d_freq, d_i,
+        d_q [nch][fsteps], d_isd, d_qsd (both or None), d_draws [nch][S][5], d_qguess [nch] or None,
+        into d_fits (_lib.LoopFit [nch]) and d_chisq_all float64 [nch][S] (optional)."""
+        self._chk(self._L.mkid_fit_loops(self._h, _ptr(d_freq), _ptr(d_i), _ptr(d_q), _ptr(d_isd), _ptr(d_qsd),
+                                         _ptr(d_draws), _ptr(d_qguess), int(nch), int(fsteps), int(n_starts),
+                                         int(max_iter), float(ftol), _ptr(d_fits), _ptr(d_chisq_all)))
+
+    def fit_loops(self, freq, I, Q, draws, **kw):
+        """Host convenience: loopfit.fit_loops on this context -> dict of arrays by field."""
+        from . import loopfit
+        return loopfit.fit_loops(self, freq, I, Q, draws, **kw)
+
     def concat_packets(self, d_a, d_na, cap_a, d_b, d_nb, cap_b, d_out, cap_out, d_nout):
         """d_out = the first min(*d_na, cap_a) packets of d_a, then the first min(*d_nb, cap_b) of d_b,
         cut at cap_out; d_nout int64 [2] = {produced, written}. Both counts are read on the device."""

@@ -1,12 +1,13 @@
 // C ABI of libmkidgpu.so (include/mkidgpu.h): calibration and pulse analysis — replay trigger,
 // template, optimal filter, bank filters, pulse heights, the pulse-height fit, pulse capture, phase thresholds, phase-noise
-// spectra, the laser lines of the pulse-height spectra with the energy calibration, the synthetic ADC
-// stream, stream copy.
+// spectra, the laser lines of the pulse-height spectra with the energy calibration, the resonator loop
+// fits, the synthetic ADC stream, stream copy.
 // Every entry point that replaces buffers of the context allocates the new ones into locals and
 // moves them in, with the scalars that describe them, only once every allocation has succeeded.
 #include <cmath>
 
 #include "fit_common.h"
+#include "loopfit_common.h"
 #include "mkid_ctx.h"
 #include "noise_common.h"
 #include "thr_common.h"
@@ -532,6 +533,35 @@ int mkid_spectrum_lines_host(const int32_t* spectra, const float* lo, const floa
         return MKID_E_ARG;
     wcal::lines_host(spectra, lo, step, nch, wcal::make_params(nbins, n_lines, energies, smooth, min_sep, min_peak, fit_half),
                      lines, cal, cal_f);
+    return MKID_OK;
+}
+
+// ---- resonator loop fits (loopfit_common.h) ----------------------------------------------------------
+#define LOOPS_ARGS_MSG                                                                                             \
+    "need pointers (d_isd and d_qsd both or neither), nch >= 1, 12 <= fsteps <= 1024, 1 <= n_starts <= 16, "      \
+    "max_iter >= 1, ftol > 0"
+
+int mkid_fit_loops(mkid_ctx* c, const double* d_freq, const double* d_i, const double* d_q, const double* d_isd,
+                   const double* d_qsd, const double* d_draws, const double* d_qguess, int32_t nch, int32_t fsteps,
+                   int32_t n_starts, int32_t max_iter, double ftol, mkid_loop_fit* d_fits, double* d_chisq_all) {
+    if (!c) return MKID_E_ARG;
+    if (!lfit::args_ok(d_freq, d_i, d_q, d_isd, d_qsd, d_draws, nch, fsteps, n_starts, max_iter, ftol, d_fits))
+        FAIL(c, MKID_E_ARG, "fit_loops: " LOOPS_ARGS_MSG);
+    HIPCHK(c, hipSetDevice(c->device));
+    LoopfitArgs a{};
+    a.freq = d_freq, a.i = d_i, a.q = d_q, a.isd = d_isd, a.qsd = d_qsd, a.draws = d_draws, a.qguess = d_qguess;
+    a.fits = d_fits, a.chisq_all = d_chisq_all, a.ftol = ftol, a.fsteps = fsteps, a.S = n_starts, a.max_iter = max_iter;
+    lfit::window_weights(a.wn);
+    HIPCHK(c, launch_fit_loops(a, nch, c->stream));
+    return MKID_OK;
+}
+
+// The CPU statement of the device call: the loops of loopfit_common.h.
+int mkid_fit_loops_host(const double* freq, const double* i, const double* q, const double* isd, const double* qsd,
+                        const double* draws, const double* qguess, int32_t nch, int32_t fsteps, int32_t n_starts,
+                        int32_t max_iter, double ftol, mkid_loop_fit* fits, double* chisq_all) {
+    if (!lfit::args_ok(freq, i, q, isd, qsd, draws, nch, fsteps, n_starts, max_iter, ftol, fits)) return MKID_E_ARG;
+    lfit::fit_host(freq, i, q, isd, qsd, draws, qguess, nch, fsteps, n_starts, max_iter, ftol, fits, chisq_all);
     return MKID_OK;
 }
 

@@ -441,6 +441,24 @@ struct WcalCubeArgs {
 };
 hipError_t launch_energy_cube(const WcalCubeArgs& a, hipStream_t s);
 
+// mkid_fit_loops (k_loopfit.hip; the rules are loopfit_common.h): one workgroup per channel, the
+// window in static LDS, one wave per start.
+struct LoopfitArgs {
+    const double* freq;    // [nch][fsteps]
+    const double* i;       // [nch][fsteps]
+    const double* q;       // [nch][fsteps]
+    const double* isd;     // nullable with qsd
+    const double* qsd;
+    const double* draws;   // [nch][S][5]
+    const double* qguess;  // nullable [nch]
+    mkid_loop_fit* fits;   // [nch]
+    double* chisq_all;     // nullable [nch][S]
+    double wn[10];         // hanning(10) / sum, made on the host
+    double ftol;
+    int32_t fsteps, S, max_iter, pad;
+};
+hipError_t launch_fit_loops(const LoopfitArgs& a, int32_t nch, hipStream_t s);
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device), thread-safe: the
 // attribute is per device, and several contexts (devices, host threads) may launch concurrently.
 // `mask` is one static per kernel instantiation; the call is idempotent, so a race only repeats it.

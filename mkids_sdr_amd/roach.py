@@ -540,6 +540,27 @@ class RoachSetup:
         self.I, self.Q = I, Q
         return I, Q
 
+    def fitLoops(self, starts=10, seed=0, use_centers=False, max_iter=200, ftol=1e-10):
+        """IQsweep.FitLoopMP (lib/iqsweep.py:141-291) for every swept tone at once on the device
+        (Channelizer.fit_loops, include/mkidgpu.h mkid_fit_loops), after sweepLOready, on self.f_span,
+        self.I, self.Q: Q, f0, loop centre, Qc, Qi and dip depth per tone, kept in self.loop_fits (a
+        dict of arrays by field, loopfit.FIELDS). Only with use_centers=True are the IQ centres of
+        the tones whose fit has no failure bit set from the fitted p[8], p[9] in place of
+        findIQcenters' midpoints; the default writes no register and changes no state but
+        self.loop_fits."""
+        from . import loopfit
+        nf = int(self.N_freqs)
+        self.loop_fits = self.roach.channelizer().fit_loops(
+            np.asarray(self.f_span, np.float64), self.I, self.Q, loopfit.draws(nf, starts, seed), max_iter=max_iter,
+            ftol=ftol)
+        if use_centers:
+            from . import _lib
+            bad = _lib.LOOP_NONFINITE | _lib.LOOP_FLAT | _lib.LOOP_NO_FIT
+            for j in range(nf):
+                if not self.loop_fits['status'][j] & bad:
+                    self.iq_centers[j] = complex(self.loop_fits['p'][j, 8], self.loop_fits['p'][j, 9])
+        return self.loop_fits
+
 
 class RoachPulses:
     """ROACH_Pulses.py AppForm trigger-setup and readback methods."""

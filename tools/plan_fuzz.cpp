@@ -6,7 +6,7 @@
 // silent miscount (the ADVICE r02 scratch-sizing bug is that class).
 // fuzz_observe, fuzz_photons and fuzz_pack drive the observing rules and the host twins' loops
 // (csrc/obs_common.h) likewise, fuzz_wavecal those of the laser-line calibration and the energy cube
-// (csrc/wavecal_common.h).
+// (csrc/wavecal_common.h), fuzz_loopfit the resonator loop fits (csrc/loopfit_common.h).
 //   plan_fuzz [iterations] [seed]
 #include <stdint.h>
 #include <stdio.h>
@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "fit_common.h"
+#include "loopfit_common.h"
 #include "mkid_plan.h"
 #include "obs_common.h"
 #include "wavecal_common.h"
@@ -1225,6 +1226,122 @@ static void fuzz_wavecal(int iters) {
           "cube argument checks");
 }
 
+// The resonator loop fits (loopfit_common.h fit_host) over random and degenerate sweeps: resonator
+// loops with noise, constant sweeps, straight lines, zero frequencies, NaN, +-inf and huge samples,
+// zero, negative and non-finite standard deviations, draws far outside their ranges, every shape's
+// ends (fsteps 12 and 1024, S 1 and 16, max_iter 1). All arrays are buffers of exactly the documented
+// sizes, so a point, start or channel outside them is an ASan report. Checked besides: the window
+// lies inside the sweep around cidx with at most 2 (fsteps / 4) points, a failure status goes with
+// NaN floats, best_start -1 and evals 0, any other with finite parameters inside their bounds, a
+// finite chi^2 that is the lowest of chisq_all with ties to the lower start, and 1 <= evals <=
+// max_iter with the max_iter bit only when evals == max_iter; the inputs are not written.
+static void fuzz_loopfit(int iters) {
+    namespace lfit = mkid::lfit;
+    std::uniform_real_distribution<double> U(0.0, 1.0);
+    std::normal_distribution<double> N(0.0, 1.0);
+    const double odd[] = {NAN, INFINITY, -INFINITY, 0.0, -0.0, 1e300, -1e300, 1e-300};
+    for (int it = 0; it < iters; ++it) {
+        const int32_t nch = (int32_t)rint_(1, 3);
+        const int32_t fsteps = (int32_t)(rint_(0, 7) == 0 ? (rint_(0, 1) ? lfit::kMinSteps : lfit::kMaxSteps) : rint_(12, 140));
+        const int32_t S = (int32_t)(rint_(0, 5) == 0 ? (rint_(0, 1) ? 1 : lfit::kMaxStarts) : rint_(1, 6));
+        const int32_t max_iter = (int32_t)(rint_(0, 5) == 0 ? 1 : rint_(2, 25));
+        const bool sd = rint_(0, 1) != 0, qg = rint_(0, 2) == 0;
+        const size_t np = (size_t)nch * fsteps;
+        std::vector<double> x(np), I(np), Q(np), isd(sd ? np : 0), qsd(sd ? np : 0), draws((size_t)nch * S * 5), qguess(qg ? nch : 0);
+        for (int32_t c = 0; c < nch; ++c) {
+            const int kind = (int)rint_(0, 6);
+            const double Qr = 15e3 + 65e3 * U(rng), f0 = 4e9 + 2e9 * U(rng), R = 2e3 + 2e4 * U(rng);
+            const double span = (4.0 + 4.0 * U(rng)) * f0 / Qr, off = (U(rng) - 0.5) * span;
+            const double ci = (2.0 + 3.0 * U(rng)) * R * (rint_(0, 1) ? 1.0 : -1.0), cq = (2.0 + 3.0 * U(rng)) * R * (rint_(0, 1) ? 1.0 : -1.0);
+            const double ang = 6.0 * U(rng) - 3.0;
+            for (int32_t i = 0; i < fsteps; ++i) {
+                const size_t k = (size_t)c * fsteps + i;
+                x[k] = kind == 3 ? 0.0 : f0 + off + span * ((double)i / (fsteps - 1) - 0.5);
+                const double t = 2.0 * Qr * (x[k] - f0) / f0, den = 1.0 + t * t;
+                const double re = (t * t / den - 0.5) * 2.0 * R, im = t / den * 2.0 * R;
+                I[k] = re * std::cos(ang) + im * std::sin(ang) + ci + 0.01 * R * N(rng);
+                Q[k] = -re * std::sin(ang) + im * std::cos(ang) + cq + 0.01 * R * N(rng);
+                if (kind == 1) I[k] = 12.0, Q[k] = -3.0;                     // a constant sweep
+                if (kind == 2) I[k] = (double)i, Q[k] = 5.0;                 // a straight line, flat in Q
+                if (kind == 4 && rint_(0, 9) == 0) (rint_(0, 1) ? I[k] : Q[k]) = odd[rint_(0, 7)];
+                if (kind == 5 && rint_(0, 9) == 0) x[k] = odd[rint_(0, 7)];
+                if (kind == 6) I[k] = std::rint(I[k]) - std::rint(ci), Q[k] = std::rint(Q[k]);   // centres near an axis
+                if (sd) {
+                    isd[k] = rint_(0, 30) ? 0.01 * R * (0.5 + U(rng)) : odd[rint_(0, 7)];
+                    qsd[k] = rint_(0, 30) ? 0.01 * R * (0.5 + U(rng)) : -1.0;
+                }
+            }
+            if (qg) qguess[(size_t)c] = rint_(0, 5) ? Qr * (0.5 + U(rng)) : odd[rint_(0, 7)];
+        }
+        for (auto& d : draws) d = rint_(0, 40) ? 2.0 * U(rng) - 1.0 : (rint_(0, 1) ? odd[rint_(0, 7)] : 50.0 * N(rng));
+        const std::vector<double> x0 = x, I0 = I, Q0 = Q;
+        std::vector<mkid_loop_fit> fits((size_t)nch);
+        std::vector<double> call((size_t)nch * S, -7.0);
+        const double ftol = rint_(0, 3) ? 1e-8 : 1e-2;
+        const bool want_all = rint_(0, 3) != 0;
+        CHECK(lfit::args_ok(x.data(), I.data(), Q.data(), sd ? isd.data() : nullptr, sd ? qsd.data() : nullptr, draws.data(), nch,
+                            fsteps, S, max_iter, ftol, fits.data()),
+              "loop fit args");
+        lfit::fit_host(x.data(), I.data(), Q.data(), sd ? isd.data() : nullptr, sd ? qsd.data() : nullptr, draws.data(),
+                       qg ? qguess.data() : nullptr, nch, fsteps, S, max_iter, ftol, fits.data(), want_all ? call.data() : nullptr);
+        CHECK(memcmp(x.data(), x0.data(), np * 8) == 0 && memcmp(I.data(), I0.data(), np * 8) == 0 &&
+                  memcmp(Q.data(), Q0.data(), np * 8) == 0,
+              "the sweep was written");
+        for (int32_t c = 0; c < nch; ++c) {
+            const mkid_loop_fit& f = fits[(size_t)c];
+            const int32_t q = fsteps / 4;
+            CHECK(f.cidx >= 0 && f.cidx <= fsteps - 3 && f.low == std::max(f.cidx - q, 0) && f.high == std::min(f.cidx + q, fsteps) &&
+                      f.n == f.high - f.low && f.n >= 3 && f.n <= 2 * q && f.n <= lfit::kMaxWindow && f.pad == 0,
+                  "window %d %d %d %d of %d", f.cidx, f.low, f.high, f.n, fsteps);
+            const int32_t fail = MKID_LOOP_NONFINITE | MKID_LOOP_FLAT | MKID_LOOP_NO_FIT;
+            CHECK((f.status & ~(fail | MKID_LOOP_MAX_ITER)) == 0, "status %d", f.status);
+            if (f.status & fail) {
+                bool nan = std::isnan(f.chisq) && std::isnan(f.qc) && std::isnan(f.qi) && std::isnan(f.dipdb);
+                for (int i = 0; i < lfit::kNP; ++i) nan = nan && std::isnan(f.p[i]);
+                CHECK(nan && f.best_start == -1 && f.evals == 0 && (f.status & MKID_LOOP_MAX_ITER) == 0, "a failed fit with results");
+                if (want_all)
+                    for (int32_t s = 0; s < S; ++s) CHECK(!std::isfinite(call[(size_t)c * S + s]), "a failed fit with a finite start");
+                continue;
+            }
+            CHECK(f.best_start >= 0 && f.best_start < S && f.evals >= 1 && f.evals <= max_iter &&
+                      (((f.status & MKID_LOOP_MAX_ITER) != 0) ? f.evals == max_iter : true) && std::isfinite(f.chisq) && f.chisq >= 0.0,
+                  "start %d evals %d status %d", f.best_start, f.evals, f.status);
+            const double* xw = x.data() + (size_t)c * fsteps;
+            const double xlo = *std::min_element(xw + f.low, xw + f.high), xhi = *std::max_element(xw + f.low, xw + f.high);
+            CHECK(f.p[0] >= 5e3 && f.p[0] <= 1e6 && f.p[1] >= xlo && f.p[1] <= xhi && f.p[2] >= 1e-4 &&
+                      f.p[2] <= 1e2 && f.p[3] >= 1.0 && f.p[3] <= 4e4 && std::fabs(f.p[4]) <= 5e3 && std::fabs(f.p[5]) <= 1.1 * lfit::kPi + 1e-12 &&
+                      f.p[6] > 0.0 && f.p[7] > 0.0 && std::isfinite(f.p[8]) && std::isfinite(f.p[9]),
+                  "parameters outside their bounds");
+            if (want_all)
+                for (int32_t s = 0; s < S; ++s) {
+                    const double v = call[(size_t)c * S + s];
+                    CHECK(!std::isfinite(v) || v > f.chisq || (v == f.chisq && s >= f.best_start), "start %d beats the best", s);
+                    if (s == f.best_start) CHECK(v == f.chisq, "chisq_all of the best start");
+                }
+        }
+    }
+    double d1 = 1.0, w[lfit::kWin], sum = 0.0;
+    mkid_loop_fit f1{};
+    lfit::window_weights(w);
+    for (double v : w) sum += v;
+    CHECK(w[0] == w[9] && std::fabs(w[0]) < 1e-16 && std::fabs(sum - 1.0) < 1e-15, "window weights");
+    CHECK(!lfit::args_ok(nullptr, &d1, &d1, nullptr, nullptr, &d1, 1, 12, 1, 1, 1e-6, &f1) &&
+              !lfit::args_ok(&d1, &d1, &d1, &d1, nullptr, &d1, 1, 12, 1, 1, 1e-6, &f1) &&
+              !lfit::args_ok(&d1, &d1, &d1, nullptr, &d1, &d1, 1, 12, 1, 1, 1e-6, &f1) &&
+              !lfit::args_ok(&d1, &d1, &d1, nullptr, nullptr, nullptr, 1, 12, 1, 1, 1e-6, &f1) &&
+              !lfit::args_ok(&d1, &d1, &d1, nullptr, nullptr, &d1, 1, 12, 1, 1, 1e-6, nullptr) &&
+              !lfit::args_ok(&d1, &d1, &d1, nullptr, nullptr, &d1, 0, 12, 1, 1, 1e-6, &f1) &&
+              !lfit::args_ok(&d1, &d1, &d1, nullptr, nullptr, &d1, 1, 11, 1, 1, 1e-6, &f1) &&
+              !lfit::args_ok(&d1, &d1, &d1, nullptr, nullptr, &d1, 1, 1025, 1, 1, 1e-6, &f1) &&
+              !lfit::args_ok(&d1, &d1, &d1, nullptr, nullptr, &d1, 1, 12, 0, 1, 1e-6, &f1) &&
+              !lfit::args_ok(&d1, &d1, &d1, nullptr, nullptr, &d1, 1, 12, 17, 1, 1e-6, &f1) &&
+              !lfit::args_ok(&d1, &d1, &d1, nullptr, nullptr, &d1, 1, 12, 1, 0, 1e-6, &f1) &&
+              !lfit::args_ok(&d1, &d1, &d1, nullptr, nullptr, &d1, 1, 12, 1, 1, 0.0, &f1) &&
+              !lfit::args_ok(&d1, &d1, &d1, nullptr, nullptr, &d1, 1, 12, 1, 1, NAN, &f1) &&
+              lfit::args_ok(&d1, &d1, &d1, &d1, &d1, &d1, 1, 1024, 16, 1, 1e-6, &f1),
+          "loop fit argument checks");
+}
+
 int main(int argc, char** argv) {
     const int iters = argc > 1 ? atoi(argv[1]) : 300;
     rng.seed(argc > 2 ? strtoull(argv[2], nullptr, 10) : 12345);
@@ -1243,6 +1360,7 @@ int main(int argc, char** argv) {
     fuzz_photons(iters);
     fuzz_pack(iters);
     fuzz_wavecal(iters / 3 + 1);
+    fuzz_loopfit(iters / 3 + 1);
     if (failures) {
         fprintf(stderr, "%d failures\n", failures);
         return 1;
