@@ -979,6 +979,120 @@ int mkid_phase_noise_spectra(mkid_ctx* ctx, const int16_t* d_raw, int64_t rows, 
 int mkid_phase_noise_spectra_host(const int16_t* raw, int64_t rows, int64_t ld, int32_t nch,
                                   int32_t n_averages, double scale, double norm1, double* spec);
 
+/* Welch power spectral densities of two real float64 series per channel in one call:
+ * matplotlib.mlab.psd's defaults (Hanning window, no detrending, one-sided, density scaling,
+ * noverlap = nfft / 2), which is how IQsweep.AnalyzeNoise (lib/iqsweep.py:792-801) calls it. For
+ * channel c, series a = d_a[c ld + j] and b = d_b[c ld + j] (d_b null: all zeros), j < n:
+ *   window     w[j] = 0.5 - 0.5 cos(2 pi j / (nfft - 1)), S2 = sum_j w[j]^2 added in ascending j in
+ *              float64 with Kahan's compensation (from s = c = 0.0: y = w^2 - c, t = s + y,
+ *              c = (t - s) - y, s = t; the plain sum is 2.4e-14 off at nfft = 262144, which scales
+ *              every bin); made once per nfft by the host entry and handed to the kernels as a table
+ *   segments   nseg = (n - nfft / 2) / (nfft / 2) (integer division); segment s covers samples
+ *              s nfft / 2 .. s nfft / 2 + nfft - 1; samples beyond the last segment are never read
+ *   transform  z[j] = (a[j] w[j], b[j] w[j]), Z = DFT_nfft(z) (np.fft.fft's sign). With Z1 = Z[k] and
+ *              Z2 = Z[(nfft - k) mod nfft], |A[k]|^2 = ((Z1.re + Z2.re)^2 + (Z1.im - Z2.im)^2) / 4 and
+ *              |B[k]|^2 = ((Z1.re - Z2.re)^2 + (Z1.im + Z2.im)^2) / 4, k = 0 .. nfft / 2
+ *   sums       the segments are added in strips of MKID_WELCH_STRIP consecutive segments: a strip's
+ *              powers in ascending segment order from 0.0, then the strips in ascending order from
+ *              0.0; no floating-point atomics
+ *   density    P[k] = (acc[k] / nseg) / (fs S2), times 2 for 0 < k < nfft / 2
+ * Everything is float64, and every product and sum is one rounded IEEE operation, never fused. The
+ * transform is decimation in frequency, in place, in passes of radix 8 while the remaining length
+ * allows, then one of radix 4 or 2; a pass on blocks of L elements multiplies output t of the
+ * butterfly at offset j by W_L^{j t} (skipped for j = 0), read from the nfft-entry table W_nfft^i =
+ * (cos, -sin)(2 pi i / nfft) that the host entry makes in float64.
+ *   nfft <= MKID_WELCH_LDS_MAX_N: one workgroup holds a segment in LDS (complex float64, 64 KiB).
+ *   nfft larger: a four-step transform nfft = n1 n2 with n1 = 2^floor(log2(nfft) / 2), n2 = nfft / n1
+ *              (8192 = 64 x 128, 32768 = 128 x 256, 262144 = 512 x 512), a function of nfft alone:
+ *              sample j = n2 j1 + j2, bin k = k1 + n1 k2. The n2 column transforms of length n1 (over
+ *              j1), the twiddle W_nfft^{j2 k1} (skipped where j2 k1 = 0), then the n1 row transforms of
+ *              length n2 (over j2), through a workspace in global memory. Bin nfft - k lies in row
+ *              (n1 - k1) mod n1, so the powers are taken from pairs of rows.
+ * Kernel and host twin share one definition of all of this (csrc/welch_common.h), so they give the
+ * same bits, and a channel's outputs depend only on its own samples, n, nfft and fs: not on nch,
+ * ld, alignment, group or its neighbours. All-zero input gives exactly 0.0 in every bin.
+ *   - mkid_welch_psd: device pointers only, asynchronous on the context stream. d_pa, d_pb (nullable)
+ *     are [nch][nfft / 2 + 1]. The workspace (strip sums, and the four-step transform's segments) is
+ *     owned by the context and bounded by a fixed byte budget (256 MiB, unless one channel alone
+ *     needs more), not by nch n: channels are worked on in groups of `group` (0: as many as the
+ *     budget holds; a larger request is cut to that). It is grown on demand (allocate, synchronise
+ *     once, move in), and the tables are kept per nfft: a repeated call makes no device-to-host
+ *     copy and no synchronisation. MKID_E_ARG before any launch, the outputs untouched: a null
+ *     required pointer, nfft no power of two or outside 8 .. MKID_WELCH_MAX_N, n < nfft or
+ *     n > 2^31 - 1, ld < n, nch < 1, group < 0, fs not finite or <= 0. Not timed (no MKID_K_ id).
+ *   - mkid_welch_psd_host: the same rule on host memory through the same definitions; needs no
+ *     device and no context. The same MKID_E_ARG cases. */
+#define MKID_WELCH_STRIP 32
+#define MKID_WELCH_LDS_MAX_N 4096
+#define MKID_WELCH_MAX_N 262144
+int mkid_welch_psd(mkid_ctx* ctx, const double* d_a, const double* d_b /* nullable */, int64_t n, int64_t ld,
+                   int32_t nch, int32_t nfft, double fs, int32_t group, double* d_pa,
+                   double* d_pb /* nullable */);
+int mkid_welch_psd_host(const double* a, const double* b /* nullable */, int64_t n, int64_t ld, int32_t nch,
+                        int32_t nfft, double fs, int32_t group, double* pa, double* pb /* nullable */);
+
+/* IQsweep.AnalyzeNoise (lib/iqsweep.py:770-822) for every channel in one call: a long int16 IQ noise
+ * record per channel, d_i, d_q [nch][ld], is moved to the fitted loop centre, rotated and normalised;
+ * Welch spectra of its phase and amplitude at two resolutions are stitched into one spectrum, and
+ * the frequency noise at f_eval is read off a line through a few of its bins. Per channel, with the
+ * float64 zero point I0, Q0 (d_i0, d_q0), the fitted centre Icen, Qcen (d_icen, d_qcen: p[8], p[9]
+ * of mkid_fit_loops) and the fitted Q (d_qfit: p[0]):
+ *   means      SI, SQ the exact int64 sums of the first n samples;
+ *              mI = ((((double)SI / (double)n) gain) / full_scale - I0) - Icen, mQ alike (np.mean's
+ *              pairwise sum replaced by an exact one); resang = atan2(mQ, mI), c = cos(resang),
+ *              s = sin(resang), rad = mI c + mQ s
+ *   sample     Ia = ((((double)x gain) / full_scale) - I0) - Icen, Qa alike;
+ *              nI = (Ia c + Qa s) / rad, nQ = (Qa c - Ia s) / rad;
+ *              phase = atan2(nQ, nI), amp = sqrt(nI nI + nQ nQ)
+ *   spectra    mkid_welch_psd's rule on (phase, amp) at nfft_low and at nfft_high, fs = samprate; the
+ *              transforms' loader forms phase and amp as it loads: no float64 copy of the record
+ *   stitch     r = nfft_low / nfft_high; pn[0 : r k_join] = low[0 : r k_join], pn[r k_join :] =
+ *              high[k_join : nfft_high / 2] (the Nyquist bin is left out, as :805 does);
+ *              nout = r k_join + nfft_high / 2 - k_join (2552 for the reference's values); an alike.
+ *              Stitched bin b has frequency b (samprate / nfft_low) below r k_join and
+ *              (b - r k_join + k_join) (samprate / nfft_high) from there (mkid_iq_noise_freqs)
+ *   fn1k       the line through stitched bins fit_first .. fit_first + fit_count - 1 of pn in closed
+ *              form: xm, ym the means (sums in ascending order over the count), slope =
+ *              sum (x - xm)(y - ym) / sum (x - xm)^2, v = ym + slope (f_eval - xm);
+ *              fn1k = v / (16.0 (Q Q))
+ * Status bits: MKID_IQN_NONFINITE an offset (I0, Q0, Icen, Qcen) is not finite; MKID_IQN_BAD_RAD rad
+ * is zero or not finite: pn, an and fn1k are NaN; MKID_IQN_BAD_Q the fitted Q is zero or not finite:
+ * fn1k alone is NaN. Device and host twin differ only through atan2, sin and cos; sum_i, sum_q,
+ * nseg_low, nseg_high and status are equal bit for bit.
+ *   - mkid_iq_noise: device pointers only, asynchronous on the context stream; workspace, tables and
+ *     grouping as mkid_welch_psd (cfg->group). d_pn, d_an [nch][nout], d_result [nch]. MKID_E_ARG
+ *     before any launch, the outputs untouched: a null pointer, nch < 1, ld < n, n < nfft_low or
+ *     n > 2^31 - 1, nfft_high no power of two or outside 8 .. MKID_WELCH_LDS_MAX_N, nfft_low no
+ *     power of two, <= nfft_high or > MKID_WELCH_MAX_N, k_join < 1, k_join >= nfft_high / 2,
+ *     r k_join > nfft_low / 2, fit_count < 2, the fit range outside [0, nout), group < 0, samprate
+ *     not finite or <= 0, f_eval not finite, gain or full_scale not finite or zero.
+ *   - mkid_iq_noise_host: the same rule on host memory through the same definitions.
+ *   - mkid_iq_noise_freqs: the nout stitched frequencies on the host; MKID_E_ARG as for the cfg. */
+#define MKID_IQN_NONFINITE 1
+#define MKID_IQN_BAD_RAD 2
+#define MKID_IQN_BAD_Q 4
+typedef struct mkid_iqnoise_cfg {
+    int32_t nfft_low, nfft_high;    /* the reference: 262144, 4096                              */
+    int32_t k_join;                 /* high-resolution bins replaced by low-resolution ones: 8  */
+    int32_t fit_first, fit_count;   /* stitched bins of the fn1k line: 521, 5                   */
+    int32_t group;                  /* channels per pass; 0 = as many as the budget holds       */
+    double samprate, f_eval;        /* 200000.0, 1000.0                                         */
+    double gain, full_scale;        /* x gain / full_scale: 0.2, 32767.0                        */
+} mkid_iqnoise_cfg;
+typedef struct mkid_iqnoise_result {   /* one per channel */
+    double mean_i, mean_q, resang, rad, fn1k;
+    int64_t sum_i, sum_q;
+    int32_t nseg_low, nseg_high, status, pad;
+} mkid_iqnoise_result;
+int mkid_iq_noise(mkid_ctx* ctx, const int16_t* d_i, const int16_t* d_q, int64_t n, int64_t ld, int32_t nch,
+                  const double* d_i0, const double* d_q0, const double* d_icen, const double* d_qcen,
+                  const double* d_qfit, const mkid_iqnoise_cfg* cfg, double* d_pn, double* d_an,
+                  mkid_iqnoise_result* d_result);
+int mkid_iq_noise_host(const int16_t* i, const int16_t* q, int64_t n, int64_t ld, int32_t nch, const double* i0,
+                       const double* q0, const double* icen, const double* qcen, const double* qfit,
+                       const mkid_iqnoise_cfg* cfg, double* pn, double* an, mkid_iqnoise_result* result);
+int mkid_iq_noise_freqs(const mkid_iqnoise_cfg* cfg, double* freqs /* [nout] */);
+
 /* Kernel timing with HIP events on the context stream (for bench roofline numbers). */
 #define MKID_K_CHANNELIZE 0
 #define MKID_K_FIR_PHASE 1

@@ -30,6 +30,8 @@ CAL_FEW_LINES, CAL_FIT_FAILED, CAL_BAD_SLOPE = 1, 2, 16   # status bits; CAL_FIT
 CUBE_ENERGY, CUBE_WAVELENGTH = 0, 1  # mkid_energy_cube's modes
 LOOP_NPAR = 10                       # mkid_fit_loops
 LOOP_NONFINITE, LOOP_FLAT, LOOP_NO_FIT, LOOP_MAX_ITER = 1, 2, 4, 8   # its status bits
+WELCH_STRIP, WELCH_LDS_MAX_N, WELCH_MAX_N = 32, 4096, 262144         # mkid_welch_psd
+IQN_NONFINITE, IQN_BAD_RAD, IQN_BAD_Q = 1, 2, 4                      # mkid_iq_noise's status bits
 
 
 class MkidError(RuntimeError):
@@ -102,12 +104,31 @@ class LoopFit(ctypes.Structure):
                 ('pad', ctypes.c_int32)]
 
 
+class IqNoiseCfg(ctypes.Structure):
+    """mkid_iqnoise_cfg: the two resolutions, the stitch, the fn1k line and the scaling of mkid_iq_noise."""
+    _fields_ = [('nfft_low', ctypes.c_int32), ('nfft_high', ctypes.c_int32), ('k_join', ctypes.c_int32),
+                ('fit_first', ctypes.c_int32), ('fit_count', ctypes.c_int32), ('group', ctypes.c_int32),
+                ('samprate', ctypes.c_double), ('f_eval', ctypes.c_double), ('gain', ctypes.c_double),
+                ('full_scale', ctypes.c_double)]
+
+
+class IqNoiseResult(ctypes.Structure):
+    """mkid_iqnoise_result: one channel's means, rotation, radius, fn1k, exact sums and status."""
+    _fields_ = [('mean_i', ctypes.c_double), ('mean_q', ctypes.c_double), ('resang', ctypes.c_double),
+                ('rad', ctypes.c_double), ('fn1k', ctypes.c_double), ('sum_i', ctypes.c_int64),
+                ('sum_q', ctypes.c_int64), ('nseg_low', ctypes.c_int32), ('nseg_high', ctypes.c_int32),
+                ('status', ctypes.c_int32), ('pad', ctypes.c_int32)]
+
+
 LINE_FIT_DTYPE = [('bin', '<i4'), ('nfit', '<i4'), ('peak_s', '<i8'), ('counts', '<i8'), ('mu', '<f8'),
                   ('sigma', '<f8'), ('amp', '<f8')]
 ENERGY_CAL_DTYPE = [('c', '<f8', (3,)), ('r', '<f8', (3,)), ('n_found', '<i4'), ('status', '<i4')]
 LOOP_FIT_DTYPE = [('p', '<f8', (10,)), ('chisq', '<f8'), ('qc', '<f8'), ('qi', '<f8'), ('dipdb', '<f8'), ('cidx', '<i4'),
                   ('low', '<i4'), ('high', '<i4'), ('n', '<i4'), ('best_start', '<i4'), ('evals', '<i4'),
                   ('status', '<i4'), ('pad', '<i4')]
+IQ_NOISE_DTYPE = [('mean_i', '<f8'), ('mean_q', '<f8'), ('resang', '<f8'), ('rad', '<f8'), ('fn1k', '<f8'),
+                  ('sum_i', '<i8'), ('sum_q', '<i8'), ('nseg_low', '<i4'), ('nseg_high', '<i4'), ('status', '<i4'),
+                  ('pad', '<i4')]
 
 BANK_USED, BANK_FEW_RECORDS, BANK_NONE_PASS1, BANK_NONE_PASS2 = range(4)
 
@@ -200,6 +221,11 @@ _SIGS = {
                               P, P],
     'mkid_fit_loops': [P, P, P, P, P, P, P, P, I32, I32, I32, I32, ctypes.c_double, P, P],
     'mkid_fit_loops_host': [P, P, P, P, P, P, P, I32, I32, I32, I32, ctypes.c_double, P, P],
+    'mkid_welch_psd': [P, P, P, I64, I64, I32, I32, ctypes.c_double, I32, P, P],
+    'mkid_welch_psd_host': [P, P, I64, I64, I32, I32, ctypes.c_double, I32, P, P],
+    'mkid_iq_noise': [P, P, P, I64, I64, I32, P, P, P, P, P, P, P, P, P],
+    'mkid_iq_noise_host': [P, P, I64, I64, I32, P, P, P, P, P, P, P, P, P],
+    'mkid_iq_noise_freqs': [P, P],
     'mkid_set_capture': [P, I32, I32, I32],
     'mkid_capture_pulses': [P, P, I64, I64, P, I64, P, P, P],
     'mkid_capture_pulses_counted': [P, P, I64, I64, P, P, I64, P, P, P],

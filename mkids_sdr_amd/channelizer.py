@@ -562,6 +562,27 @@ class Channelizer:
         from . import loopfit
         return loopfit.fit_loops(self, freq, I, Q, draws, **kw)
 
+    # ---- Welch spectra and the IQ noise analysis (include/mkidgpu.h mkid_welch_psd, mkid_iq_noise) ------
+    def welch_psd_device(self, d_a, d_b, n, ld, nch, nfft, fs, group, d_pa, d_pb=None):
+        """Device pointers; asynchronous on the context stream (mkid_welch_psd): float64 d_a, d_b
+        (nullable) [nch][ld] -> d_pa, d_pb (nullable) [nch][nfft/2+1]."""
+        self._chk(self._L.mkid_welch_psd(self._h, _ptr(d_a), _ptr(d_b), int(n), int(ld), int(nch), int(nfft),
+                                         float(fs), int(group), _ptr(d_pa), _ptr(d_pb)))
+
+    def iq_noise_device(self, d_i, d_q, n, ld, nch, d_i0, d_q0, d_icen, d_qcen, d_qfit, cfg, d_pn, d_an, d_result):
+        """Device pointers; asynchronous on the context stream (mkid_iq_noise): int16 d_i, d_q
+        [nch][ld], float64 offsets, centres and Q [nch], cfg an _lib.IqNoiseCfg -> d_pn, d_an
+        [nch][nout], d_result [nch] mkid_iqnoise_result."""
+        self._chk(self._L.mkid_iq_noise(self._h, _ptr(d_i), _ptr(d_q), int(n), int(ld), int(nch), _ptr(d_i0),
+                                        _ptr(d_q0), _ptr(d_icen), _ptr(d_qcen), _ptr(d_qfit),
+                                        None if cfg is None else ctypes.byref(cfg), _ptr(d_pn), _ptr(d_an),
+                                        _ptr(d_result)))
+
+    def analyze_noise(self, I, Q, fits, **kw):
+        """Host convenience: iqnoise.analyze_noise on this context -> dict of arrays by field."""
+        from . import iqnoise
+        return iqnoise.analyze_noise(self, I, Q, fits, **kw)
+
     def concat_packets(self, d_a, d_na, cap_a, d_b, d_nb, cap_b, d_out, cap_out, d_nout):
         """d_out = the first min(*d_na, cap_a) packets of d_a, then the first min(*d_nb, cap_b) of d_b,
         cut at cap_out; d_nout int64 [2] = {produced, written}. Both counts are read on the device."""

@@ -1,5 +1,6 @@
 // The context behind the C ABI and what owns its device memory; private to the host translation
-// units of libmkidgpu.so (mkid_api.hip, mkid_stream.hip, mkid_calib.hip, mkid_observe.hip).
+// units of libmkidgpu.so (mkid_api.hip, mkid_stream.hip, mkid_calib.hip, mkid_observe.hip,
+// mkid_iqnoise.hip).
 #pragma once
 #include <algorithm>
 #include <string>
@@ -217,6 +218,17 @@ struct mkid_ctx : CtxHandles {
     // plan::noise_pack_tables lays them out; noise_plan keeps the passes and offsets only)
     DevBuf<char> d_noisetab;
     mkid::plan::NoisePlan noise_plan;
+    // mkid_welch_psd and mkid_iq_noise: the workspace (strip sums and the four-step transform's
+    // segments; lazy, grown on demand inside plan::kBankBudget unless one channel needs more) and the
+    // window and twiddle tables kept per nfft (lazy; a context sees a handful of lengths)
+    DevBuf<char> d_welchws;
+    size_t welchws_n = 0;
+    struct WelchTab {
+        int32_t nfft = 0;
+        double S2 = 0.0;
+        DevBuf<double> w, tw;   // [nfft], [nfft][2]
+    };
+    std::vector<WelchTab> welch_tabs;
     // mkid_height_spectra: per-workgroup deferred counts and offsets (lazy; their size is fixed,
     // mkid_internal.h kObsMaxBlocks), and the form of the spectra kernel: the plain one (one global
     // atomic per packet) unless MKID_OBS_LDS=1 at mkid_create asks for the LDS table, which the

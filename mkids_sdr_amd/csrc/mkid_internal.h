@@ -459,6 +459,48 @@ struct LoopfitArgs {
 };
 hipError_t launch_fit_loops(const LoopfitArgs& a, int32_t nch, hipStream_t s);
 
+// mkid_welch_psd and mkid_iq_noise (k_welch.hip; the rules are welch_common.h). One group of g
+// channels c0 .. c0 + g - 1 at one nfft: the strip sums of every channel and strip go to `part`
+// [g][nstrips][2][nfft / 2 + 1] (nfft <= MKID_WELCH_LDS_MAX_N: one workgroup per channel and strip,
+// one launch; larger: per segment of a strip a column launch and a row launch through `y`
+// [g][nstrips][nfft] complex), then one launch adds the strips and writes the densities of bins
+// k_lo .. k_hi - 1 to out_a / out_b [c ldo + off + k - k_lo]. The samples are float64 rows (a, b) or,
+// with xi set, the phase and amplitude of an int16 IQ record (welch::IqLoader over res and the offsets).
+struct WelchArgs {
+    const double* a;        // [nch][ld]
+    const double* b;        // nullable
+    const int16_t* xi;      // [nch][ld]; null: the float64 rows
+    const int16_t* xq;
+    const double *i0, *q0, *icen, *qcen;   // [nch]
+    const mkid_iqnoise_result* res;        // [nch]
+    mkid_iqnoise_cfg cfg;
+    const double* w;        // [nfft]
+    const double* tw;       // [nfft][2]
+    double* part;
+    double* y;
+    double* out_a;
+    double* out_b;          // nullable
+    int64_t ld, ldo, off, nseg, nstrips;
+    double den;             // fs S2
+    int32_t nfft, c0, g, k_lo, k_hi, pad;
+};
+hipError_t launch_welch_group(const WelchArgs& a, hipStream_t s);
+// mkid_iq_noise's first and last launch: the exact sums and each channel's constants into res; then
+// fn1k, and NaN over the spectra of a channel whose rad is unusable
+struct IqNoiseArgs {
+    const int16_t* xi;
+    const int16_t* xq;
+    const double *i0, *q0, *icen, *qcen, *qfit;
+    mkid_iqnoise_result* res;
+    double* pn;
+    double* an;
+    mkid_iqnoise_cfg cfg;
+    int64_t n, ld;
+    int32_t nch, pad;
+};
+hipError_t launch_iq_means(const IqNoiseArgs& a, hipStream_t s);
+hipError_t launch_iq_fn1k(const IqNoiseArgs& a, hipStream_t s);
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device), thread-safe: the
 // attribute is per device, and several contexts (devices, host threads) may launch concurrently.
 // `mask` is one static per kernel instantiation; the call is idempotent, so a race only repeats it.

@@ -561,6 +561,41 @@ class RoachSetup:
                     self.iq_centers[j] = complex(self.loop_fits['p'][j, 8], self.loop_fits['p'][j, 9])
         return self.loop_fits
 
+    def analyzeNoise(self, rows, channels=None, **cfg):
+        """IQsweep.AnalyzeNoise (lib/iqsweep.py:770-822) for the fitted tones at once on the device
+        (iqnoise.analyze_noise, include/mkidgpu.h mkid_iq_noise), after fitLoops: each channel's
+        noise record is `rows` low-pass IQ pairs taken at the LO through the IQ tap, one channel per
+        pass (slow: the tap holds one channel), all analysed in one call against self.loop_fits. The
+        tap and the sweep are both in ADC counts, so gain = full_scale = 1 and the zero point is 0
+        unless cfg says otherwise. `channels` picks tones (default: every swept tone). The result (a
+        dict of arrays by field, with 'channels' and the records 'I', 'Q') is kept in self.noise;
+        no register is written."""
+        from . import iqnoise
+        chans = list(range(int(self.N_freqs))) if channels is None else [int(c) for c in channels]
+        fpga = self.roach
+        ch = fpga.sync()
+        step = max(1, int(ch.cfg.max_chunk) // fpga.N)
+        I = np.zeros((len(chans), int(rows)), np.int16)
+        Q = np.zeros((len(chans), int(rows)), np.int16)
+        try:
+            for k, c in enumerate(chans):
+                ch.set_iq_tap(c)
+                fpga._process(ch, 64)                # settle, as _read_avgiq does
+                r0 = 0
+                while r0 < rows:
+                    n = min(step, int(rows) - r0)
+                    fpga._process(ch, n)
+                    iq = ch.iq_tap()
+                    I[k, r0:r0 + n], Q[k, r0:r0 + n] = iq[:n, 0], iq[:n, 1]
+                    r0 += n
+        finally:
+            ch.set_iq_tap(fpga.regs.get('conv_phase_ch_we_IQ', -1))   # the register's channel, or no tap
+        fits = {'p': np.asarray(self.loop_fits['p'], np.float64)[chans]}
+        kw = dict(dict(gain=1.0, full_scale=1.0), **cfg)
+        self.noise = iqnoise.analyze_noise(ch, I, Q, fits, **kw)
+        self.noise.update(channels=np.asarray(chans), I=I, Q=Q)
+        return self.noise
+
 
 class RoachPulses:
     """ROACH_Pulses.py AppForm trigger-setup and readback methods."""

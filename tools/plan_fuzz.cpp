@@ -6,7 +6,8 @@
 // silent miscount (the ADVICE r02 scratch-sizing bug is that class).
 // fuzz_observe, fuzz_photons and fuzz_pack drive the observing rules and the host twins' loops
 // (csrc/obs_common.h) likewise, fuzz_wavecal those of the laser-line calibration and the energy cube
-// (csrc/wavecal_common.h), fuzz_loopfit the resonator loop fits (csrc/loopfit_common.h).
+// (csrc/wavecal_common.h), fuzz_loopfit the resonator loop fits (csrc/loopfit_common.h), fuzz_welch the
+// Welch transforms' index maps and the IQ noise analysis (csrc/welch_common.h).
 //   plan_fuzz [iterations] [seed]
 #include <stdint.h>
 #include <stdio.h>
@@ -23,6 +24,7 @@
 #include "mkid_plan.h"
 #include "obs_common.h"
 #include "wavecal_common.h"
+#include "welch_common.h"
 
 extern "C" {
 typedef struct {
@@ -1342,6 +1344,92 @@ static void fuzz_loopfit(int iters) {
           "loop fit argument checks");
 }
 
+// Welch spectra and the IQ noise analysis (welch_common.h): pos_of_bin is a permutation for every
+// length a pass sequence serves, the four-step split multiplies back to nfft with both factors inside
+// the LDS limit, and the host twin's loops (which the kernels' index maps restate) run on buffers of
+// exactly the stated sizes: an index outside a segment, a table or a stitched row is an ASan error.
+static void fuzz_welch(int iters) {
+    namespace wl = mkid::welch;
+    for (int32_t n = 2; n <= wl::kLdsMaxN; n *= 2) {
+        const wl::Plan p = wl::make_plan(n);
+        std::vector<char> seen((size_t)n, 0);
+        int32_t prod = 1;
+        for (int32_t s = 0; s < p.npass; ++s) prod *= wl::radix(p, s);
+        CHECK(prod == n && p.npass >= 1, "welch plan of %d", n);
+        for (int32_t k = 0; k < n; ++k) {
+            const int32_t pos = wl::pos_of_bin(p, k);
+            CHECK(pos >= 0 && pos < n && !seen[(size_t)pos], "welch pos_of_bin(%d) of %d", k, n);
+            if (pos >= 0 && pos < n) seen[(size_t)pos] = 1;
+        }
+    }
+    for (int32_t nfft = 2 * wl::kLdsMaxN; nfft <= wl::kMaxN; nfft *= 2) {
+        int32_t n1, n2;
+        wl::split(nfft, n1, n2);
+        CHECK(n1 * n2 == nfft && n1 >= 8 && n1 <= n2 && n2 <= wl::kLdsMaxN && 4096 % n1 == 0 && n2 % (4096 / n1) == 0,
+              "welch split of %d: %d x %d", nfft, n1, n2);
+    }
+    std::normal_distribution<double> nd;
+    for (int it = 0; it < iters; ++it) {
+        const int m = (int)(rint_(0, 11) == 0 ? rint_(13, 16) : rint_(3, 12));
+        const int32_t nfft = 1 << m;
+        const int64_t n = nfft + rint_(0, m > 12 ? nfft : 40 * (int64_t)nfft / (m > 8 ? 16 : 1));
+        std::vector<double> a((size_t)n), b((size_t)n), pa((size_t)nfft / 2 + 1), pb(pa.size());
+        for (auto& x : a) x = nd(rng);
+        for (auto& x : b) x = 1.0 + 1e-3 * nd(rng);
+        const bool two = rint_(0, 3) != 0;
+        CHECK(wl::psd_args_ok(a.data(), n, n, 1, nfft, 1.0, 0, pa.data()) &&
+                  !wl::psd_args_ok(a.data(), nfft - 1, n, 1, nfft, 1.0, 0, pa.data()) &&
+                  !wl::psd_args_ok(a.data(), n, n - 1, 1, nfft, 1.0, 0, pa.data()) &&
+                  !wl::psd_args_ok(a.data(), n, n, 1, nfft + 1, 1.0, 0, pa.data()),
+              "welch args at %d", nfft);
+        wl::Tables t;
+        wl::make_tables(nfft, t);
+        wl::channel_host(nfft, t, wl::RowLoader{a.data(), two ? b.data() : nullptr}, n, 2e5,
+                         wl::Sink{pa.data(), two ? pb.data() : nullptr, 0, nfft / 2 + 1, 0});
+        double sum = 0.0;
+        bool ok = true;
+        for (double v : pa) ok = ok && std::isfinite(v) && v >= 0.0, sum += v;
+        // Parseval: sum of the one-sided density x (fs / nfft) is the windowed mean square (about 1)
+        CHECK(ok && sum * (2e5 / nfft) > 0.05 && sum * (2e5 / nfft) < 20.0, "welch density at %d: %g", nfft, sum);
+    }
+    for (int it = 0; it < iters / 4 + 1; ++it) {
+        mkid_iqnoise_cfg c{};
+        c.nfft_high = 1 << rint_(3, 8), c.nfft_low = c.nfft_high << rint_(1, 14 - wl::log2i(c.nfft_high));
+        c.k_join = (int32_t)rint_(1, c.nfft_high / 2 - 1);
+        const int32_t nout = wl::iq_nout(c);
+        c.fit_count = (int32_t)rint_(2, std::min(nout, 9)), c.fit_first = (int32_t)rint_(0, nout - c.fit_count);
+        c.samprate = 2e5, c.f_eval = 1e3, c.gain = 0.2, c.full_scale = 32767.0;
+        CHECK(wl::iq_cfg_ok(&c), "iq cfg %d/%d/%d", c.nfft_low, c.nfft_high, c.k_join);
+        mkid_iqnoise_cfg bad = c;
+        bad.fit_first = nout - c.fit_count + 1;
+        CHECK(!wl::iq_cfg_ok(&bad), "iq cfg fit range");
+        const int64_t n = c.nfft_low + rint_(0, c.nfft_low);
+        std::vector<int16_t> I((size_t)n), Q((size_t)n);
+        const bool centred = rint_(0, 5) == 0;   // a record whose mean is the centre: rad == 0
+        for (int64_t j = 0; j < n; ++j) {
+            I[(size_t)j] = centred ? (int16_t)((j & 1) ? 7 : -7) : (int16_t)(3000 + 30 * nd(rng));
+            Q[(size_t)j] = centred ? (int16_t)((j & 1) ? -3 : 3) : (int16_t)(-2000 + 30 * nd(rng));
+        }
+        if (centred && (n & 1)) I[(size_t)n - 1] = 0, Q[(size_t)n - 1] = 0;
+        int64_t si = 0, sq = 0;
+        for (int64_t j = 0; j < n; ++j) si += I[(size_t)j], sq += Q[(size_t)j];
+        mkid_iqnoise_result r;
+        const double icen = centred ? 0.0 : 6e-3, qcen = centred ? 0.0 : -3e-3;
+        wl::iq_means(si, sq, n, c, 0.0, 0.0, icen, qcen, 2e4, &r);
+        CHECK(centred == ((r.status & MKID_IQN_BAD_RAD) != 0) && r.sum_i == si && r.pad == 0, "iq status %d", r.status);
+        std::vector<double> pn((size_t)nout), an((size_t)nout);
+        wl::Tables tl, th;
+        wl::make_tables(c.nfft_low, tl), wl::make_tables(c.nfft_high, th);
+        const wl::IqLoader ld(I.data(), Q.data(), c, 0.0, 0.0, icen, qcen, r);
+        wl::channel_host(c.nfft_low, tl, ld, n, c.samprate, wl::iq_sink_low(c, pn.data(), an.data()));
+        wl::channel_host(c.nfft_high, th, ld, n, c.samprate, wl::iq_sink_high(c, pn.data(), an.data()));
+        const double fn = wl::iq_fn1k(c, pn.data(), 2e4, r.status);
+        CHECK(centred ? std::isnan(fn) : std::isfinite(fn), "iq fn1k %g", fn);
+        for (int32_t b2 = 1; b2 < nout; ++b2)
+            CHECK(wl::iq_freq(c, b2) > wl::iq_freq(c, b2 - 1), "iq freq axis at %d", b2);
+    }
+}
+
 int main(int argc, char** argv) {
     const int iters = argc > 1 ? atoi(argv[1]) : 300;
     rng.seed(argc > 2 ? strtoull(argv[2], nullptr, 10) : 12345);
@@ -1361,6 +1449,7 @@ int main(int argc, char** argv) {
     fuzz_pack(iters);
     fuzz_wavecal(iters / 3 + 1);
     fuzz_loopfit(iters / 3 + 1);
+    fuzz_welch(iters / 10 + 2);
     if (failures) {
         fprintf(stderr, "%d failures\n", failures);
         return 1;
