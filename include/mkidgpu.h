@@ -740,7 +740,7 @@ int mkid_energy_cube_host(const uint64_t* events, const float* heights, int64_t 
  * the zero point already subtracted. d_isd, d_qsd [nch][fsteps], both or neither: weights wI = 1 /
  * isd, wQ = 1 / qsd (1 when null). d_draws [nch][S][5]: the random numbers of :236-244 for start s, g
  * (standard normal), u2, u3, u4 in [0, 1), u5 in [-1, 1); the caller supplies them, so the call is a
- * pure function of its arguments. d_qguess [nch], nullable: a Q from elsewhere (FitMagMP's).
+ * pure function of its arguments. d_qguess [nch], nullable: a Q from elsewhere (mkid_fit_mags' d_qout).
  * fsteps 12 .. 1024, n_starts S 1 .. 16, max_iter >= 1, ftol > 0. Per channel, integer division:
  *   Window (bit-identical on device, host twin and any restatement: +, -, x, sqrt, comparisons).
  *     v[i] = sqrt((I[i] - I[i+1])^2 + (Q[i] - Q[i+1])^2), i = 0 .. nv - 1, nv = fsteps - 2 (the last
@@ -810,6 +810,73 @@ int mkid_fit_loops(mkid_ctx* ctx, const double* d_freq, const double* d_i, const
 int mkid_fit_loops_host(const double* freq, const double* i, const double* q, const double* isd, const double* qsd,
                         const double* draws, const double* qguess, int32_t nch, int32_t fsteps, int32_t n_starts,
                         int32_t max_iter, double ftol, mkid_loop_fit* fits, double* chisq_all);
+
+/* Resonator magnitude fits: every channel's swept |S21| fitted with the six-parameter model of the
+ * reference's IQsweep.FitMagMP (lib/iqsweep.py:293-356, MAGDIFF :913-917) in one call, giving Q and f0
+ * from the magnitude alone, the parameters Pdf() plots as mopt / magfit, and the Q that seeds the
+ * loop fit's starts (:227-231): d_qout is a valid d_qguess of mkid_fit_loops on the same stream. Kept
+ * from the reference: the model, the normalisation, the error 1e-5, the bounds, the start recipe and
+ * "the lowest chi^2 wins". The optimiser is mkid_fit_loops' own, with one definition for both fits
+ * (csrc/loopfit_common.h step and run_start at N parameters). The rules have one definition,
+ * csrc/magfit_common.h; the kernel is csrc/k_magfit.hip. All data are float64.
+ *
+ * mkid_fit_mags. d_freq, d_i, d_q [nch][fsteps]: a channel's frequencies in Hz and its I and Q with
+ * the zero point already subtracted. d_draws [nch][S]: the standard normal g of :335 for start s; the
+ * caller supplies it, so the call is a pure function of its arguments. fsteps 12 .. 1024, n_starts S
+ * 1 .. 16, max_iter >= 1, ftol > 0. Per channel, over the whole sweep (there is no window):
+ *   Data: mag[i] = sqrt(I[i] I[i] + Q[i] Q[i]); norm = the maximum of mag, found with > from mag[0]
+ *     (a NaN never wins; a NaN at mag[0] stays); y[i] = mag[i] / norm; w = 1 / 1e-5 for every point.
+ *     cidx = mkid_fit_loops' cidx, the first index of the maximum of the smoothed IQ velocity, by the
+ *     same functions (the reference's vmaxidx); the fit does not use it.
+ *   Bounds: Q [5e3, 1e6]; f0 [min x, max x]; carrier [1e-4, 1e2]; depth [0.01, 10]; slope [-5e3, 5e3];
+ *     curve [-1e8, 1e8]. A parameter with lo == hi is held fixed.
+ *   Start s: Q = max(10000 s + 5000 g, 5000), g = d_draws[c][s]; f0 = (sum of x, ascending) / fsteps;
+ *     carrier 1.0, depth 0.7, slope 0.1, curve -10; every value clipped into its bounds.
+ *   Model at x: dx = (x - f0) / f0, t = (2 Q) dx, den = 1 + t t, r = sqrt(den), a = |t| / r,
+ *     m = (((a - 1) depth + carrier) + slope dx) + (curve dx) dx. Residual res = (y - m) w; chi^2 = sum
+ *     res^2. No sin, cos or atan2: +, -, x, /, sqrt, |.| and comparisons only.
+ *   Jacobian: sg = (t > 0) - (t < 0), 0 at the cusp t = 0; k = sg / (den r); ddx = -x / (f0 f0);
+ *     dk = depth k; J = [w (dk (2 dx)), w (ddx (((dk (2 Q)) + slope) + (2 curve) dx)), w, w (a - 1),
+ *     w dx, w (dx dx)], every product and sum in the order of the brackets.
+ *   Sums: the 21 entries of A = J^T J (lower triangle), the 6 of g = J^T res and chi^2 are 64 lane
+ *     partials, lane l taking points l, l + 64, .. in ascending order, per point chi^2 first, then g_i
+ *     and A_ij (j <= i) by ascending i, j; they combine by the butterfly p[l] = p[l] + p[l ^ m], m =
+ *     32, 16, .., 1. Every product and sum is one IEEE operation, never fused.
+ *   Solver per start, accept rule, stop rules and winner: those of mkid_fit_loops word for word, at
+ *     six parameters (lambda = 1e-3, D = diag A, the free set hi > lo and D > 0, the Cholesky, trial =
+ *     clip(p + delta), accept a finite smaller chi^2 with lambda = max(lambda / 10, 1e-12) and stop at
+ *     a relative gain <= ftol, else lambda x= 10; stop at lambda > 1e12, an empty free set or max_iter
+ *     model evaluations; the lowest finite chi^2 wins, ties to the lower s).
+ *   Result: p, chisq, norm, cidx, best_start, evals = the best start's model evaluations. status bits,
+ *     with mkid_fit_loops' values: MKID_LOOP_NONFINITE a value of x, I or Q anywhere in the sweep is
+ *     not finite; MKID_LOOP_FLAT norm == 0; MKID_LOOP_NO_FIT no start reached a finite chi^2;
+ *     MKID_LOOP_MAX_ITER the best start stopped on max_iter. With any of the first three every float
+ *     but norm is NaN, best_start = -1 and evals = 0. cidx and norm are always set.
+ *   d_qout [nch], nullable: p[0] of a fitted channel, 50000.0 (FitLoopMP's own default Q, :193) for a
+ *     channel with one of the first three bits, so that the array is always a valid d_qguess.
+ *   d_chisq_all [nch][S], nullable: every start's final chi^2 (NaN for a channel with one of the
+ *     first two bits).
+ * Device, host twin and a float64 restatement agree in every bit; the bits do not depend on the
+ * launch shape. One workgroup per channel of min(S, 8) waves, the sweep's x and y staged in LDS once
+ * (the velocity scratch uses the same rows first), norm by a parallel maximum, one wave per start,
+ * the butterfly by __shfl_xor, the Cholesky on one lane, the best start chosen through LDS without
+ * atomics. Device pointers only; asynchronous on the context stream; no copy, no synchronisation, no
+ * workspace. Not timed. MKID_E_ARG before any launch: a null pointer (d_qout and d_chisq_all
+ * excepted), a parameter outside the ranges above.
+ * mkid_fit_mags_host: the same rules on host memory through the same definitions; no device, no
+ * context. The same MKID_E_ARG cases. */
+#define MKID_MAG_NPAR 6
+typedef struct mkid_mag_fit {
+    double p[MKID_MAG_NPAR];   /* Q, f0, carrier, depth, slope, curve */
+    double chisq, norm;
+    int32_t cidx, best_start, evals, status;
+} mkid_mag_fit;
+int mkid_fit_mags(mkid_ctx* ctx, const double* d_freq, const double* d_i, const double* d_q, const double* d_draws,
+                  int32_t nch, int32_t fsteps, int32_t n_starts, int32_t max_iter, double ftol, mkid_mag_fit* d_fits,
+                  double* d_qout /* nullable */, double* d_chisq_all /* nullable */);
+int mkid_fit_mags_host(const double* freq, const double* i, const double* q, const double* draws, int32_t nch,
+                       int32_t fsteps, int32_t n_starts, int32_t max_iter, double ftol, mkid_mag_fit* fits, double* qout,
+                       double* chisq_all);
 
 /* Pulse capture: the firmware-style capture block between the stream and the template analysis.
  * For every photon packet the phase window around its stamp is copied into a caller-owned,

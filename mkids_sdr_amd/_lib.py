@@ -30,6 +30,7 @@ CAL_FEW_LINES, CAL_FIT_FAILED, CAL_BAD_SLOPE = 1, 2, 16   # status bits; CAL_FIT
 CUBE_ENERGY, CUBE_WAVELENGTH = 0, 1  # mkid_energy_cube's modes
 LOOP_NPAR = 10                       # mkid_fit_loops
 LOOP_NONFINITE, LOOP_FLAT, LOOP_NO_FIT, LOOP_MAX_ITER = 1, 2, 4, 8   # its status bits
+MAG_NPAR = 6                         # mkid_fit_mags (its status bits are the LOOP_* ones)
 WELCH_STRIP, WELCH_LDS_MAX_N, WELCH_MAX_N = 32, 4096, 262144         # mkid_welch_psd
 IQN_NONFINITE, IQN_BAD_RAD, IQN_BAD_Q = 1, 2, 4                      # mkid_iq_noise's status bits
 
@@ -104,6 +105,13 @@ class LoopFit(ctypes.Structure):
                 ('pad', ctypes.c_int32)]
 
 
+class MagFit(ctypes.Structure):
+    """mkid_mag_fit: one channel's fitted resonator magnitude."""
+    _fields_ = [('p', ctypes.c_double * 6), ('chisq', ctypes.c_double), ('norm', ctypes.c_double),
+                ('cidx', ctypes.c_int32), ('best_start', ctypes.c_int32), ('evals', ctypes.c_int32),
+                ('status', ctypes.c_int32)]
+
+
 class IqNoiseCfg(ctypes.Structure):
     """mkid_iqnoise_cfg: the two resolutions, the stitch, the fn1k line and the scaling of mkid_iq_noise."""
     _fields_ = [('nfft_low', ctypes.c_int32), ('nfft_high', ctypes.c_int32), ('k_join', ctypes.c_int32),
@@ -126,6 +134,8 @@ ENERGY_CAL_DTYPE = [('c', '<f8', (3,)), ('r', '<f8', (3,)), ('n_found', '<i4'), 
 LOOP_FIT_DTYPE = [('p', '<f8', (10,)), ('chisq', '<f8'), ('qc', '<f8'), ('qi', '<f8'), ('dipdb', '<f8'), ('cidx', '<i4'),
                   ('low', '<i4'), ('high', '<i4'), ('n', '<i4'), ('best_start', '<i4'), ('evals', '<i4'),
                   ('status', '<i4'), ('pad', '<i4')]
+MAG_FIT_DTYPE = [('p', '<f8', (6,)), ('chisq', '<f8'), ('norm', '<f8'), ('cidx', '<i4'), ('best_start', '<i4'),
+                 ('evals', '<i4'), ('status', '<i4')]
 IQ_NOISE_DTYPE = [('mean_i', '<f8'), ('mean_q', '<f8'), ('resang', '<f8'), ('rad', '<f8'), ('fn1k', '<f8'),
                   ('sum_i', '<i8'), ('sum_q', '<i8'), ('nseg_low', '<i4'), ('nseg_high', '<i4'), ('status', '<i4'),
                   ('pad', '<i4')]
@@ -221,6 +231,8 @@ _SIGS = {
                               P, P],
     'mkid_fit_loops': [P, P, P, P, P, P, P, P, I32, I32, I32, I32, ctypes.c_double, P, P],
     'mkid_fit_loops_host': [P, P, P, P, P, P, P, I32, I32, I32, I32, ctypes.c_double, P, P],
+    'mkid_fit_mags': [P, P, P, P, P, I32, I32, I32, I32, ctypes.c_double, P, P, P],
+    'mkid_fit_mags_host': [P, P, P, P, I32, I32, I32, I32, ctypes.c_double, P, P, P],
     'mkid_welch_psd': [P, P, P, I64, I64, I32, I32, ctypes.c_double, I32, P, P],
     'mkid_welch_psd_host': [P, P, I64, I64, I32, I32, ctypes.c_double, I32, P, P],
     'mkid_iq_noise': [P, P, P, I64, I64, I32, P, P, P, P, P, P, P, P, P],

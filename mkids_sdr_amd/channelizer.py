@@ -562,6 +562,21 @@ class Channelizer:
         from . import loopfit
         return loopfit.fit_loops(self, freq, I, Q, draws, **kw)
 
+    # ---- resonator magnitude fits (include/mkidgpu.h mkid_fit_mags) -----------------------------------
+    def fit_mags_device(self, d_freq, d_i, d_q, d_draws, nch, fsteps, n_starts, max_iter, ftol, d_fits, d_qout=None,
+                        d_chisq_all=None):
+        """Device pointers; asynchronous on the context stream (mkid_fit_mags): float64 d_freq, d_i,
+        d_q [nch][fsteps], d_draws [nch][S], into d_fits (_lib.MagFit [nch]), d_qout float64 [nch]
+        (optional; a valid d_qguess of fit_loops_device) and d_chisq_all float64 [nch][S] (optional)."""
+        self._chk(self._L.mkid_fit_mags(self._h, _ptr(d_freq), _ptr(d_i), _ptr(d_q), _ptr(d_draws), int(nch),
+                                        int(fsteps), int(n_starts), int(max_iter), float(ftol), _ptr(d_fits),
+                                        _ptr(d_qout), _ptr(d_chisq_all)))
+
+    def fit_mags(self, freq, I, Q, draws, **kw):
+        """Host convenience: loopfit.fit_mags on this context -> dict of arrays by field."""
+        from . import loopfit
+        return loopfit.fit_mags(self, freq, I, Q, draws, **kw)
+
     # ---- Welch spectra and the IQ noise analysis (include/mkidgpu.h mkid_welch_psd, mkid_iq_noise) ------
     def welch_psd_device(self, d_a, d_b, n, ld, nch, nfft, fs, group, d_pa, d_pb=None):
         """Device pointers; asynchronous on the context stream (mkid_welch_psd): float64 d_a, d_b

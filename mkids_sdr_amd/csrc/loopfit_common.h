@@ -17,6 +17,10 @@
 // contraction off for their own statement, as wavecal_common.h's), and every sum has a written
 // order, so that device, host twin and a float64 restatement differ only through sin, cos, atan2
 // (and log10 in dipdb).
+//
+// The sums, the butterfly, the step and the run of one start are templates on the number of
+// parameters N: the loop fit is their instance at N = 10 and the magnitude fit (magfit_common.h)
+// at N = 6, so both fits share one Cholesky, one accept rule and one set of stop rules.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -169,14 +173,19 @@ LFIT_HD void make_start(const Problem& pr, int32_t s, const double* d, bool have
 }
 
 // ---- the model, its Jacobian and the sums ---------------------------------------------------------
-struct Sums {
-    double A[kNA], g[kNP], chi;
+// The sums of a fit with N parameters (the magnitude fit of magfit_common.h has six): the lower
+// triangle of A = J^T J, g = J^T r and chi^2.
+template <int32_t N>
+struct SumsT {
+    double A[N * (N + 1) / 2], g[N], chi;
 };
-LFIT_HD void zero(Sums* s) {
+using Sums = SumsT<kNP>;
+template <int32_t N>
+LFIT_HD void zero(SumsT<N>* s) {
     LFIT_UNROLL
-    for (int32_t i = 0; i < kNA; ++i) s->A[i] = 0.0;
+    for (int32_t i = 0; i < N * (N + 1) / 2; ++i) s->A[i] = 0.0;
     LFIT_UNROLL
-    for (int32_t i = 0; i < kNP; ++i) s->g[i] = 0.0;
+    for (int32_t i = 0; i < N; ++i) s->g[i] = 0.0;
     s->chi = 0.0;
 }
 
@@ -201,10 +210,11 @@ LFIT_HD Point model_point(const double* p, double ca, double sa, double x) {
 }
 
 // one half of a point into the sums: chi, then g_i and A_ij (j <= i) by ascending i, j
-LFIT_HD void accumulate(Sums* s, const double* J, double r) {
+template <int32_t N>
+LFIT_HD void accumulate(SumsT<N>* s, const double* J, double r) {
     s->chi = add(s->chi, mul(r, r));
     LFIT_UNROLL
-    for (int32_t i = 0; i < kNP; ++i) {
+    for (int32_t i = 0; i < N; ++i) {
         s->g[i] = add(s->g[i], mul(J[i], r));
         LFIT_UNROLL
         for (int32_t j = 0; j <= i; ++j) s->A[i * (i + 1) / 2 + j] = add(s->A[i * (i + 1) / 2 + j], mul(J[i], J[j]));
@@ -259,20 +269,22 @@ LFIT_HD void lane_partial(const double* p, const double* x, const double* I, con
 // trial = clip(p + delta), (A + lam diag D) delta = g on the free set (hi > lo and D = A_ii > 0). A
 // parameter outside the free set has its row and column replaced by the identity's and g = 0, so
 // that its delta is exactly 0 and the others are those of the reduced system. Cholesky, column by
-// column, every inner sum by ascending k. false: a pivot that is not positive and finite.
-LFIT_HD bool step(const Sums& c, double lam, const double* p, const double* lo, const double* hi, double* trial,
+// column, every inner sum by ascending k. false: a pivot that is not positive and finite. N: the
+// number of parameters (p, lo, hi, trial [N]).
+template <int32_t N>
+LFIT_HD bool step(const SumsT<N>& c, double lam, const double* p, const double* lo, const double* hi, double* trial,
                   int32_t* nfree) {
-    double L[kNA], y[kNP];
-    bool fr[kNP];
+    double L[N * (N + 1) / 2], y[N];
+    bool fr[N];
     int32_t nf = 0;
     LFIT_UNROLL
-    for (int32_t i = 0; i < kNP; ++i) {
+    for (int32_t i = 0; i < N; ++i) {
         fr[i] = hi[i] > lo[i] && c.A[i * (i + 1) / 2 + i] > 0.0;
         nf += fr[i] ? 1 : 0;
     }
     *nfree = nf;
     LFIT_UNROLL
-    for (int32_t j = 0; j < kNP; ++j) {
+    for (int32_t j = 0; j < N; ++j) {
         const double ajj = c.A[j * (j + 1) / 2 + j];
         double s = fr[j] ? add(ajj, mul(lam, ajj)) : 1.0;
         LFIT_UNROLL
@@ -281,7 +293,7 @@ LFIT_HD bool step(const Sums& c, double lam, const double* p, const double* lo, 
         const double d = sqrt(s);
         L[j * (j + 1) / 2 + j] = d;
         LFIT_UNROLL
-        for (int32_t i = j + 1; i < kNP; ++i) {
+        for (int32_t i = j + 1; i < N; ++i) {
             double t = fr[i] && fr[j] ? c.A[i * (i + 1) / 2 + j] : 0.0;
             LFIT_UNROLL
             for (int32_t k = 0; k < j; ++k) t = sub(t, mul(L[i * (i + 1) / 2 + k], L[j * (j + 1) / 2 + k]));
@@ -289,35 +301,37 @@ LFIT_HD bool step(const Sums& c, double lam, const double* p, const double* lo, 
         }
     }
     LFIT_UNROLL
-    for (int32_t i = 0; i < kNP; ++i) {   // L y = g
+    for (int32_t i = 0; i < N; ++i) {   // L y = g
         double t = fr[i] ? c.g[i] : 0.0;
         LFIT_UNROLL
         for (int32_t k = 0; k < i; ++k) t = sub(t, mul(L[i * (i + 1) / 2 + k], y[k]));
         y[i] = div(t, L[i * (i + 1) / 2 + i]);
     }
     LFIT_UNROLL
-    for (int32_t i = kNP - 1; i >= 0; --i) {   // L^T delta = y, delta kept in y
+    for (int32_t i = N - 1; i >= 0; --i) {   // L^T delta = y, delta kept in y
         double t = y[i];
         LFIT_UNROLL
-        for (int32_t k = i + 1; k < kNP; ++k) t = sub(t, mul(L[k * (k + 1) / 2 + i], y[k]));
+        for (int32_t k = i + 1; k < N; ++k) t = sub(t, mul(L[k * (k + 1) / 2 + i], y[k]));
         y[i] = div(t, L[i * (i + 1) / 2 + i]);
     }
     LFIT_UNROLL
-    for (int32_t i = 0; i < kNP; ++i) trial[i] = clip(add(p[i], y[i]), lo[i], hi[i]);
+    for (int32_t i = 0; i < N; ++i) trial[i] = clip(add(p[i], y[i]), lo[i], hi[i]);
     return true;
 }
 
 // ---- one start --------------------------------------------------------------------------------------
-struct StartResult {
-    double p[kNP], chi;
+template <int32_t N>
+struct StartResultT {
+    double p[N], chi;
     int32_t evals, hit_max;
 };
+using StartResult = StartResultT<kNP>;
 
 // eval(p, &sums): the combined sums at p. solve(sums, lam, p, trial, &nfree): step() (the device has
 // one lane run it and hands the result to the wave). r->p holds the start on entry.
-template <class Eval, class Solve>
-LFIT_HD void run_start(int32_t max_iter, double ftol, Eval&& eval, Solve&& solve, StartResult* r) {
-    Sums cur, nxt;
+template <int32_t N, class Eval, class Solve>
+LFIT_HD void run_start(int32_t max_iter, double ftol, Eval&& eval, Solve&& solve, StartResultT<N>* r) {
+    SumsT<N> cur, nxt;
     eval(r->p, &cur);
     r->chi = cur.chi, r->evals = 1, r->hit_max = 0;
     if (!fin(cur.chi)) return;
@@ -327,7 +341,7 @@ LFIT_HD void run_start(int32_t max_iter, double ftol, Eval&& eval, Solve&& solve
             r->hit_max = 1;
             return;
         }
-        double trial[kNP];
+        double trial[N];
         int32_t nfree = 0;
         if (!solve(cur, lam, r->p, trial, &nfree)) {
             lam = mul(lam, 10.0);
@@ -340,7 +354,7 @@ LFIT_HD void run_start(int32_t max_iter, double ftol, Eval&& eval, Solve&& solve
         if (fin(nxt.chi) && nxt.chi < r->chi) {
             const double rel = div(sub(r->chi, nxt.chi), r->chi);
             LFIT_UNROLL
-            for (int32_t i = 0; i < kNP; ++i) r->p[i] = trial[i];
+            for (int32_t i = 0; i < N; ++i) r->p[i] = trial[i];
             r->chi = nxt.chi;
             cur = nxt;
             const double l = div(lam, 10.0);
@@ -382,21 +396,28 @@ LFIT_HD void finish(const Window& w, int32_t status, const StartResult* best, in
 }
 
 // ---- the host twin ----------------------------------------------------------------------------------
+// the butterfly over the 64 lane partials: p[l] = p[l] + p[l ^ m] on every lane at once, m = 32 .. 1
+template <int32_t N>
+inline void butterfly_host(SumsT<N>* part) {
+    for (int32_t m = kLanes / 2; m >= 1; m >>= 1) {
+        for (int32_t l = 0; l < kLanes; ++l) {
+            if (l & m) continue;
+            SumsT<N>& a = part[l];
+            SumsT<N>& b = part[l ^ m];
+            for (int32_t i = 0; i < N * (N + 1) / 2; ++i) a.A[i] = b.A[i] = add(a.A[i], b.A[i]);
+            for (int32_t i = 0; i < N; ++i) a.g[i] = b.g[i] = add(a.g[i], b.g[i]);
+            a.chi = b.chi = add(a.chi, b.chi);
+        }
+    }
+}
+
 struct HostEval {
     const double *x, *I, *Q, *wI, *wQ;
     int32_t n;
     void operator()(const double* p, Sums* out) const {
         Sums part[kLanes];
         for (int32_t l = 0; l < kLanes; ++l) lane_partial(p, x, I, Q, wI, wQ, n, l, &part[l]);
-        for (int32_t m = kLanes / 2; m >= 1; m >>= 1) {   // p[l] = p[l] + p[l ^ m] on every lane at once
-            for (int32_t l = 0; l < kLanes; ++l) {
-                if (l & m) continue;
-                Sums &a = part[l], &b = part[l ^ m];
-                for (int32_t i = 0; i < kNA; ++i) a.A[i] = b.A[i] = add(a.A[i], b.A[i]);
-                for (int32_t i = 0; i < kNP; ++i) a.g[i] = b.g[i] = add(a.g[i], b.g[i]);
-                a.chi = b.chi = add(a.chi, b.chi);
-            }
-        }
+        butterfly_host(part);
         *out = part[0];
     }
 };

@@ -8,6 +8,7 @@
 
 #include "fit_common.h"
 #include "loopfit_common.h"
+#include "magfit_common.h"
 #include "mkid_ctx.h"
 #include "noise_common.h"
 #include "thr_common.h"
@@ -562,6 +563,34 @@ int mkid_fit_loops_host(const double* freq, const double* i, const double* q, co
                         int32_t max_iter, double ftol, mkid_loop_fit* fits, double* chisq_all) {
     if (!lfit::args_ok(freq, i, q, isd, qsd, draws, nch, fsteps, n_starts, max_iter, ftol, fits)) return MKID_E_ARG;
     lfit::fit_host(freq, i, q, isd, qsd, draws, qguess, nch, fsteps, n_starts, max_iter, ftol, fits, chisq_all);
+    return MKID_OK;
+}
+
+// ---- resonator magnitude fits (magfit_common.h) ------------------------------------------------------
+#define MAGS_ARGS_MSG \
+    "need pointers, nch >= 1, 12 <= fsteps <= 1024, 1 <= n_starts <= 16, max_iter >= 1, ftol > 0"
+
+int mkid_fit_mags(mkid_ctx* c, const double* d_freq, const double* d_i, const double* d_q, const double* d_draws,
+                  int32_t nch, int32_t fsteps, int32_t n_starts, int32_t max_iter, double ftol, mkid_mag_fit* d_fits,
+                  double* d_qout, double* d_chisq_all) {
+    if (!c) return MKID_E_ARG;
+    if (!mfit::args_ok(d_freq, d_i, d_q, d_draws, nch, fsteps, n_starts, max_iter, ftol, d_fits))
+        FAIL(c, MKID_E_ARG, "fit_mags: " MAGS_ARGS_MSG);
+    HIPCHK(c, hipSetDevice(c->device));
+    MagfitArgs a{};
+    a.freq = d_freq, a.i = d_i, a.q = d_q, a.draws = d_draws, a.fits = d_fits, a.qout = d_qout, a.chisq_all = d_chisq_all;
+    a.ftol = ftol, a.fsteps = fsteps, a.S = n_starts, a.max_iter = max_iter;
+    lfit::window_weights(a.wn);
+    HIPCHK(c, launch_fit_mags(a, nch, c->stream));
+    return MKID_OK;
+}
+
+// The CPU statement of the device call: the loops of magfit_common.h.
+int mkid_fit_mags_host(const double* freq, const double* i, const double* q, const double* draws, int32_t nch,
+                       int32_t fsteps, int32_t n_starts, int32_t max_iter, double ftol, mkid_mag_fit* fits, double* qout,
+                       double* chisq_all) {
+    if (!mfit::args_ok(freq, i, q, draws, nch, fsteps, n_starts, max_iter, ftol, fits)) return MKID_E_ARG;
+    mfit::fit_host(freq, i, q, draws, nch, fsteps, n_starts, max_iter, ftol, fits, qout, chisq_all);
     return MKID_OK;
 }
 

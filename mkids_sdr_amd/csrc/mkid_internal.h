@@ -459,6 +459,22 @@ struct LoopfitArgs {
 };
 hipError_t launch_fit_loops(const LoopfitArgs& a, int32_t nch, hipStream_t s);
 
+// mkid_fit_mags (k_magfit.hip; the rules are magfit_common.h): one workgroup per channel, the
+// sweep's x and normalised magnitude in static LDS, one wave per start.
+struct MagfitArgs {
+    const double* freq;    // [nch][fsteps]
+    const double* i;       // [nch][fsteps]
+    const double* q;       // [nch][fsteps]
+    const double* draws;   // [nch][S]
+    mkid_mag_fit* fits;    // [nch]
+    double* qout;          // nullable [nch]
+    double* chisq_all;     // nullable [nch][S]
+    double wn[10];         // hanning(10) / sum, made on the host
+    double ftol;
+    int32_t fsteps, S, max_iter, pad;
+};
+hipError_t launch_fit_mags(const MagfitArgs& a, int32_t nch, hipStream_t s);
+
 // mkid_welch_psd and mkid_iq_noise (k_welch.hip; the rules are welch_common.h). One group of g
 // channels c0 .. c0 + g - 1 at one nfft: the strip sums of every channel and strip go to `part`
 // [g][nstrips][2][nfft / 2 + 1] (nfft <= MKID_WELCH_LDS_MAX_N: one workgroup per channel and strip,

@@ -2,6 +2,12 @@
 the reference's ten-parameter model (IQsweep.FitLoopMP, lib/iqsweep.py:141-291) in one device call,
 giving Q, f0, the loop centre, Qc, Qi and the dip depth per channel. The model, window, guesses,
 bounds, start recipe and derived quantities are the reference's; the solver is the library's own.
+
+Resonator magnitude fits (mkid_fit_mags): IQsweep.FitMagMP (:293-356), the six-parameter fit of
+|S21| alone, for every channel in one device call; fit_sweeps chains it into the loop fit on the
+device, the magnitude fit's Q seeding the loop fit's starts as the reference does (:227-231).
+internal_power is the reference's Pint (:275-276), and load_swp / save_swp read and write the .swp
+text files of LoadSWP (:97-139) that carry the attenuator setting Pint needs.
 """
 import ctypes
 
@@ -85,3 +91,196 @@ def fit_loops_host(freq, I, Q, draws, isd=None, qsd=None, qguess=None, max_iter=
     _lib.check(L.mkid_fit_loops_host(p(f), p(i), p(q), p(sI), p(sQ), p(d), p(g), nch, fsteps, S, int(max_iter),
                                      float(ftol), p(fits), p(call)))
     return _by_field(fits, call)
+
+
+# ---- magnitude fits (include/mkidgpu.h mkid_fit_mags) -----------------------------------------------
+MAG_PARAMS = ('Q', 'f0', 'carrier', 'depth', 'slope', 'curve')
+MAG_FIELDS = ('p', 'chisq', 'norm', 'cidx', 'best_start', 'evals', 'status')
+
+
+def mag_draws(nch, S, seed):
+    """The random numbers of lib/iqsweep.py:335 for nch channels and S starts -> float64 [nch][S],
+    standard normal."""
+    return np.random.default_rng(seed).standard_normal((int(nch), int(S)))
+
+
+def mag_model(p, x):
+    """The magnitude model (MAGDIFF, lib/iqsweep.py:913-917; what `magfit` plots) at frequencies x for
+    parameters p (MAG_PARAMS order), in the operation order of include/mkidgpu.h."""
+    Qp, f0, carrier, depth, slope, curve = [float(v) for v in p]
+    x = np.asarray(x, np.float64)
+    with np.errstate(all='ignore'):
+        dx = (x - f0) / f0
+        t = (2.0 * Qp) * dx
+        a = np.abs(t) / np.sqrt(1.0 + t * t)
+        return (((a - 1.0) * depth + carrier) + slope * dx) + (curve * dx) * dx
+
+
+def _mag_by_field(fits, qout, chisq_all):
+    out = {k: fits[k].copy() for k in MAG_FIELDS}
+    out['qout'], out['chisq_all'] = qout, chisq_all
+    return out
+
+
+def _mag_inputs(freq, I, Q, dr):
+    f = np.ascontiguousarray(freq, np.float64)
+    i = np.ascontiguousarray(I, np.float64)
+    q = np.ascontiguousarray(Q, np.float64)
+    if not (f.ndim == 2 and f.shape == i.shape == q.shape):
+        raise ValueError('freq, I, Q must be [nch][fsteps] of one shape')
+    d = np.ascontiguousarray(dr, np.float64)
+    if d.ndim != 2 or d.shape[0] != f.shape[0]:
+        raise ValueError('draws must be [nch][S]')
+    return f, i, q, d, f.shape[0], f.shape[1], d.shape[1]
+
+
+def fit_mags(chan, freq, I, Q, draws, max_iter=200, ftol=1e-10):
+    """Fit the magnitude of every row of a sweep on the GPU of `chan`: freq (Hz), I, Q float64
+    [nch][fsteps] (zero point subtracted), draws [nch][S] (mag_draws()). One device call on the
+    context's stream, one synchronisation, one copy of the results (80 bytes a channel) -> dict of
+    arrays by field (MAG_FIELDS), 'p' [nch][6] in MAG_PARAMS order, 'qout' [nch] (the fitted Q, 50000
+    where there is no fit: a valid qguess of fit_loops) and 'chisq_all' [nch][S]."""
+    import torch
+    dev = chan.torch_device()
+    f, i, q, d, nch, fsteps, S = _mag_inputs(freq, I, Q, draws)
+    t = [torch.from_numpy(a).to(dev) for a in (f, i, q, d)]
+    d_fits = torch.zeros(nch * ctypes.sizeof(_lib.MagFit), dtype=torch.uint8, device=dev)
+    d_qout = torch.zeros(nch, dtype=torch.float64, device=dev)
+    d_all = torch.zeros((nch, S), dtype=torch.float64, device=dev)
+    torch.cuda.synchronize(dev)      # the uploads run on torch's stream, the kernel on the context's
+    chan.fit_mags_device(*t, nch, fsteps, S, max_iter, ftol, d_fits, d_qout, d_all)
+    torch.cuda.synchronize(dev)
+    fits = d_fits.cpu().numpy().view(np.dtype(_lib.MAG_FIT_DTYPE))
+    return _mag_by_field(fits, d_qout.cpu().numpy(), d_all.cpu().numpy())
+
+
+def fit_mags_host(freq, I, Q, draws, max_iter=200, ftol=1e-10):
+    """The same call through the host twin (mkid_fit_mags_host); needs no GPU."""
+    L = _lib.load()
+    f, i, q, d, nch, fsteps, S = _mag_inputs(freq, I, Q, draws)
+    fits = np.zeros(nch, np.dtype(_lib.MAG_FIT_DTYPE))
+    qout = np.zeros(nch, np.float64)
+    call = np.zeros((nch, S), np.float64)
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    _lib.check(L.mkid_fit_mags_host(p(f), p(i), p(q), p(d), nch, fsteps, S, int(max_iter), float(ftol), p(fits),
+                                    p(qout), p(call)))
+    return _mag_by_field(fits, qout, call)
+
+
+def fit_sweeps(chan, freq, I, Q, mag_draws, loop_draws, isd=None, qsd=None, max_iter=200, ftol=1e-10):
+    """The reference's characterisation order on the device: the magnitude fit first, its Q the
+    loop fit's Q guess (lib/iqsweep.py:227-231), without a host round trip. One upload,
+    fit_mags_device writing d_qout, fit_loops_device reading that buffer as d_qguess on the same
+    stream, one synchronisation -> (mags, loops), the dicts fit_mags and fit_loops return. The loop
+    results are those of fit_loops(qguess=mags['qout']) bit for bit."""
+    import torch
+    dev = chan.torch_device()
+    f, i, q, sI, sQ, d, _, nch, fsteps, S = _inputs(freq, I, Q, isd, qsd, loop_draws, None)
+    md = _mag_inputs(f, i, q, mag_draws)[3]
+    up = lambda a: None if a is None else torch.from_numpy(a).to(dev)
+    t = [up(a) for a in (f, i, q, sI, sQ, d, md)]
+    d_mags = torch.zeros(nch * ctypes.sizeof(_lib.MagFit), dtype=torch.uint8, device=dev)
+    d_qout = torch.zeros(nch, dtype=torch.float64, device=dev)
+    d_mall = torch.zeros((nch, md.shape[1]), dtype=torch.float64, device=dev)
+    d_fits = torch.zeros(nch * ctypes.sizeof(_lib.LoopFit), dtype=torch.uint8, device=dev)
+    d_all = torch.zeros((nch, S), dtype=torch.float64, device=dev)
+    torch.cuda.synchronize(dev)      # the uploads run on torch's stream, the kernels on the context's
+    chan.fit_mags_device(t[0], t[1], t[2], t[6], nch, fsteps, md.shape[1], max_iter, ftol, d_mags, d_qout, d_mall)
+    chan.fit_loops_device(*t[:6], d_qout, nch, fsteps, S, max_iter, ftol, d_fits, d_all)
+    torch.cuda.synchronize(dev)
+    mags = d_mags.cpu().numpy().view(np.dtype(_lib.MAG_FIT_DTYPE))
+    fits = d_fits.cpu().numpy().view(np.dtype(_lib.LOOP_FIT_DTYPE))
+    return (_mag_by_field(mags, d_qout.cpu().numpy(), d_mall.cpu().numpy()), _by_field(fits, d_all.cpu().numpy()))
+
+
+def internal_power(fits, atten1):
+    """The reference's Pint (lib/iqsweep.py:275-276) in dB for loop fits (a dict with 'p' and 'qc',
+    fit_loops') at input attenuator setting atten1 (dB; a scalar or one per channel):
+    10 log10((2 Q^2 / (pi Qc)) 10^((-atten1 - 35) / 10)), in numpy on the host."""
+    Qm = np.asarray(fits['p'], np.float64)[..., 0]
+    qc = np.asarray(fits['qc'], np.float64)
+    with np.errstate(all='ignore'):
+        power = 10.0 ** ((-np.asarray(atten1, np.float64) - 35.0) / 10.0)
+        return 10.0 * np.log10((2.0 * Qm ** 2 / (np.pi * qc)) * power)
+
+
+# ---- .swp sweep files (lib/iqsweep.py:97-139 LoadSWP) -------------------------------------------------
+# Seven tab-separated header lines,
+#   f0_0 span_0 fsteps_0 atten1 / f0_1 span_1 fsteps_1 atten2 / Tstart Tend / Iz0 Iz0sd / Qz0 Qz0sd /
+#   Iz1 Iz1sd / Qz1 Qz1sd,
+# then one table of five columns, freq (GHz) I Isd Q Qsd: resonator 0 in rows 0 .. fsteps_0 - 1,
+# resonator 1 in rows fsteps_0 .. fsteps_0 + fsteps_1 - 1 (LoadSWP's h3 offset).
+def _ghz_to_hz(tok):
+    """A GHz number as text -> the float64 nearest to its value in Hz (the decimal point moved nine
+    places, rounded once; LoadSWP's freq * 1e9 rounds twice and may differ in the last bit)."""
+    return float(tok + 'e9') if 'e' not in tok.lower() else float(tok) * 1e9
+
+
+def _hz_to_ghz(v):
+    """The text _ghz_to_hz reads back as exactly v."""
+    from decimal import Decimal
+    return format(Decimal(repr(float(v))).scaleb(-9), 'f') if np.isfinite(v) else repr(float(v))
+
+
+def load_swp(path, resnum=0):
+    """Read resonator `resnum` (0 or 1) of a .swp text file -> dict: 'freq' in Hz, 'I', 'Q' with the
+    zero point subtracted, 'Isd', 'Qsd' (float64 [fsteps]), 'atten1', 'atten2', 'f0', 'span' (the
+    header's own numbers, GHz), 'fsteps', 'I0', 'Q0', 'I0sd', 'Q0sd', 'Tstart', 'Tend'."""
+    if resnum not in (0, 1):
+        raise ValueError('resnum is 0 or 1')
+    with open(path) as f:
+        lines = f.read().splitlines()
+    head = [ln.split() for ln in lines[:7]]
+    if len(head) < 7 or [len(h) for h in head] != [4, 4, 2, 2, 2, 2, 2]:
+        raise ValueError('%s: not a .swp header' % path)
+    hv = [[float(v) for v in h] for h in head]
+    rows = [ln.split() for ln in lines[7:] if ln.strip()]
+    if any(len(r) != 5 for r in rows):
+        raise ValueError('%s: the table has five columns' % path)
+    n0, n1 = int(hv[0][2]), int(hv[1][2])
+    first, n = (0, n0) if resnum == 0 else (n0, n1)
+    if n < 0 or first + n > len(rows):
+        raise ValueError('%s: resonator %d needs rows %d .. %d of %d' % (path, resnum, first, first + n - 1, len(rows)))
+    tab = rows[first:first + n]
+    col = lambda k: np.array([float(r[k]) for r in tab], np.float64)
+    I0, I0sd = hv[3 + 2 * resnum]
+    Q0, Q0sd = hv[4 + 2 * resnum]
+    return dict(freq=np.array([_ghz_to_hz(r[0]) for r in tab], np.float64), I=col(1) - I0, Q=col(3) - Q0, Isd=col(2),
+                Qsd=col(4), atten1=hv[0][3], atten2=hv[1][3], f0=hv[resnum][0], span=hv[resnum][1], fsteps=n, I0=I0,
+                Q0=Q0, I0sd=I0sd, Q0sd=Q0sd, Tstart=hv[2][0], Tend=hv[2][1])
+
+
+def save_swp(path, res0, res1=None, atten1=0.0, atten2=0.0, tstart=0.0, tend=0.0):
+    """Write a .swp text file load_swp (and LoadSWP) reads. res0, res1 (optional): dicts with 'freq'
+    in Hz, 'I', 'Q' with the zero point subtracted, 'Isd', 'Qsd', and optionally 'I0', 'Q0' (the
+    zero point, added back into the table; default 0), 'I0sd', 'Q0sd', 'f0', 'span' (header numbers
+    in GHz; default the sweep's middle and width). Numbers are written with repr, so load_swp returns
+    freq, Isd and Qsd exactly, and I and Q exactly wherever I + I0 is exact (a zero point of 0, or
+    integer data)."""
+    r = repr
+    head, zero, table = [], [], []
+    for res, att in ((res0, atten1), (res1, atten2)):
+        if res is None:
+            head.append([0.0, 0.0, 0, float(att)])
+            zero += [[0.0, 0.0], [0.0, 0.0]]
+            continue
+        a = {k: np.asarray(res[k], np.float64) for k in ('freq', 'I', 'Q', 'Isd', 'Qsd')}
+        n = a['freq'].shape[0]
+        if a['freq'].ndim != 1 or any(v.shape != (n,) for v in a.values()):
+            raise ValueError('freq, I, Q, Isd, Qsd must be [fsteps] of one length')
+        I0, Q0 = float(res.get('I0', 0.0)), float(res.get('Q0', 0.0))
+        f0 = res.get('f0', float((a['freq'].max() + a['freq'].min()) / 2e9) if n else 0.0)
+        span = res.get('span', float((a['freq'].max() - a['freq'].min()) / 1e9) if n else 0.0)
+        head.append([float(f0), float(span), n, float(att)])
+        zero += [[I0, float(res.get('I0sd', 0.0))], [Q0, float(res.get('Q0sd', 0.0))]]
+        for k in range(n):
+            table.append([_hz_to_ghz(a['freq'][k]), r(float(a['I'][k] + I0)), r(float(a['Isd'][k])),
+                          r(float(a['Q'][k] + Q0)), r(float(a['Qsd'][k]))])
+    with open(path, 'w') as f:
+        for h in head:
+            f.write('\t'.join([r(h[0]), r(h[1]), str(h[2]), r(h[3])]) + '\n')
+        f.write('\t'.join([r(float(tstart)), r(float(tend))]) + '\n')
+        for z in zero:
+            f.write('\t'.join([r(z[0]), r(z[1])]) + '\n')
+        for row in table:
+            f.write('\t'.join(row) + '\n')

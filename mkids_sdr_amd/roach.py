@@ -540,19 +540,40 @@ class RoachSetup:
         self.I, self.Q = I, Q
         return I, Q
 
-    def fitLoops(self, starts=10, seed=0, use_centers=False, max_iter=200, ftol=1e-10):
+    def fitMags(self, starts=10, seed=0, max_iter=200, ftol=1e-10):
+        """IQsweep.FitMagMP (lib/iqsweep.py:293-356) for every swept tone at once on the device
+        (Channelizer.fit_mags, include/mkidgpu.h mkid_fit_mags), after sweepLOready, on self.f_span,
+        self.I, self.Q: Q and f0 from |S21| alone with the carrier, depth, slope and curve of the
+        magnitude model per tone, kept in self.mag_fits (a dict of arrays by field,
+        loopfit.MAG_FIELDS, with 'qout' and 'chisq_all'). Writes no register and changes no state but
+        self.mag_fits."""
+        from . import loopfit
+        nf = int(self.N_freqs)
+        self.mag_fits = self.roach.channelizer().fit_mags(
+            np.asarray(self.f_span, np.float64), self.I, self.Q, loopfit.mag_draws(nf, starts, seed), max_iter=max_iter,
+            ftol=ftol)
+        return self.mag_fits
+
+    def fitLoops(self, starts=10, seed=0, use_centers=False, max_iter=200, ftol=1e-10, mag_first=False):
         """IQsweep.FitLoopMP (lib/iqsweep.py:141-291) for every swept tone at once on the device
         (Channelizer.fit_loops, include/mkidgpu.h mkid_fit_loops), after sweepLOready, on self.f_span,
         self.I, self.Q: Q, f0, loop centre, Qc, Qi and dip depth per tone, kept in self.loop_fits (a
         dict of arrays by field, loopfit.FIELDS). Only with use_centers=True are the IQ centres of
         the tones whose fit has no failure bit set from the fitted p[8], p[9] in place of
         findIQcenters' midpoints; the default writes no register and changes no state but
-        self.loop_fits."""
+        self.loop_fits. mag_first=True fits the magnitudes first and seeds the loop fit's starts
+        with their Q, as the reference's characterisation does (:227-231), in one chain on the device
+        (loopfit.fit_sweeps); it keeps self.mag_fits as fitMags(starts, seed) does."""
         from . import loopfit
         nf = int(self.N_freqs)
-        self.loop_fits = self.roach.channelizer().fit_loops(
-            np.asarray(self.f_span, np.float64), self.I, self.Q, loopfit.draws(nf, starts, seed), max_iter=max_iter,
-            ftol=ftol)
+        if mag_first:
+            self.mag_fits, self.loop_fits = loopfit.fit_sweeps(
+                self.roach.channelizer(), np.asarray(self.f_span, np.float64), self.I, self.Q,
+                loopfit.mag_draws(nf, starts, seed), loopfit.draws(nf, starts, seed), max_iter=max_iter, ftol=ftol)
+        else:
+            self.loop_fits = self.roach.channelizer().fit_loops(
+                np.asarray(self.f_span, np.float64), self.I, self.Q, loopfit.draws(nf, starts, seed), max_iter=max_iter,
+                ftol=ftol)
         if use_centers:
             from . import _lib
             bad = _lib.LOOP_NONFINITE | _lib.LOOP_FLAT | _lib.LOOP_NO_FIT

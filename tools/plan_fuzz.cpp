@@ -6,7 +6,8 @@
 // silent miscount (the ADVICE r02 scratch-sizing bug is that class).
 // fuzz_observe, fuzz_photons and fuzz_pack drive the observing rules and the host twins' loops
 // (csrc/obs_common.h) likewise, fuzz_wavecal those of the laser-line calibration and the energy cube
-// (csrc/wavecal_common.h), fuzz_loopfit the resonator loop fits (csrc/loopfit_common.h), fuzz_welch the
+// (csrc/wavecal_common.h), fuzz_loopfit the resonator loop fits (csrc/loopfit_common.h), fuzz_magfit the
+// resonator magnitude fits (csrc/magfit_common.h), fuzz_welch the
 // Welch transforms' index maps and the IQ noise analysis (csrc/welch_common.h).
 //   plan_fuzz [iterations] [seed]
 #include <stdint.h>
@@ -21,6 +22,7 @@
 
 #include "fit_common.h"
 #include "loopfit_common.h"
+#include "magfit_common.h"
 #include "mkid_plan.h"
 #include "obs_common.h"
 #include "wavecal_common.h"
@@ -1344,6 +1346,104 @@ static void fuzz_loopfit(int iters) {
           "loop fit argument checks");
 }
 
+// The resonator magnitude fits (magfit_common.h fit_host) over random and degenerate sweeps: dips with
+// noise, all-zero and constant sweeps, zero and equal frequencies, NaN, +-inf and huge samples, draws
+// far outside a normal's range, every shape's ends. All arrays are buffers of exactly the documented
+// sizes, so a point, start or channel outside them is an ASan report. Checked besides: cidx lies
+// inside the velocities, norm is the largest magnitude, a failure status goes with NaN parameters,
+// best_start -1, evals 0 and a d_qout of 50000, any other with finite parameters inside their bounds,
+// a d_qout of p[0], a finite chi^2 that is the lowest of chisq_all with ties to the lower start, and
+// 1 <= evals <= max_iter with the max_iter bit only when evals == max_iter; the inputs are not written.
+static void fuzz_magfit(int iters) {
+    namespace mfit = mkid::mfit;
+    std::uniform_real_distribution<double> U(0.0, 1.0);
+    std::normal_distribution<double> N(0.0, 1.0);
+    const double odd[] = {NAN, INFINITY, -INFINITY, 0.0, -0.0, 1e300, -1e300, 1e-300};
+    for (int it = 0; it < iters; ++it) {
+        const int32_t nch = (int32_t)rint_(1, 3);
+        const int32_t fsteps = (int32_t)(rint_(0, 7) == 0 ? (rint_(0, 1) ? mfit::kMinSteps : mfit::kMaxSteps) : rint_(12, 140));
+        const int32_t S = (int32_t)(rint_(0, 5) == 0 ? (rint_(0, 1) ? 1 : mfit::kMaxStarts) : rint_(1, 6));
+        const int32_t max_iter = (int32_t)(rint_(0, 5) == 0 ? 1 : rint_(2, 25));
+        const size_t np = (size_t)nch * fsteps;
+        std::vector<double> x(np), I(np), Q(np), draws((size_t)nch * S);
+        for (int32_t c = 0; c < nch; ++c) {
+            const int kind = (int)rint_(0, 6);
+            const double Qr = 15e3 + 65e3 * U(rng), f0 = 4e9 + 2e9 * U(rng), R = 2e3 + 2e4 * U(rng);
+            const double span = (4.0 + 4.0 * U(rng)) * f0 / Qr, off = (U(rng) - 0.5) * span, ang = 6.0 * U(rng);
+            for (int32_t i = 0; i < fsteps; ++i) {
+                const size_t k = (size_t)c * fsteps + i;
+                x[k] = kind == 3 ? 0.0 : (kind == 6 ? f0 : f0 + off + span * ((double)i / (fsteps - 1) - 0.5));
+                const double t = 2.0 * Qr * (f0 + off + span * ((double)i / (fsteps - 1) - 0.5) - f0) / f0;
+                const double m = R * (1.0 - 0.7 * (1.0 - std::fabs(t) / std::sqrt(1.0 + t * t))) * (1.0 + 1e-3 * N(rng));
+                I[k] = m * std::cos(ang), Q[k] = m * std::sin(ang);
+                if (kind == 1) I[k] = 0.0, Q[k] = 0.0;                       // an all-zero sweep
+                if (kind == 2) I[k] = 12.0, Q[k] = -3.0;                     // a constant sweep
+                if (kind == 4 && rint_(0, 9) == 0) (rint_(0, 1) ? I[k] : Q[k]) = odd[rint_(0, 7)];
+                if (kind == 5 && rint_(0, 9) == 0) x[k] = odd[rint_(0, 7)];
+            }
+        }
+        for (auto& d : draws) d = rint_(0, 40) ? N(rng) : (rint_(0, 1) ? odd[rint_(0, 7)] : 50.0 * N(rng));
+        const std::vector<double> x0 = x, I0 = I, Q0 = Q;
+        std::vector<mkid_mag_fit> fits((size_t)nch);
+        std::vector<double> call((size_t)nch * S, -7.0), qout((size_t)nch, -7.0);
+        const double ftol = rint_(0, 3) ? 1e-8 : 1e-2;
+        const bool want_all = rint_(0, 3) != 0, want_q = rint_(0, 3) != 0;
+        CHECK(mfit::args_ok(x.data(), I.data(), Q.data(), draws.data(), nch, fsteps, S, max_iter, ftol, fits.data()), "mag fit args");
+        mfit::fit_host(x.data(), I.data(), Q.data(), draws.data(), nch, fsteps, S, max_iter, ftol, fits.data(),
+                       want_q ? qout.data() : nullptr, want_all ? call.data() : nullptr);
+        CHECK(memcmp(x.data(), x0.data(), np * 8) == 0 && memcmp(I.data(), I0.data(), np * 8) == 0 &&
+                  memcmp(Q.data(), Q0.data(), np * 8) == 0,
+              "the sweep was written");
+        for (int32_t c = 0; c < nch; ++c) {
+            const mkid_mag_fit& f = fits[(size_t)c];
+            const double *xw = x.data() + (size_t)c * fsteps, *Iw = I.data() + (size_t)c * fsteps, *Qw = Q.data() + (size_t)c * fsteps;
+            CHECK(f.cidx >= 0 && f.cidx <= fsteps - 3, "cidx %d of %d", f.cidx, fsteps);
+            bool finite = true, top = true;
+            for (int32_t i = 0; i < fsteps; ++i) {
+                finite = finite && std::isfinite(xw[i]) && std::isfinite(Iw[i]) && std::isfinite(Qw[i]);
+                top = top && !(std::sqrt(Iw[i] * Iw[i] + Qw[i] * Qw[i]) > f.norm);
+            }
+            const int32_t fail = MKID_LOOP_NONFINITE | MKID_LOOP_FLAT | MKID_LOOP_NO_FIT;
+            CHECK((f.status & ~(fail | MKID_LOOP_MAX_ITER)) == 0 && finite == ((f.status & MKID_LOOP_NONFINITE) == 0), "status %d", f.status);
+            if (finite) CHECK(top && f.norm >= 0.0 && ((f.status & MKID_LOOP_FLAT) != 0) == (f.norm == 0.0), "norm %g status %d", f.norm, f.status);
+            if (f.status & fail) {
+                bool nan = std::isnan(f.chisq);
+                for (int i = 0; i < mfit::kNP; ++i) nan = nan && std::isnan(f.p[i]);
+                CHECK(nan && f.best_start == -1 && f.evals == 0 && (f.status & MKID_LOOP_MAX_ITER) == 0, "a failed fit with results");
+                if (want_q) CHECK(qout[(size_t)c] == 50000.0, "qout of a failed fit %g", qout[(size_t)c]);
+                if (want_all)
+                    for (int32_t s = 0; s < S; ++s) CHECK(!std::isfinite(call[(size_t)c * S + s]), "a failed fit with a finite start");
+                continue;
+            }
+            CHECK(f.best_start >= 0 && f.best_start < S && f.evals >= 1 && f.evals <= max_iter &&
+                      (((f.status & MKID_LOOP_MAX_ITER) != 0) ? f.evals == max_iter : true) && std::isfinite(f.chisq) && f.chisq >= 0.0,
+                  "start %d evals %d status %d", f.best_start, f.evals, f.status);
+            const double xlo = *std::min_element(xw, xw + fsteps), xhi = *std::max_element(xw, xw + fsteps);
+            CHECK(f.p[0] >= 5e3 && f.p[0] <= 1e6 && f.p[1] >= xlo && f.p[1] <= xhi && f.p[2] >= 1e-4 && f.p[2] <= 1e2 &&
+                      f.p[3] >= 0.01 && f.p[3] <= 10.0 && std::fabs(f.p[4]) <= 5e3 && std::fabs(f.p[5]) <= 1e8,
+                  "parameters outside their bounds");
+            if (want_q) CHECK(qout[(size_t)c] == f.p[0], "qout %g of Q %g", qout[(size_t)c], f.p[0]);
+            if (want_all)
+                for (int32_t s = 0; s < S; ++s) {
+                    const double v = call[(size_t)c * S + s];
+                    CHECK(!std::isfinite(v) || v > f.chisq || (v == f.chisq && s >= f.best_start), "start %d beats the best", s);
+                    if (s == f.best_start) CHECK(v == f.chisq, "chisq_all of the best start");
+                }
+        }
+    }
+    double d1 = 1.0;
+    mkid_mag_fit f1{};
+    CHECK(!mfit::args_ok(nullptr, &d1, &d1, &d1, 1, 12, 1, 1, 1e-6, &f1) && !mfit::args_ok(&d1, nullptr, &d1, &d1, 1, 12, 1, 1, 1e-6, &f1) &&
+              !mfit::args_ok(&d1, &d1, nullptr, &d1, 1, 12, 1, 1, 1e-6, &f1) && !mfit::args_ok(&d1, &d1, &d1, nullptr, 1, 12, 1, 1, 1e-6, &f1) &&
+              !mfit::args_ok(&d1, &d1, &d1, &d1, 1, 12, 1, 1, 1e-6, nullptr) && !mfit::args_ok(&d1, &d1, &d1, &d1, 0, 12, 1, 1, 1e-6, &f1) &&
+              !mfit::args_ok(&d1, &d1, &d1, &d1, 1, 11, 1, 1, 1e-6, &f1) && !mfit::args_ok(&d1, &d1, &d1, &d1, 1, 1025, 1, 1, 1e-6, &f1) &&
+              !mfit::args_ok(&d1, &d1, &d1, &d1, 1, 12, 0, 1, 1e-6, &f1) && !mfit::args_ok(&d1, &d1, &d1, &d1, 1, 12, 17, 1, 1e-6, &f1) &&
+              !mfit::args_ok(&d1, &d1, &d1, &d1, 1, 12, 1, 0, 1e-6, &f1) && !mfit::args_ok(&d1, &d1, &d1, &d1, 1, 12, 1, 1, 0.0, &f1) &&
+              !mfit::args_ok(&d1, &d1, &d1, &d1, 1, 12, 1, 1, NAN, &f1) && mfit::args_ok(&d1, &d1, &d1, &d1, 1, 1024, 16, 1, 1e-6, &f1) &&
+              sizeof(mkid_mag_fit) == 80,
+          "mag fit argument checks");
+}
+
 // Welch spectra and the IQ noise analysis (welch_common.h): pos_of_bin is a permutation for every
 // length a pass sequence serves, the four-step split multiplies back to nfft with both factors inside
 // the LDS limit, and the host twin's loops (which the kernels' index maps restate) run on buffers of
@@ -1449,6 +1549,7 @@ int main(int argc, char** argv) {
     fuzz_pack(iters);
     fuzz_wavecal(iters / 3 + 1);
     fuzz_loopfit(iters / 3 + 1);
+    fuzz_magfit(iters / 3 + 1);
     fuzz_welch(iters / 10 + 2);
     if (failures) {
         fprintf(stderr, "%d failures\n", failures);
