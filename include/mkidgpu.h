@@ -771,7 +771,7 @@ int mkid_energy_cube_host(const uint64_t* events, const float* heights, int64_t 
  *     point; they combine by the butterfly p[l] = p[l] + p[l ^ m], m = 32, 16, .., 1. Every product
  *     and sum is one IEEE operation, never fused.
  *   Solver per start: lambda = 1e-3; D = diag A. The free set is the parameters with hi > lo and D >
- *     0; (A + lambda diag D) delta = g on the free set by the Cholesky written in loopfit_common.h
+ *     0; (A + lambda diag D) delta = g on the free set by the Cholesky written in lm_common.h
  *     step; a pivot that is not positive and finite: lambda x= 10 and retry. trial = clip(p + delta).
  *     Accept when chi^2(trial) is finite and smaller: lambda = max(lambda / 10, 1e-12), and stop when
  *     (chi^2 - chi^2(trial)) / chi^2 <= ftol. Otherwise lambda x= 10. Stop when lambda > 1e12, when
@@ -817,7 +817,7 @@ int mkid_fit_loops_host(const double* freq, const double* i, const double* q, co
  * loop fit's starts (:227-231): d_qout is a valid d_qguess of mkid_fit_loops on the same stream. Kept
  * from the reference: the model, the normalisation, the error 1e-5, the bounds, the start recipe and
  * "the lowest chi^2 wins". The optimiser is mkid_fit_loops' own, with one definition for both fits
- * (csrc/loopfit_common.h step and run_start at N parameters). The rules have one definition,
+ * (csrc/lm_common.h step and run_start at N parameters). The rules have one definition,
  * csrc/magfit_common.h; the kernel is csrc/k_magfit.hip. All data are float64.
  *
  * mkid_fit_mags. d_freq, d_i, d_q [nch][fsteps]: a channel's frequencies in Hz and its I and Q with

@@ -1,4 +1,5 @@
-// Resonator loop fits (include/mkidgpu.h mkid_fit_loops; the rules are loopfit_common.h).
+// Resonator loop fits (include/mkidgpu.h mkid_fit_loops; the rules are loopfit_common.h, the solver and the
+// workgroup's driver lm_common.h).
 //
 // k_loopfit  one workgroup of 256 threads per channel.
 //   Window:  thread t computes velocities t, t + 256, .. into LDS, then the smoothed velocities from
@@ -24,38 +25,6 @@ namespace mkid {
 constexpr int kLfitThreads = 256;
 constexpr int kLfitWaves = kLfitThreads / 64;
 
-struct LfitDevEval {
-    const double *x, *I, *Q, *wI, *wQ;
-    int32_t n, lane;
-    __device__ void operator()(const double* p, lfit::Sums* s) const {
-        lfit::lane_partial(p, x, I, Q, wI, wQ, n, lane, s);
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) {
-#pragma unroll
-            for (int i = 0; i < lfit::kNA; ++i) s->A[i] = lfit::add(s->A[i], __shfl_xor(s->A[i], m, 64));
-#pragma unroll
-            for (int i = 0; i < lfit::kNP; ++i) s->g[i] = lfit::add(s->g[i], __shfl_xor(s->g[i], m, 64));
-            s->chi = lfit::add(s->chi, __shfl_xor(s->chi, m, 64));
-        }
-    }
-};
-
-struct LfitDevSolve {
-    const double *lo, *hi;
-    int32_t lane;
-    __device__ bool operator()(const lfit::Sums& c, double lam, const double* p, double* trial, int32_t* nfree) const {
-        int ok = 0, nf = 0;
-#pragma unroll
-        for (int i = 0; i < lfit::kNP; ++i) trial[i] = 0.0;
-        if (lane == 0) ok = lfit::step(c, lam, p, lo, hi, trial, &nf) ? 1 : 0;
-        ok = __shfl(ok, 0, 64), nf = __shfl(nf, 0, 64);
-#pragma unroll
-        for (int i = 0; i < lfit::kNP; ++i) trial[i] = __shfl(trial[i], 0, 64);
-        *nfree = nf;
-        return ok != 0;
-    }
-};
-
 __global__ __launch_bounds__(kLfitThreads) void k_loopfit(LoopfitArgs a) {
     __shared__ double s_vel[lfit::kMaxSteps], s_sv[lfit::kMaxSteps];
     __shared__ double s_x[lfit::kMaxWindow], s_i[lfit::kMaxWindow], s_q[lfit::kMaxWindow], s_wi[lfit::kMaxWindow],
@@ -69,41 +38,40 @@ __global__ __launch_bounds__(kLfitThreads) void k_loopfit(LoopfitArgs a) {
     const int32_t fsteps = a.fsteps, S = a.S;
     const int64_t o = ch * fsteps;
     const double *gI = a.i + o, *gQ = a.q + o;
-    const int32_t nv = fsteps - 2, nsv = lfit::smooth_len(nv);
-    for (int32_t i = t; i < nv; i += kLfitThreads) s_vel[i] = lfit::velocity(gI, gQ, i);
-    __syncthreads();
-    for (int32_t i = t; i < nsv; i += kLfitThreads) s_sv[i] = lfit::smooth_at(s_vel, nv, a.wn, i);
-    __syncthreads();
-    if (t == 0) s_win = lfit::window(s_sv, nsv, fsteps);
+    const lfit::Window w0 = lfit::window_group(gI, gQ, fsteps, a.wn, t, kLfitThreads, s_vel, s_sv);
+    if (t == 0) s_win = w0;
     __syncthreads();
     const lfit::Window w = s_win;
     for (int32_t i = t; i < w.n; i += kLfitThreads) {
         s_x[i] = a.freq[o + w.low + i], s_i[i] = gI[w.low + i], s_q[i] = gQ[w.low + i];
-        s_wi[i] = a.isd ? lfit::div(1.0, a.isd[o + w.low + i]) : 1.0;
-        s_wq[i] = a.qsd ? lfit::div(1.0, a.qsd[o + w.low + i]) : 1.0;
+        s_wi[i] = a.isd ? lm::div(1.0, a.isd[o + w.low + i]) : 1.0;
+        s_wq[i] = a.qsd ? lm::div(1.0, a.qsd[o + w.low + i]) : 1.0;
     }
     __syncthreads();
     if (t == 0) lfit::guesses(s_x, s_i, s_q, s_wi, s_wq, w.n, w.cidx - w.low, &s_pr);
     __syncthreads();
     const int32_t status = s_pr.status;   // workgroup-uniform
     if (status != 0) {
-        if (a.chisq_all)
-            for (int32_t s = t; s < S; s += kLfitThreads) a.chisq_all[ch * S + s] = lfit::nan64();
+        lm::no_fit(a.chisq_all, ch * S, S, t, kLfitThreads);
         if (t == 0) lfit::finish(w, status, nullptr, -1, &a.fits[ch]);
         return;
     }
+    const bool have_q = a.qguess != nullptr;
+    const double qg = have_q ? a.qguess[ch] : 0.0;
     lfit::StartResult r{};
     double best_chi = 0.0;   // the wave's best start itself waits in LDS, written by lane 0
     int32_t best_s = -1;
-    const LfitDevEval ev{s_x, s_i, s_q, s_wi, s_wq, w.n, lane};
-    const LfitDevSolve sol{s_pr.lo, s_pr.hi, lane};
-    const bool have_q = a.qguess != nullptr;
-    const double qg = have_q ? a.qguess[ch] : 0.0;
-    for (int32_t s = wv; s < S; s += kLfitWaves) {   // wave-uniform
+    // the partial holds pointers, as written: naming the arrays in it changes the register allocation
+    const double *x = s_x, *yI = s_i, *yQ = s_q, *wI = s_wi, *wQ = s_wq;
+    const int32_t n = w.n;
+    const auto part = [=](const double* p, lfit::Sums* s) { lfit::lane_partial(p, x, yI, yQ, wI, wQ, n, lane, s); };
+    const lm::WaveEval<lfit::kNP, decltype(part)> ev{part};
+    const lm::WaveSolve<lfit::kNP> sol{s_pr.lo, s_pr.hi, lane};
+    for (int32_t s = wv; s < S; s += kLfitWaves) {   // wave-uniform; written here and in k_magfit (lm_common.h)
         lfit::make_start(s_pr, s, a.draws + (ch * S + s) * 5, have_q, qg, r.p);
-        lfit::run_start(a.max_iter, a.ftol, ev, sol, &r);
+        lm::run_start(a.max_iter, a.ftol, ev, sol, &r);
         if (lane == 0 && a.chisq_all) a.chisq_all[ch * S + s] = r.chi;
-        if (lfit::better(r.chi, s, best_chi, best_s)) {
+        if (lm::better(r.chi, s, best_chi, best_s)) {
             best_chi = r.chi, best_s = s;
             if (lane == 0) s_best[wv] = r;
         }
@@ -111,11 +79,7 @@ __global__ __launch_bounds__(kLfitThreads) void k_loopfit(LoopfitArgs a) {
     if (lane == 0) s_best_s[wv] = best_s;
     __syncthreads();
     if (t == 0) {
-        int32_t pick = -1;
-        for (int i = 0; i < kLfitWaves; ++i)
-            if (s_best_s[i] >= 0 && lfit::better(s_best[i].chi, s_best_s[i], pick < 0 ? 0.0 : s_best[pick].chi,
-                                                  pick < 0 ? -1 : s_best_s[pick]))
-                pick = i;
+        const int32_t pick = lm::pick_wave(s_best, s_best_s, kLfitWaves);
         lfit::finish(w, 0, pick < 0 ? nullptr : &s_best[pick], pick < 0 ? -1 : s_best_s[pick], &a.fits[ch]);
     }
 }

@@ -1,4 +1,5 @@
-// Resonator magnitude fits (include/mkidgpu.h mkid_fit_mags; the rules are magfit_common.h).
+// Resonator magnitude fits (include/mkidgpu.h mkid_fit_mags; the rules are magfit_common.h, the solver and the
+// workgroup's driver lm_common.h).
 //
 // k_magfit  one workgroup per channel, min(S, 8) waves: one wave per start up to eight.
 //   Index:   thread t computes velocities t, t + T, .. into LDS, then the smoothed velocities from
@@ -40,38 +41,6 @@ namespace mkid {
 constexpr int kMfitMaxWaves = MKID_MFIT_WAVES;
 constexpr int kMfitMaxThreads = kMfitMaxWaves * 64;
 
-struct MfitDevEval {
-    const double *x, *y;
-    int32_t n, lane;
-    __device__ void operator()(const double* p, mfit::Sums* s) const {
-        mfit::lane_partial(p, x, y, n, lane, s);
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) {
-#pragma unroll
-            for (int i = 0; i < mfit::kNA; ++i) s->A[i] = lfit::add(s->A[i], __shfl_xor(s->A[i], m, 64));
-#pragma unroll
-            for (int i = 0; i < mfit::kNP; ++i) s->g[i] = lfit::add(s->g[i], __shfl_xor(s->g[i], m, 64));
-            s->chi = lfit::add(s->chi, __shfl_xor(s->chi, m, 64));
-        }
-    }
-};
-
-struct MfitDevSolve {
-    const double *lo, *hi;
-    int32_t lane;
-    __device__ bool operator()(const mfit::Sums& c, double lam, const double* p, double* trial, int32_t* nfree) const {
-        int ok = 0, nf = 0;
-#pragma unroll
-        for (int i = 0; i < mfit::kNP; ++i) trial[i] = 0.0;
-        if (lane == 0) ok = lfit::step(c, lam, p, lo, hi, trial, &nf) ? 1 : 0;
-        ok = __shfl(ok, 0, 64), nf = __shfl(nf, 0, 64);
-#pragma unroll
-        for (int i = 0; i < mfit::kNP; ++i) trial[i] = __shfl(trial[i], 0, 64);
-        *nfree = nf;
-        return ok != 0;
-    }
-};
-
 __global__ __launch_bounds__(kMfitMaxThreads) void k_magfit(MagfitArgs a) {
     __shared__ double s_x[mfit::kMaxSteps], s_y[mfit::kMaxSteps];   // first the velocities and their smoothing
     __shared__ double s_wmax[kMfitMaxWaves];
@@ -84,14 +53,9 @@ __global__ __launch_bounds__(kMfitMaxThreads) void k_magfit(MagfitArgs a) {
     const int32_t fsteps = a.fsteps, S = a.S;
     const int64_t o = ch * fsteps;
     const double *gI = a.i + o, *gQ = a.q + o;
-    const int32_t nv = fsteps - 2, nsv = lfit::smooth_len(nv);
-    double *s_vel = s_x, *s_sv = s_y;
     if (t == 0) s_bad = 0;
-    for (int32_t i = t; i < nv; i += T) s_vel[i] = lfit::velocity(gI, gQ, i);
-    __syncthreads();
-    for (int32_t i = t; i < nsv; i += T) s_sv[i] = lfit::smooth_at(s_vel, nv, a.wn, i);
-    __syncthreads();
-    if (t == 0) s_cidx = lfit::window(s_sv, nsv, fsteps).cidx;
+    const lfit::Window w0 = lfit::window_group(gI, gQ, fsteps, a.wn, t, T, s_x, s_y);
+    if (t == 0) s_cidx = w0.cidx;
     __syncthreads();   // the scan is over: the rows are free
     const int32_t cidx = s_cidx;
     double mx = 0.0;
@@ -99,7 +63,7 @@ __global__ __launch_bounds__(kMfitMaxThreads) void k_magfit(MagfitArgs a) {
     for (int32_t i = t; i < fsteps; i += T) {
         const double x = a.freq[o + i], I = gI[i], Q = gQ[i];
         const double mag = mfit::magnitude(I, Q);
-        bad = bad || !(lfit::fin(x) && lfit::fin(I) && lfit::fin(Q));
+        bad = bad || !(lm::fin(x) && lm::fin(I) && lm::fin(Q));
         s_x[i] = x, s_y[i] = mag;
         mx = mag > mx ? mag : mx;
     }
@@ -117,13 +81,12 @@ __global__ __launch_bounds__(kMfitMaxThreads) void k_magfit(MagfitArgs a) {
     if (mag0 != mag0) norm = mag0;
     const bool nonfinite = s_bad != 0;
     __syncthreads();   // everyone has read mag[0]
-    for (int32_t i = t; i < fsteps; i += T) s_y[i] = lfit::div(s_y[i], norm);
+    for (int32_t i = t; i < fsteps; i += T) s_y[i] = lm::div(s_y[i], norm);
     if (t == 0) mfit::problem(s_x, fsteps, nonfinite, norm, &s_pr);
     __syncthreads();
     const int32_t status = s_pr.status;   // workgroup-uniform
     if (status != 0) {
-        if (a.chisq_all)
-            for (int32_t s = t; s < S; s += T) a.chisq_all[ch * S + s] = lfit::nan64();
+        lm::no_fit(a.chisq_all, ch * S, S, t, T);
         if (t == 0) {
             const double qo = mfit::finish(cidx, norm, status, nullptr, -1, &a.fits[ch]);
             if (a.qout) a.qout[ch] = qo;
@@ -133,13 +96,14 @@ __global__ __launch_bounds__(kMfitMaxThreads) void k_magfit(MagfitArgs a) {
     mfit::StartResult r{};
     double best_chi = 0.0;   // the wave's best start itself waits in LDS, written by lane 0
     int32_t best_s = -1;
-    const MfitDevEval ev{s_x, s_y, fsteps, lane};
-    const MfitDevSolve sol{s_pr.lo, s_pr.hi, lane};
-    for (int32_t s = wv; s < S; s += W) {   // wave-uniform
+    const auto part = [=](const double* p, mfit::Sums* s) { mfit::lane_partial(p, s_x, s_y, fsteps, lane, s); };
+    const lm::WaveEval<mfit::kNP, decltype(part)> ev{part};
+    const lm::WaveSolve<mfit::kNP> sol{s_pr.lo, s_pr.hi, lane};
+    for (int32_t s = wv; s < S; s += W) {   // wave-uniform; written here and in k_loopfit (lm_common.h)
         mfit::make_start(s_pr, s, a.draws[ch * S + s], r.p);
-        lfit::run_start(a.max_iter, a.ftol, ev, sol, &r);
+        lm::run_start(a.max_iter, a.ftol, ev, sol, &r);
         if (lane == 0 && a.chisq_all) a.chisq_all[ch * S + s] = r.chi;
-        if (lfit::better(r.chi, s, best_chi, best_s)) {
+        if (lm::better(r.chi, s, best_chi, best_s)) {
             best_chi = r.chi, best_s = s;
             if (lane == 0) s_best[wv] = r;
         }
@@ -147,11 +111,7 @@ __global__ __launch_bounds__(kMfitMaxThreads) void k_magfit(MagfitArgs a) {
     if (lane == 0) s_best_s[wv] = best_s;
     __syncthreads();
     if (t == 0) {
-        int32_t pick = -1;
-        for (int i = 0; i < W; ++i)
-            if (s_best_s[i] >= 0 && lfit::better(s_best[i].chi, s_best_s[i], pick < 0 ? 0.0 : s_best[pick].chi,
-                                                  pick < 0 ? -1 : s_best_s[pick]))
-                pick = i;
+        const int32_t pick = lm::pick_wave(s_best, s_best_s, W);
         const double qo =
             mfit::finish(cidx, norm, 0, pick < 0 ? nullptr : &s_best[pick], pick < 0 ? -1 : s_best_s[pick], &a.fits[ch]);
         if (a.qout) a.qout[ch] = qo;

@@ -1,11 +1,11 @@
 // Resonator magnitude fits (include/mkidgpu.h mkid_fit_mags states the rules), one definition for the
 // kernel of k_magfit.hip and for the host entry point mkid_fit_mags_host: the normalised magnitude
 // over the whole sweep, the bounds, the starts, the six-parameter magnitude model with its analytic
-// Jacobian, the 64 lane partials and the result. The velocity-maximum index, the butterfly, the
-// damped normal equations with their Cholesky, the accept rule and the winner are the loop fit's own
-// (loopfit_common.h: velocity, smooth_at, window, SumsT, step, run_start, better), at six parameters.
-// No HIP is used: the host loops below are the whole of the host entry point, so that the CPU
-// sanitizer build (tools/plan_fuzz.cpp) runs them.
+// Jacobian, its lane partial of the sums and the result. The solver and the drivers that run the
+// starts, on the host and in the workgroup, are lm_common.h's at N = 6; the velocity-maximum index
+// is the loop fit's (loopfit_common.h: window_host, window_group). No HIP is used: the host loops
+// below are the whole of the host entry point, so that the CPU sanitizer build
+// (tools/plan_fuzz.cpp) runs them.
 //
 // Kept from the reference's IQsweep.FitMagMP (lib/iqsweep.py:293-356): the model MAGDIFF (:913-917),
 // the normalisation by the largest magnitude, the constant error 1e-5, the bounds, the recipe of the
@@ -15,26 +15,28 @@
 // model uses +, -, x, /, sqrt, |.| and comparisons only, so that device, host twin and a float64
 // restatement agree in every bit.
 #pragma once
+#include "lm_common.h"
 #include "loopfit_common.h"
 
 namespace mkid {
 namespace mfit {
 
-using lfit::add;
-using lfit::div;
-using lfit::fin;
-using lfit::mul;
-using lfit::nan64;
-using lfit::sub;
+using lm::add;
+using lm::clip;
+using lm::div;
+using lm::fin;
+using lm::kLanes;
+using lm::kMaxStarts;
+using lm::mul;
+using lm::nan64;
+using lm::sub;
 
 constexpr int32_t kNP = MKID_MAG_NPAR;   // 6 parameters: Q, f0, carrier, depth, slope, curve
-constexpr int32_t kNA = 21;              // lower triangle of J^T J
-constexpr int32_t kLanes = lfit::kLanes;
-constexpr int32_t kMinSteps = lfit::kMinSteps, kMaxSteps = lfit::kMaxSteps, kMaxStarts = lfit::kMaxStarts;
+constexpr int32_t kMinSteps = lfit::kMinSteps, kMaxSteps = lfit::kMaxSteps;   // the sweeps are the loop fit's
 constexpr double kQFail = 50000.0;       // d_qout of a channel without a fit: FitLoopMP's default Q (:193)
 
-using Sums = lfit::SumsT<kNP>;
-using StartResult = lfit::StartResultT<kNP>;
+using Sums = lm::SumsT<kNP>;
+using StartResult = lm::StartResultT<kNP>;
 
 inline bool args_ok(const double* freq, const double* i, const double* q, const double* draws, int32_t nch, int32_t fsteps,
                     int32_t S, int32_t max_iter, double ftol, const mkid_mag_fit* fits) {
@@ -43,8 +45,8 @@ inline bool args_ok(const double* freq, const double* i, const double* q, const 
 }
 
 // ---- the data ---------------------------------------------------------------------------------------
-LFIT_HD double magnitude(double I, double Q) { return sqrt(add(mul(I, I), mul(Q, Q))); }
-LFIT_HD double weight() { return div(1.0, 1e-5); }
+LM_HD double magnitude(double I, double Q) { return sqrt(add(mul(I, I), mul(Q, Q))); }
+LM_HD double weight() { return div(1.0, 1e-5); }
 
 // ---- bounds and starts ------------------------------------------------------------------------------
 struct Problem {
@@ -55,7 +57,7 @@ struct Problem {
 
 // x: the n sweep frequencies. One thread, ascending order. nonfinite: a value of x, I or Q that is not
 // finite was seen; norm: the largest magnitude.
-LFIT_HD void problem(const double* x, int32_t n, bool nonfinite, double norm, Problem* pr) {
+LM_HD void problem(const double* x, int32_t n, bool nonfinite, double norm, Problem* pr) {
     double xmin = x[0], xmax = x[0], xsum = 0.0;
     for (int32_t i = 0; i < n; ++i) {
         xsum = add(xsum, x[i]);
@@ -73,12 +75,12 @@ LFIT_HD void problem(const double* x, int32_t n, bool nonfinite, double norm, Pr
 }
 
 // start s of a channel; g = its draw (a standard normal)
-LFIT_HD void make_start(const Problem& pr, int32_t s, double g, double* p) {
+LM_HD void make_start(const Problem& pr, int32_t s, double g, double* p) {
     const double qt = add(mul(10000.0, (double)s), mul(5000.0, g));
     p[0] = qt < 5000.0 ? 5000.0 : qt;
     p[1] = pr.f0;
     p[2] = 1.0, p[3] = 0.7, p[4] = 0.1, p[5] = -10.0;
-    for (int32_t i = 0; i < kNP; ++i) p[i] = lfit::clip(p[i], pr.lo[i], pr.hi[i]);
+    for (int32_t i = 0; i < kNP; ++i) p[i] = clip(p[i], pr.lo[i], pr.hi[i]);
 }
 
 // ---- the model, its Jacobian and the sums ---------------------------------------------------------
@@ -86,7 +88,7 @@ LFIT_HD void make_start(const Problem& pr, int32_t s, double g, double* p) {
 struct Point {
     double dx, t, den, r, a, m;
 };
-LFIT_HD Point model_point(const double* p, double x) {
+LM_HD Point model_point(const double* p, double x) {
     Point m;
     m.dx = div(sub(x, p[1]), p[1]);
     m.t = mul(mul(2.0, p[0]), m.dx);
@@ -98,7 +100,7 @@ LFIT_HD Point model_point(const double* p, double x) {
 }
 
 // One point: the residual res = (y - m) w and J = w d(m)/dp.
-LFIT_HD void point_terms(const double* p, double x, double y, double w, double* J, double* res) {
+LM_HD void point_terms(const double* p, double x, double y, double w, double* J, double* res) {
     const Point m = model_point(p, x);
     *res = mul(sub(y, m.m), w);
     const double sg = (double)((m.t > 0.0) - (m.t < 0.0));   // 0 at the cusp t = 0
@@ -114,19 +116,19 @@ LFIT_HD void point_terms(const double* p, double x, double y, double w, double* 
 }
 
 // Lane `lane` of 64: points lane, lane + 64, .. of the sweep in ascending order.
-LFIT_HD void lane_partial(const double* p, const double* x, const double* y, int32_t n, int32_t lane, Sums* s) {
-    lfit::zero(s);
+LM_HD void lane_partial(const double* p, const double* x, const double* y, int32_t n, int32_t lane, Sums* s) {
+    lm::zero(s);
     const double w = weight();
     for (int32_t i = lane; i < n; i += kLanes) {
         double J[kNP], res;
         point_terms(p, x[i], y[i], w, J, &res);
-        lfit::accumulate(s, J, res);
+        lm::accumulate(s, J, res);
     }
 }
 
 // ---- the result -------------------------------------------------------------------------------------
 // -> the channel's d_qout value
-LFIT_HD double finish(int32_t cidx, double norm, int32_t status, const StartResult* best, int32_t best_s, mkid_mag_fit* f) {
+LM_HD double finish(int32_t cidx, double norm, int32_t status, const StartResult* best, int32_t best_s, mkid_mag_fit* f) {
     f->cidx = cidx, f->norm = norm;
     if (status == 0 && best_s < 0) status = MKID_LOOP_NO_FIT;
     if (status != 0) {
@@ -143,26 +145,12 @@ LFIT_HD double finish(int32_t cidx, double norm, int32_t status, const StartResu
 }
 
 // ---- the host twin ----------------------------------------------------------------------------------
-struct HostEval {
-    const double *x, *y;
-    int32_t n;
-    void operator()(const double* p, Sums* out) const {
-        Sums part[kLanes];
-        for (int32_t l = 0; l < kLanes; ++l) lane_partial(p, x, y, n, l, &part[l]);
-        lfit::butterfly_host(part);
-        *out = part[0];
-    }
-};
-
 // One channel on the host. freq, I, Q: its fsteps points; draws [S].
 inline void fit_channel_host(const double* freq, const double* I, const double* Q, const double* draws, int32_t fsteps,
                              int32_t S, int32_t max_iter, double ftol, const double* wn, mkid_mag_fit* fit, double* qout,
                              double* chisq_all) {
-    double vel[kMaxSteps], sv[kMaxSteps], y[kMaxSteps];
-    const int32_t nv = fsteps - 2, nsv = lfit::smooth_len(nv);
-    for (int32_t i = 0; i < nv; ++i) vel[i] = lfit::velocity(I, Q, i);
-    for (int32_t i = 0; i < nsv; ++i) sv[i] = lfit::smooth_at(vel, nv, wn, i);
-    const int32_t cidx = lfit::window(sv, nsv, fsteps).cidx;
+    double y[kMaxSteps];
+    const int32_t cidx = lfit::window_host(I, Q, fsteps, wn).cidx;
     bool nonfinite = false;
     for (int32_t i = 0; i < fsteps; ++i) {
         nonfinite = nonfinite || !(fin(freq[i]) && fin(I[i]) && fin(Q[i]));
@@ -174,24 +162,11 @@ inline void fit_channel_host(const double* freq, const double* I, const double* 
     for (int32_t i = 0; i < fsteps; ++i) y[i] = div(y[i], norm);
     Problem pr;
     problem(freq, fsteps, nonfinite, norm, &pr);
-    StartResult best{}, r{};
-    int32_t best_s = -1;
-    for (int32_t s = 0; s < S; ++s) {
-        if (pr.status != 0) {
-            if (chisq_all) chisq_all[s] = nan64();
-            continue;
-        }
-        make_start(pr, s, draws[s], r.p);
-        const HostEval ev{freq, y, fsteps};
-        lfit::run_start(
-            max_iter, ftol, ev,
-            [&](const Sums& c, double lam, const double* p, double* trial, int32_t* nfree) {
-                return lfit::step(c, lam, p, pr.lo, pr.hi, trial, nfree);
-            },
-            &r);
-        if (chisq_all) chisq_all[s] = r.chi;
-        if (lfit::better(r.chi, s, best.chi, best_s)) best = r, best_s = s;
-    }
+    StartResult best{};
+    const int32_t best_s = lm::run_starts_host(
+        pr.status, S, max_iter, ftol, [&](int32_t s, double* p) { make_start(pr, s, draws[s], p); },
+        lm::host_eval<kNP>([&](const double* p, int32_t lane, Sums* s) { lane_partial(p, freq, y, fsteps, lane, s); }),
+        pr.lo, pr.hi, &best, chisq_all);
     const double qo = finish(cidx, norm, pr.status, &best, best_s, fit);
     if (qout) *qout = qo;
 }

@@ -37,17 +37,21 @@ def model(p, x):
 
 
 def _by_field(fits, chisq_all):
+    fits = fits.view(np.dtype(_lib.LOOP_FIT_DTYPE))
     out = {k: fits[k].copy() for k in FIELDS}
     out['chisq_all'] = chisq_all
     return out
 
 
-def _inputs(freq, I, Q, isd, qsd, dr, qguess):
-    f = np.ascontiguousarray(freq, np.float64)
-    i = np.ascontiguousarray(I, np.float64)
-    q = np.ascontiguousarray(Q, np.float64)
+def _sweep(freq, I, Q):
+    f, i, q = (np.ascontiguousarray(a, np.float64) for a in (freq, I, Q))
     if not (f.ndim == 2 and f.shape == i.shape == q.shape):
         raise ValueError('freq, I, Q must be [nch][fsteps] of one shape')
+    return f, i, q
+
+
+def _inputs(freq, I, Q, isd, qsd, dr, qguess):
+    f, i, q = _sweep(freq, I, Q)
     nch, fsteps = f.shape
     d = np.ascontiguousarray(dr, np.float64)
     if d.ndim != 3 or d.shape[0] != nch or d.shape[2] != 5:
@@ -61,24 +65,35 @@ def _inputs(freq, I, Q, isd, qsd, dr, qguess):
     return f, i, q, sd[0], sd[1], d, g, nch, fsteps, d.shape[1]
 
 
+def _device(dev, arrays, outs, enqueue):
+    """A device call: `arrays` uploaded and the result buffers `outs` ((shape, dtype) each) zeroed on
+    torch's stream, one synchronisation (the kernels run on the context's stream),
+    enqueue(uploads, buffers), one synchronisation -> the buffers as numpy arrays."""
+    import torch
+    t = [None if a is None else torch.from_numpy(a).to(dev) for a in arrays]
+    o = [torch.zeros(shape, dtype=getattr(torch, dt), device=dev) for shape, dt in outs]
+    torch.cuda.synchronize(dev)
+    enqueue(t, o)
+    torch.cuda.synchronize(dev)
+    return [b.cpu().numpy() for b in o]
+
+
+def _loop_call(chan, nch, fsteps, S, max_iter, ftol):
+    """-> (the result buffers d_fits, d_chisq_all as (shape, dtype); enqueue(t, d_qguess, buffers), t the
+    six device arrays freq .. draws)."""
+    outs = [(nch * ctypes.sizeof(_lib.LoopFit), 'uint8'), ((nch, S), 'float64')]
+    return outs, lambda t, qg, o: chan.fit_loops_device(*t, qg, nch, fsteps, S, max_iter, ftol, *o)
+
+
 def fit_loops(chan, freq, I, Q, draws, isd=None, qsd=None, qguess=None, max_iter=200, ftol=1e-10):
     """Fit every row of a sweep on the GPU of `chan`: freq (Hz), I, Q float64 [nch][fsteps] (zero point
     subtracted), draws [nch][S][5] (draws()), optional isd, qsd (weights 1 / sd) and qguess [nch].
     One device call on the context's stream, one synchronisation, one copy of the results (144 bytes
     a channel) -> dict of arrays by field (FIELDS), 'p' [nch][10] in PARAMS order, and 'chisq_all'
     [nch][S]."""
-    import torch
-    dev = chan.torch_device()
-    f, i, q, sI, sQ, d, g, nch, fsteps, S = _inputs(freq, I, Q, isd, qsd, draws, qguess)
-    up = lambda a: None if a is None else torch.from_numpy(a).to(dev)
-    t = [up(a) for a in (f, i, q, sI, sQ, d, g)]
-    d_fits = torch.zeros(nch * ctypes.sizeof(_lib.LoopFit), dtype=torch.uint8, device=dev)
-    d_all = torch.zeros((nch, S), dtype=torch.float64, device=dev)
-    torch.cuda.synchronize(dev)      # the uploads run on torch's stream, the kernel on the context's
-    chan.fit_loops_device(*t, nch, fsteps, S, max_iter, ftol, d_fits, d_all)
-    torch.cuda.synchronize(dev)
-    fits = d_fits.cpu().numpy().view(np.dtype(_lib.LOOP_FIT_DTYPE))
-    return _by_field(fits, d_all.cpu().numpy())
+    *a, nch, fsteps, S = _inputs(freq, I, Q, isd, qsd, draws, qguess)
+    outs, enqueue = _loop_call(chan, nch, fsteps, S, max_iter, ftol)
+    return _by_field(*_device(chan.torch_device(), a, outs, lambda t, o: enqueue(t[:6], t[6], o)))
 
 
 def fit_loops_host(freq, I, Q, draws, isd=None, qsd=None, qguess=None, max_iter=200, ftol=1e-10):
@@ -117,21 +132,25 @@ def mag_model(p, x):
 
 
 def _mag_by_field(fits, qout, chisq_all):
+    fits = fits.view(np.dtype(_lib.MAG_FIT_DTYPE))
     out = {k: fits[k].copy() for k in MAG_FIELDS}
     out['qout'], out['chisq_all'] = qout, chisq_all
     return out
 
 
 def _mag_inputs(freq, I, Q, dr):
-    f = np.ascontiguousarray(freq, np.float64)
-    i = np.ascontiguousarray(I, np.float64)
-    q = np.ascontiguousarray(Q, np.float64)
-    if not (f.ndim == 2 and f.shape == i.shape == q.shape):
-        raise ValueError('freq, I, Q must be [nch][fsteps] of one shape')
+    f, i, q = _sweep(freq, I, Q)
     d = np.ascontiguousarray(dr, np.float64)
     if d.ndim != 2 or d.shape[0] != f.shape[0]:
         raise ValueError('draws must be [nch][S]')
     return f, i, q, d, f.shape[0], f.shape[1], d.shape[1]
+
+
+def _mag_call(chan, nch, fsteps, S, max_iter, ftol):
+    """-> (the result buffers d_fits, d_qout, d_chisq_all as (shape, dtype); enqueue(t, buffers), t the
+    four device arrays freq .. draws)."""
+    outs = [(nch * ctypes.sizeof(_lib.MagFit), 'uint8'), (nch, 'float64'), ((nch, S), 'float64')]
+    return outs, lambda t, o: chan.fit_mags_device(*t, nch, fsteps, S, max_iter, ftol, *o)
 
 
 def fit_mags(chan, freq, I, Q, draws, max_iter=200, ftol=1e-10):
@@ -140,18 +159,9 @@ def fit_mags(chan, freq, I, Q, draws, max_iter=200, ftol=1e-10):
     context's stream, one synchronisation, one copy of the results (80 bytes a channel) -> dict of
     arrays by field (MAG_FIELDS), 'p' [nch][6] in MAG_PARAMS order, 'qout' [nch] (the fitted Q, 50000
     where there is no fit: a valid qguess of fit_loops) and 'chisq_all' [nch][S]."""
-    import torch
-    dev = chan.torch_device()
-    f, i, q, d, nch, fsteps, S = _mag_inputs(freq, I, Q, draws)
-    t = [torch.from_numpy(a).to(dev) for a in (f, i, q, d)]
-    d_fits = torch.zeros(nch * ctypes.sizeof(_lib.MagFit), dtype=torch.uint8, device=dev)
-    d_qout = torch.zeros(nch, dtype=torch.float64, device=dev)
-    d_all = torch.zeros((nch, S), dtype=torch.float64, device=dev)
-    torch.cuda.synchronize(dev)      # the uploads run on torch's stream, the kernel on the context's
-    chan.fit_mags_device(*t, nch, fsteps, S, max_iter, ftol, d_fits, d_qout, d_all)
-    torch.cuda.synchronize(dev)
-    fits = d_fits.cpu().numpy().view(np.dtype(_lib.MAG_FIT_DTYPE))
-    return _mag_by_field(fits, d_qout.cpu().numpy(), d_all.cpu().numpy())
+    *a, nch, fsteps, S = _mag_inputs(freq, I, Q, draws)
+    outs, enqueue = _mag_call(chan, nch, fsteps, S, max_iter, ftol)
+    return _mag_by_field(*_device(chan.torch_device(), a, outs, enqueue))
 
 
 def fit_mags_host(freq, I, Q, draws, max_iter=200, ftol=1e-10):
@@ -173,24 +183,13 @@ def fit_sweeps(chan, freq, I, Q, mag_draws, loop_draws, isd=None, qsd=None, max_
     fit_mags_device writing d_qout, fit_loops_device reading that buffer as d_qguess on the same
     stream, one synchronisation -> (mags, loops), the dicts fit_mags and fit_loops return. The loop
     results are those of fit_loops(qguess=mags['qout']) bit for bit."""
-    import torch
-    dev = chan.torch_device()
     f, i, q, sI, sQ, d, _, nch, fsteps, S = _inputs(freq, I, Q, isd, qsd, loop_draws, None)
     md = _mag_inputs(f, i, q, mag_draws)[3]
-    up = lambda a: None if a is None else torch.from_numpy(a).to(dev)
-    t = [up(a) for a in (f, i, q, sI, sQ, d, md)]
-    d_mags = torch.zeros(nch * ctypes.sizeof(_lib.MagFit), dtype=torch.uint8, device=dev)
-    d_qout = torch.zeros(nch, dtype=torch.float64, device=dev)
-    d_mall = torch.zeros((nch, md.shape[1]), dtype=torch.float64, device=dev)
-    d_fits = torch.zeros(nch * ctypes.sizeof(_lib.LoopFit), dtype=torch.uint8, device=dev)
-    d_all = torch.zeros((nch, S), dtype=torch.float64, device=dev)
-    torch.cuda.synchronize(dev)      # the uploads run on torch's stream, the kernels on the context's
-    chan.fit_mags_device(t[0], t[1], t[2], t[6], nch, fsteps, md.shape[1], max_iter, ftol, d_mags, d_qout, d_mall)
-    chan.fit_loops_device(*t[:6], d_qout, nch, fsteps, S, max_iter, ftol, d_fits, d_all)
-    torch.cuda.synchronize(dev)
-    mags = d_mags.cpu().numpy().view(np.dtype(_lib.MAG_FIT_DTYPE))
-    fits = d_fits.cpu().numpy().view(np.dtype(_lib.LOOP_FIT_DTYPE))
-    return (_mag_by_field(mags, d_qout.cpu().numpy(), d_mall.cpu().numpy()), _by_field(fits, d_all.cpu().numpy()))
+    mouts, mags = _mag_call(chan, nch, fsteps, md.shape[1], max_iter, ftol)
+    louts, loops = _loop_call(chan, nch, fsteps, S, max_iter, ftol)
+    o = _device(chan.torch_device(), (f, i, q, sI, sQ, d, md), mouts + louts,
+                lambda t, o: (mags(t[:3] + t[6:], o[:3]), loops(t[:6], o[1], o[3:])))
+    return _mag_by_field(*o[:3]), _by_field(*o[3:])
 
 
 def internal_power(fits, atten1):

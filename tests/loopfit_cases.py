@@ -7,7 +7,9 @@ arithmetic is one IEEE operation per element and is never fused, so the per-poin
 over the window's points; sin, cos and atan2 go through `math` one element at a time (the C
 library's, which the host twin calls as well). The 64 lane partials are an array [66][64] to which
 round r adds the I terms and then the Q terms of points 64 r + l, and the butterfly is p = p + p[l ^ m].
-The Cholesky and the iteration are scalar Python floats.
+The Cholesky and the iteration are scalar Python floats. The solver (csrc/lm_common.h: lane_sums_ref,
+step_ref, run_start_ref) is restated once, here, for any number of parameters; tests/magfit_cases.py
+runs its own model through the same functions.
 
 Trig(rng) moves every sin, cos, atan2 (and log10) result by one ulp up or down at random. The window
 weights are not moved: the host entry makes them for device and twin alike. The change this makes
@@ -22,9 +24,7 @@ import numpy as np
 from mkids_sdr_amd import _lib, roach
 
 PI = 3.141592653589793
-NP, NA, LANES = 10, 55, 64
-IU = np.array([i for i in range(NP) for j in range(i + 1)])
-JU = np.array([j for i in range(NP) for j in range(i + 1)])
+NP, LANES = 10, 64
 LANE = np.arange(LANES)
 FIT_DT = np.dtype(_lib.LOOP_FIT_DTYPE)
 INT_FIELDS = ('cidx', 'low', 'high', 'n', 'best_start', 'evals', 'status')
@@ -208,32 +208,50 @@ def chisq_ref(p, x, yI, yQ, wI, wQ, trig=EXACT):
 
 
 def sums_ref(p, x, yI, yQ, wI, wQ, trig):
-    """-> (A [55], g [10], chi) as Python floats: 64 lane partials, then the butterfly."""
+    """-> (A [55], g [10], chi) as Python floats: a point adds its I terms, then its Q terms."""
     _, _, rI, rQ, JI, JQ = terms_ref(p, x, yI, yQ, wI, wQ, trig)
-    n = len(x)
+    return lane_sums_ref([(JI, rI), (JQ, rQ)])
+
+
+# ---- the solver (csrc/lm_common.h), for any number of parameters N ------------------------------------
+_TRI = {}
+
+
+def lane_sums_ref(blocks):
+    """blocks: the (J [N][n], r [n]) term blocks a point adds, in their order -> (A [N (N + 1) / 2],
+    g [N], chi) as Python floats: 64 lane partials, round r adding every block's terms of points
+    64 r + l in turn, then the butterfly."""
+    N, n = blocks[0][0].shape
+    if N not in _TRI:
+        _TRI[N] = (np.array([i for i in range(N) for j in range(i + 1)]),
+                   np.array([j for i in range(N) for j in range(i + 1)]))
+    iu, ju = _TRI[N]
+    NA = len(iu)
     R = (n + LANES - 1) // LANES
-    acc = np.zeros((NA + NP + 1, LANES))
+    acc = np.zeros((NA + N + 1, LANES))
     with np.errstate(all='ignore'):
-        TI, TQ = np.zeros((2, NA + NP + 1, R * LANES))
-        for T, J, r in ((TI, JI, rI), (TQ, JQ, rQ)):
-            T[:NA, :n], T[NA:NA + NP, :n], T[NA + NP, :n] = J[IU] * J[JU], J * r, r * r
-        TI, TQ = TI.reshape(NA + NP + 1, R, LANES), TQ.reshape(NA + NP + 1, R, LANES)
+        Ts = []
+        for J, r in blocks:
+            T = np.zeros((NA + N + 1, R * LANES))
+            T[:NA, :n], T[NA:NA + N, :n], T[NA + N, :n] = J[iu] * J[ju], J * r, r * r
+            Ts.append(T.reshape(NA + N + 1, R, LANES))
         for rd in range(R):
             valid = (rd * LANES + LANE) < n
-            acc = np.where(valid, acc + TI[:, rd, :], acc)
-            acc = np.where(valid, acc + TQ[:, rd, :], acc)
+            for T in Ts:
+                acc = np.where(valid, acc + T[:, rd, :], acc)
         for m in (32, 16, 8, 4, 2, 1):
             acc = acc + acc[:, LANE ^ m]
     col = acc[:, 0].tolist()
-    return col[:NA], col[NA:NA + NP], col[NA + NP]
+    return col[:NA], col[NA:NA + N], col[NA + N]
 
 
 def step_ref(A, g, lam, p, lo, hi):
-    """-> (trial or None, nfree): the Cholesky of loopfit_common.h step."""
-    fr = [hi[i] > lo[i] and A[ix(i, i)] > 0.0 for i in range(NP)]
+    """-> (trial or None, nfree): the Cholesky of lm_common.h step at len(p) parameters."""
+    N = len(p)
+    fr = [hi[i] > lo[i] and A[ix(i, i)] > 0.0 for i in range(N)]
     nf = sum(fr)
-    L = [0.0] * NA
-    for j in range(NP):
+    L = [0.0] * len(A)
+    for j in range(N):
         ajj = A[ix(j, j)]
         s = ajj + lam * ajj if fr[j] else 1.0
         for k in range(j):
@@ -242,28 +260,28 @@ def step_ref(A, g, lam, p, lo, hi):
             return None, nf
         d = math.sqrt(s)
         L[ix(j, j)] = d
-        for i in range(j + 1, NP):
+        for i in range(j + 1, N):
             t = A[ix(i, j)] if fr[i] and fr[j] else 0.0
             for k in range(j):
                 t = t - L[ix(i, k)] * L[ix(j, k)]
             L[ix(i, j)] = t / d
-    y = [0.0] * NP
-    for i in range(NP):
+    y = [0.0] * N
+    for i in range(N):
         t = g[i] if fr[i] else 0.0
         for k in range(i):
             t = t - L[ix(i, k)] * y[k]
         y[i] = t / L[ix(i, i)]
-    for i in range(NP - 1, -1, -1):
+    for i in range(N - 1, -1, -1):
         t = y[i]
-        for k in range(i + 1, NP):
+        for k in range(i + 1, N):
             t = t - L[ix(k, i)] * y[k]
         y[i] = t / L[ix(i, i)]
-    return [clip(p[i] + y[i], lo[i], hi[i]) for i in range(NP)], nf
+    return [clip(p[i] + y[i], lo[i], hi[i]) for i in range(N)], nf
 
 
-def run_start_ref(p, lo, hi, win, max_iter, ftol, trig):
-    """-> (p, chi, evals, hit_max)."""
-    A, g, chi = sums_ref(p, *win, trig)
+def run_start_ref(p, lo, hi, sums, max_iter, ftol):
+    """One start from p; sums(p) -> (A, g, chi), the model's combined sums -> (p, chi, evals, hit_max)."""
+    A, g, chi = sums(p)
     evals = 1
     if not math.isfinite(chi):
         return p, chi, evals, 0
@@ -279,7 +297,7 @@ def run_start_ref(p, lo, hi, win, max_iter, ftol, trig):
             continue
         if nfree == 0:
             return p, chi, evals, 0
-        A2, g2, chi2 = sums_ref(trial, *win, trig)
+        A2, g2, chi2 = sums(trial)
         evals += 1
         if math.isfinite(chi2) and chi2 < chi:
             rel = (chi - chi2) / chi
@@ -331,7 +349,8 @@ def fit_ref(freq, I, Q, draws, isd=None, qsd=None, qguess=None, max_iter=200, ft
         if status == 0:
             qg = None if qguess is None else float(qguess[c])
             for s in range(S):
-                r = run_start_ref(start_ref(lo, hi, base, s, draws[c, s].tolist(), qg), lo, hi, win, max_iter, ftol, trig)
+                r = run_start_ref(start_ref(lo, hi, base, s, draws[c, s].tolist(), qg), lo, hi,
+                                  lambda p: sums_ref(p, *win, trig), max_iter, ftol)
                 call[c, s] = r[1]
                 if math.isfinite(r[1]) and (best is None or r[1] < best[1][1]):
                     best = (s, r)

@@ -7,8 +7,9 @@ arithmetic (+, -, x, /, sqrt, abs) is one IEEE operation per element and is neve
 per-point terms are arrays over the sweep's points. The 64 lane partials are an array [28][64] (21
 rows of A, 6 of g, chi^2) to which round r adds the terms of points 64 r + l, and the butterfly is
 p = p + p[l ^ m]. The Cholesky and the iteration are scalar Python floats. The model calls no library
-function, so the host twin and the device are held to the restatement bit for bit. The
-velocity-maximum index is the loop fit's (loopfit_cases.window_ref).
+function, so the host twin and the device are held to the restatement bit for bit. The solver
+(lane partials and butterfly, step, one start) and the velocity-maximum index are the loop fit's
+restatements (loopfit_cases lane_sums_ref, step_ref, run_start_ref, window_ref).
 """
 import ctypes
 import math
@@ -18,10 +19,7 @@ import numpy as np
 import loopfit_cases as lc
 from mkids_sdr_amd import _lib, loopfit
 
-NP, NA, LANES = 6, 21, 64
-IU = np.array([i for i in range(NP) for j in range(i + 1)])
-JU = np.array([j for i in range(NP) for j in range(i + 1)])
-LANE = np.arange(LANES)
+NP = 6
 FIT_DT = np.dtype(_lib.MAG_FIT_DTYPE)
 INT_FIELDS = ('cidx', 'best_start', 'evals', 'status')
 FLOAT_FIELDS = ('p', 'chisq', 'norm')
@@ -29,7 +27,7 @@ FAIL_BITS = _lib.LOOP_NONFINITE | _lib.LOOP_FLAT | _lib.LOOP_NO_FIT
 NAN = float('nan')
 W = 1.0 / 1e-5
 Q_FAIL = 50000.0
-ix, clip, same_bits = lc.ix, lc.clip, lc.same_bits
+clip, same_bits = lc.clip, lc.same_bits
 
 
 # ---- the data -----------------------------------------------------------------------------------------
@@ -92,87 +90,9 @@ def model_ref(p, x):
 
 
 def sums_ref(p, x, y):
-    """-> (A [21], g [6], chi) as Python floats: 64 lane partials, then the butterfly."""
+    """-> (A [21], g [6], chi) as Python floats: a point adds one block of terms."""
     _, res, J = terms_ref(p, x, y)
-    n = len(x)
-    R = (n + LANES - 1) // LANES
-    acc = np.zeros((NA + NP + 1, LANES))
-    with np.errstate(all='ignore'):
-        T = np.zeros((NA + NP + 1, R * LANES))
-        T[:NA, :n], T[NA:NA + NP, :n], T[NA + NP, :n] = J[IU] * J[JU], J * res, res * res
-        T = T.reshape(NA + NP + 1, R, LANES)
-        for rd in range(R):
-            valid = (rd * LANES + LANE) < n
-            acc = np.where(valid, acc + T[:, rd, :], acc)
-        for m in (32, 16, 8, 4, 2, 1):
-            acc = acc + acc[:, LANE ^ m]
-    col = acc[:, 0].tolist()
-    return col[:NA], col[NA:NA + NP], col[NA + NP]
-
-
-def step_ref(A, g, lam, p, lo, hi):
-    """-> (trial or None, nfree): the Cholesky of loopfit_common.h step at six parameters."""
-    fr = [hi[i] > lo[i] and A[ix(i, i)] > 0.0 for i in range(NP)]
-    nf = sum(fr)
-    L = [0.0] * NA
-    for j in range(NP):
-        ajj = A[ix(j, j)]
-        s = ajj + lam * ajj if fr[j] else 1.0
-        for k in range(j):
-            s = s - L[ix(j, k)] * L[ix(j, k)]
-        if not (s > 0.0 and math.isfinite(s)):
-            return None, nf
-        d = math.sqrt(s)
-        L[ix(j, j)] = d
-        for i in range(j + 1, NP):
-            t = A[ix(i, j)] if fr[i] and fr[j] else 0.0
-            for k in range(j):
-                t = t - L[ix(i, k)] * L[ix(j, k)]
-            L[ix(i, j)] = t / d
-    y = [0.0] * NP
-    for i in range(NP):
-        t = g[i] if fr[i] else 0.0
-        for k in range(i):
-            t = t - L[ix(i, k)] * y[k]
-        y[i] = t / L[ix(i, i)]
-    for i in range(NP - 1, -1, -1):
-        t = y[i]
-        for k in range(i + 1, NP):
-            t = t - L[ix(k, i)] * y[k]
-        y[i] = t / L[ix(i, i)]
-    return [clip(p[i] + y[i], lo[i], hi[i]) for i in range(NP)], nf
-
-
-def run_start_ref(p, lo, hi, x, y, max_iter, ftol):
-    """-> (p, chi, evals, hit_max)."""
-    A, g, chi = sums_ref(p, x, y)
-    evals = 1
-    if not math.isfinite(chi):
-        return p, chi, evals, 0
-    lam = 1e-3
-    while True:
-        if evals >= max_iter:
-            return p, chi, evals, 1
-        trial, nfree = step_ref(A, g, lam, p, lo, hi)
-        if trial is None:
-            lam = lam * 10.0
-            if lam > 1e12:
-                return p, chi, evals, 0
-            continue
-        if nfree == 0:
-            return p, chi, evals, 0
-        A2, g2, chi2 = sums_ref(trial, x, y)
-        evals += 1
-        if math.isfinite(chi2) and chi2 < chi:
-            rel = (chi - chi2) / chi
-            p, chi, A, g = trial, chi2, A2, g2
-            lam = max(lam / 10.0, 1e-12)
-            if rel <= ftol:
-                return p, chi, evals, 0
-        else:
-            lam = lam * 10.0
-            if lam > 1e12:
-                return p, chi, evals, 0
+    return lc.lane_sums_ref([(J, res)])
 
 
 def fit_ref(freq, I, Q, draws, max_iter=200, ftol=1e-10):
@@ -191,7 +111,8 @@ def fit_ref(freq, I, Q, draws, max_iter=200, ftol=1e-10):
         best = None
         if status == 0:
             for s in range(S):
-                r = run_start_ref(start_ref(lo, hi, f0, s, float(draws[c, s])), lo, hi, freq[c], y, max_iter, ftol)
+                r = lc.run_start_ref(start_ref(lo, hi, f0, s, float(draws[c, s])), lo, hi,
+                                     lambda p: sums_ref(p, freq[c], y), max_iter, ftol)
                 call[c, s] = r[1]
                 if math.isfinite(r[1]) and (best is None or r[1] < best[1][1]):
                     best = (s, r)
