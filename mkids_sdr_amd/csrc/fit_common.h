@@ -1,9 +1,10 @@
 // The pulse-height fit (include/mkidgpu.h mkid_pulse_fit states it), one definition for the kernel
-// of k_heights_fit.hip and for the host entry point mkid_pulse_fit_host: a packet's channel and
-// unwrapped stamp, the test that its search window lies inside the rows, and the choice of the lag
-// with the 3-point parabolic vertex around it. The vertex is the reference's peakfit
-// (Utils/bin.py:12-16), y2 - (y3 - y1)^2 / (8 (y3 + y1 - 2 y2)), written with the two non-negative
-// differences a = y2 - y1 and b = y2 - y3 so that the same terms give the vertex's position.
+// of k_heights_fit.hip and for the host entry point mkid_pulse_fit_host: the test that a packet's
+// search window lies inside the rows (its channel and unwrapped stamp are pkt_common.h decode's),
+// and the choice of the lag with the 3-point parabolic vertex around it. The vertex is the
+// reference's peakfit (Utils/bin.py:12-16), y2 - (y3 - y1)^2 / (8 (y3 + y1 - 2 y2)), written with the
+// two non-negative differences a = y2 - y1 and b = y2 - y3 so that the same terms give the vertex's
+// position.
 #pragma once
 #include <stdint.h>
 
@@ -23,19 +24,6 @@ constexpr int kMaxCoeff = 4096;  // mkid_set_pulse_filter's bound
 
 FIT_HD bool params_ok(int32_t search, int32_t polarity) {
     return search >= 0 && search <= kMaxSearch && (polarity == 1 || polarity == -1);
-}
-
-// Channel and global phase index of a wide packet: the 28-bit stamp unwrapped into
-// [j0 - 2^27, j0 + 2^27), exactly as k_pulse_heights does.
-struct Stamp {
-    int32_t ch;
-    int64_t jg;
-};
-FIT_HD Stamp decode(uint64_t w, int64_t j0) {
-    const int64_t mask = (int64_t)MKID_PKT_TS_MASK;
-    const int64_t ts = (int64_t)(w & MKID_PKT_TS_MASK);
-    const int64_t base = j0 > ((int64_t)1 << 27) ? j0 - ((int64_t)1 << 27) : 0;
-    return Stamp{(int32_t)((w >> MKID_PKT_CH_SHIFT) & 0xFFF), base + ((ts - (base & mask)) & mask)};
 }
 
 // Rows r0 - L .. r0 + L + ncoeff - 1 (relative to the call's first row) inside (hrows carried rows,

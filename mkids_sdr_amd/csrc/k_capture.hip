@@ -6,7 +6,7 @@
 // Contract (include/mkidgpu.h mkid_capture_pulses; tests/capture_ref.py is its numpy statement).
 // The capture is configured with length L, pre and max_per_ch R. A stream segment is a run of calls
 // whose j0 each equal the previous j0 + rows; it covers global phase rows [j_first, j_end).
-//   - a packet's 28-bit stamp is unwrapped as in k_heights.hip: base = max(j0 - 2^27, 0),
+//   - a packet's 28-bit stamp is unwrapped by pkt::decode (pkt_common.h): base = max(j0 - 2^27, 0),
 //     jg = base + ((ts - base) mod 2^28), with the j0 of the call that delivers the packet;
 //   - a packet of channel c < C is eligible when its window start s = jg - pre >= j_first and the
 //     context still carries row s (s >= j0 - carried rows: true for every packet passed with the
@@ -44,18 +44,12 @@ constexpr int kCapPitch = kCapTile + 1;
 constexpr int kCapWaves = 4;          // waves per workgroup (plan: channels; tiles: 16 columns each)
 constexpr int kCapNear = 4;           // overlapping records per (tile, channel) whose stamps the search keeps
 
-__device__ __forceinline__ int64_t cap_unwrap(uint64_t w, int64_t j0) {
-    const int64_t ts = (int64_t)(w & MKID_PKT_TS_MASK);
-    const int64_t base = j0 > ((int64_t)1 << 27) ? j0 - ((int64_t)1 << 27) : 0;
-    return base + ((ts - (base & (int64_t)MKID_PKT_TS_MASK)) & (int64_t)MKID_PKT_TS_MASK);
-}
-
 // first index in [0, n) whose channel field is >= c (n if none); the list is channel-major
 __device__ __forceinline__ int64_t cap_lower(const uint64_t* ev, int64_t n, int c) {
     int64_t lo = 0, hi = n;
     while (lo < hi) {
         const int64_t mid = lo + ((hi - lo) >> 1);
-        if ((int)((ev[mid] >> MKID_PKT_CH_SHIFT) & 0xFFF) < c) lo = mid + 1; else hi = mid;
+        if (pkt::channel(ev[mid]) < c) lo = mid + 1; else hi = mid;
     }
     return lo;
 }
@@ -64,7 +58,7 @@ __global__ __launch_bounds__(64 * kCapWaves) void k_capture_plan(CaptureArgs a) 
     const int lane = threadIdx.x & 63;
     const int c = (int)blockIdx.x * kCapWaves + (threadIdx.x >> 6);
     if (c >= a.C) return;
-    const int64_t n = a.d_n ? (*a.d_n < a.n ? (*a.d_n < 0 ? 0 : *a.d_n) : a.n) : a.n;
+    const int64_t n = pkt::count(a.d_n, a.n);
     const int64_t lo = cap_lower(a.events, n, c), hi = cap_lower(a.events, n, c + 1);
     const int np = min(max(a.pend_n_in[c], 0), a.PC);
     const int64_t total = np + (hi - lo);
@@ -80,9 +74,9 @@ __global__ __launch_bounds__(64 * kCapWaves) void k_capture_plan(CaptureArgs a) 
             jg = a.pend_in[(size_t)c * a.PC + idx];
             ok = true;
         } else if (idx < total) {
-            const uint64_t w = a.events[lo + (idx - np)];
-            jg = cap_unwrap(w, a.j0);
-            ok = (int)((w >> MKID_PKT_CH_SHIFT) & 0xFFF) == c && jg - a.pre >= first;
+            const pkt::Stamp st = pkt::decode(a.events[lo + (idx - np)], a.j0);
+            jg = st.jg;
+            ok = st.ch == c && jg - a.pre >= first;
         }
         const bool comp = ok && jg - a.pre + a.L <= j_end;
         const bool pend = ok && !comp;

@@ -20,24 +20,18 @@ constexpr int kHeightWaves = 4;  // packets (waves) per 256-thread workgroup
 // a.d_n) so that a step launches with no host round trip; waves beyond it exit at once.
 __global__ __launch_bounds__(64 * kHeightWaves) void k_pulse_heights(HeightArgs a) {
     const int lane = threadIdx.x & 63;
-    const int64_t n = a.d_n ? (*a.d_n < a.n ? *a.d_n : a.n) : a.n;
+    const int64_t n = pkt::count(a.d_n, a.n);
     const int64_t nw = (int64_t)gridDim.x * kHeightWaves;
     for (int64_t p = (int64_t)blockIdx.x * kHeightWaves + (threadIdx.x >> 6); p < n; p += nw) {
-        const uint64_t w = a.events[p];
-        const int ch = (int)((w >> MKID_PKT_CH_SHIFT) & 0xFFF);
-        const int64_t ts = (int64_t)(w & MKID_PKT_TS_MASK);
-        // global phase index of the packet: the 28-bit stamp unwrapped into [j0 - 2^27, j0 + 2^27)
-        // (a packet emitted at a call's first sample is stamped at the previous call's last row)
-        const int64_t base = a.j0 > ((int64_t)1 << 27) ? a.j0 - ((int64_t)1 << 27) : 0;
-        const int64_t jg = base + ((ts - (base & (int64_t)MKID_PKT_TS_MASK)) & (int64_t)MKID_PKT_TS_MASK);
-        const int64_t r0 = jg - a.j0 - a.pre;  // first phase row of the window (< 0: history)
-        const bool inside = ch < a.C && r0 >= -a.hrows && r0 + a.ncoeff <= a.rows;
+        const pkt::Stamp st = pkt::decode(a.events[p], a.j0);
+        const int64_t r0 = st.jg - a.j0 - a.pre;  // first phase row of the window (< 0: history)
+        const bool inside = st.ch < a.C && r0 >= -a.hrows && r0 + a.ncoeff <= a.rows;
         float acc = 0.f;
         if (inside) {
-            const float* cf = a.coeff + (size_t)ch * a.ncoeff;
+            const float* cf = a.coeff + (size_t)st.ch * a.ncoeff;
             for (int i = lane; i < a.ncoeff; i += 64) {
                 const int64_t r = r0 + i;
-                const float v = r >= 0 ? a.phase[r * a.C + ch] : a.hist[(a.hrows + r) * a.C + ch];
+                const float v = r >= 0 ? a.phase[r * a.C + st.ch] : a.hist[(a.hrows + r) * a.C + st.ch];
                 acc = fmaf(cf[i], v, acc);
             }
         }
@@ -49,9 +43,8 @@ __global__ __launch_bounds__(64 * kHeightWaves) void k_pulse_heights(HeightArgs 
 
 hipError_t launch_pulse_heights(const HeightArgs& a, hipStream_t s) {
     if (a.n <= 0) return hipSuccess;
-    int64_t blocks = (a.n + kHeightWaves - 1) / kHeightWaves;
-    const int64_t cap = (int64_t)(a.ncu > 0 ? a.ncu : 256) * 32;  // 8 waves per SIMD on every CU, then grid-stride
-    if (blocks > cap) blocks = cap;
+    // a wave per packet until 8 waves per SIMD on every CU (32 workgroups of 4), then grid-stride
+    const int64_t blocks = pkt::grid_stride_blocks(a.n, kHeightWaves, a.ncu, 32);
     hipLaunchKernelGGL(k_pulse_heights, dim3((unsigned)blocks), dim3(64 * kHeightWaves), 0, s, a);
     return hipGetLastError();
 }

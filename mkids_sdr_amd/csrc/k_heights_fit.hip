@@ -31,11 +31,11 @@ __global__ __launch_bounds__(64 * plan::kFitWaves) void k_pulse_fit(FitArgs a) {
     float* hv = w + a.off_h;
     const int g = lane / a.nl, d = lane - g * a.nl;
     const bool works = g < a.G;
-    const int64_t n = a.d_n ? (*a.d_n < a.n ? *a.d_n : a.n) : a.n;
+    const int64_t n = pkt::count(a.d_n, a.n);
     const int64_t nw = (int64_t)gridDim.x * waves;
     const float nan = __builtin_nanf("");
     for (int64_t p = (int64_t)blockIdx.x * waves + wave; p < n; p += nw) {
-        const fit::Stamp st = fit::decode(a.events[p], a.j0);
+        const pkt::Stamp st = pkt::decode(a.events[p], a.j0);
         const int64_t r0 = st.jg - a.j0 - a.pre;
         if (!fit::inside(st.ch, a.C, r0, a.L, a.ncoeff, a.hrows, a.rows)) {   // wave-uniform
             if (lane == 0) {

@@ -30,21 +30,15 @@ namespace mkid {
 
 constexpr int kObsThreads = 256;
 
-__device__ __forceinline__ int64_t obs_count(const int64_t* d_n, int64_t n) {
-    if (!d_n) return n;
-    const int64_t v = *d_n;
-    return v < 0 ? 0 : (v < n ? v : n);
-}
-
 __global__ __launch_bounds__(kObsThreads) void k_obs_count(ObsCountArgs a) {
-    const int64_t n = obs_count(a.d_n, a.n);
+    const int64_t n = pkt::count(a.d_n, a.n);
     const int64_t stride = (int64_t)gridDim.x * kObsThreads;
     for (int64_t i = (int64_t)blockIdx.x * kObsThreads + threadIdx.x; i < n; i += stride) {
-        const int64_t k = obs::cell(fit::decode(a.events[i], a.j0), a.C, a.N, a.fs, a.n_seconds);
-        const bool first = i == 0 || obs::cell(fit::decode(a.events[i - 1], a.j0), a.C, a.N, a.fs, a.n_seconds) != k;
-        const bool last = i == n - 1 || obs::cell(fit::decode(a.events[i + 1], a.j0), a.C, a.N, a.fs, a.n_seconds) != k;
+        const int64_t k = obs::cell(pkt::decode(a.events[i], a.j0), a.C, a.N, a.fs, a.n_seconds);
+        const bool first = i == 0 || obs::cell(pkt::decode(a.events[i - 1], a.j0), a.C, a.N, a.fs, a.n_seconds) != k;
+        const bool last = i == n - 1 || obs::cell(pkt::decode(a.events[i + 1], a.j0), a.C, a.N, a.fs, a.n_seconds) != k;
         if (!first && !last) continue;
-        const uint64_t d = (last ? (uint64_t)(i + 1) : 0) - (first ? (uint64_t)i : 0);
+        const uint64_t d = pkt::run_delta(i, first, last);
         if (k >= 0)
             atomicAdd(reinterpret_cast<unsigned int*>(a.image) + k, (unsigned int)d);
         else
@@ -55,18 +49,15 @@ __global__ __launch_bounds__(kObsThreads) void k_obs_count(ObsCountArgs a) {
 
 hipError_t launch_count_photons(const ObsCountArgs& a, hipStream_t s) {
     if (a.n <= 0) return hipSuccess;
-    const int64_t need = (a.n + kObsThreads - 1) / kObsThreads, cap = (int64_t)(a.ncu > 0 ? a.ncu : 256) * 8;
-    hipLaunchKernelGGL(k_obs_count, dim3((unsigned)(need < cap ? need : cap)), dim3(kObsThreads), 0, s, a);
+    const int64_t blocks = pkt::grid_stride_blocks(a.n, kObsThreads, a.ncu, 8);
+    hipLaunchKernelGGL(k_obs_count, dim3((unsigned)blocks), dim3(kObsThreads), 0, s, a);
     return hipGetLastError();
 }
 
 // ---- spectra and the deferred list -----------------------------------------------------------
 ObsPlan plan_spectra(int64_t n, int32_t nbins, bool lds) {
     ObsPlan p{};
-    const int64_t want = (n + kObsSlice - 1) / kObsSlice;
-    p.blocks = (int32_t)(want < 1 ? 1 : (want > kObsMaxBlocks ? kObsMaxBlocks : want));
-    const int64_t per = (n + p.blocks - 1) / p.blocks;
-    p.slice = (per + kObsThreads - 1) / kObsThreads * kObsThreads;
+    p.cut = pkt::slices(n, kObsThreads);
     const int64_t row_bytes = (int64_t)(nbins + obs::kExtraCols) * 4;
     const int64_t fit = kObsLdsBytes / row_bytes;
     p.lds_rows = lds ? (int32_t)(fit < kObsMaxRows ? fit : kObsMaxRows) : 0;
@@ -77,19 +68,19 @@ ObsPlan plan_spectra(int64_t n, int32_t nbins, bool lds) {
 __global__ __launch_bounds__(kObsThreads) void k_obs_spectra(ObsSpectraArgs a) {
     extern __shared__ unsigned int obs_tab[];
     __shared__ int s_ndef;
-    const int64_t n = obs_count(a.d_n, a.n);
-    const int64_t b0 = (int64_t)blockIdx.x * a.slice;
-    const int64_t b1 = b0 + a.slice < n ? b0 + a.slice : n;
+    const int64_t n = pkt::count(a.d_n, a.n);
+    int64_t b0, b1;
+    pkt::bounds(blockIdx.x, a.slice, n, b0, b1);
     const int32_t cols = a.nbins + obs::kExtraCols;
     const int32_t tab_n = a.lds_rows * cols;
     if (threadIdx.x == 0) s_ndef = 0;
     for (int32_t i = threadIdx.x; i < tab_n; i += kObsThreads) obs_tab[i] = 0;
     __syncthreads();
     if (b0 < b1) {
-        const int32_t ch_first = fit::decode(a.events[b0], a.j0).ch;
+        const int32_t ch_first = pkt::decode(a.events[b0], a.j0).ch;
         int mine = 0;
         for (int64_t i = b0 + threadIdx.x; i < b1; i += kObsThreads) {
-            const fit::Stamp st = fit::decode(a.events[i], a.j0);
+            const pkt::Stamp st = pkt::decode(a.events[i], a.j0);
             if (st.ch >= a.C) continue;
             const float h = a.heights[i];
             if (a.deferred && obs::deferred(h, st.jg, a.j_defer)) {
@@ -148,9 +139,9 @@ __global__ __launch_bounds__(kObsMaxBlocks) void k_obs_scan(const int32_t* wg_co
 __global__ __launch_bounds__(kObsThreads) void k_obs_scatter(ObsSpectraArgs a) {
     __shared__ int wtot[kObsThreads / 64];
     if (a.wg_count[blockIdx.x] == 0) return;   // workgroup-uniform
-    const int64_t n = obs_count(a.d_n, a.n);
-    const int64_t b0 = (int64_t)blockIdx.x * a.slice;
-    const int64_t b1 = b0 + a.slice < n ? b0 + a.slice : n;
+    const int64_t n = pkt::count(a.d_n, a.n);
+    int64_t b0, b1;
+    pkt::bounds(blockIdx.x, a.slice, n, b0, b1);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     int64_t o = a.wg_off[blockIdx.x];
     for (int64_t t0 = b0; t0 < b1; t0 += kObsThreads) {   // workgroup-uniform trip count
@@ -159,7 +150,7 @@ __global__ __launch_bounds__(kObsThreads) void k_obs_scatter(ObsSpectraArgs a) {
         uint64_t word = 0;
         if (i < b1) {
             word = a.events[i];
-            const fit::Stamp st = fit::decode(word, a.j0);
+            const pkt::Stamp st = pkt::decode(word, a.j0);
             q = st.ch < a.C && obs::deferred(a.heights[i], st.jg, a.j_defer);
         }
         const uint64_t m = __ballot(q);
@@ -182,13 +173,13 @@ __global__ __launch_bounds__(kObsThreads) void k_obs_scatter(ObsSpectraArgs a) {
 hipError_t launch_height_spectra(const ObsSpectraArgs& a0, const ObsPlan& p, hipStream_t s) {
     if (a0.n <= 0) return hipSuccess;
     ObsSpectraArgs a = a0;
-    a.slice = p.slice, a.lds_rows = p.lds_rows;
-    hipLaunchKernelGGL(k_obs_spectra, dim3((unsigned)p.blocks), dim3(kObsThreads), (size_t)p.lds_bytes, s, a);
+    a.slice = p.cut.slice, a.lds_rows = p.lds_rows;
+    hipLaunchKernelGGL(k_obs_spectra, dim3((unsigned)p.cut.blocks), dim3(kObsThreads), (size_t)p.lds_bytes, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || !a.deferred) return e;
-    hipLaunchKernelGGL(k_obs_scan, dim3(1), dim3(kObsMaxBlocks), 0, s, a.wg_count, p.blocks, a.wg_off, a.cap_def, a.ndef);
+    hipLaunchKernelGGL(k_obs_scan, dim3(1), dim3(kObsMaxBlocks), 0, s, a.wg_count, p.cut.blocks, a.wg_off, a.cap_def, a.ndef);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_obs_scatter, dim3((unsigned)p.blocks), dim3(kObsThreads), 0, s, a);
+    hipLaunchKernelGGL(k_obs_scatter, dim3((unsigned)p.cut.blocks), dim3(kObsThreads), 0, s, a);
     return hipGetLastError();
 }
 
@@ -196,7 +187,7 @@ hipError_t launch_height_spectra(const ObsSpectraArgs& a0, const ObsPlan& p, hip
 __global__ __launch_bounds__(kObsThreads) void k_obs_concat(const uint64_t* a, const int64_t* d_na, int64_t cap_a,
                                                             const uint64_t* b, const int64_t* d_nb, int64_t cap_b,
                                                             uint64_t* out, int64_t cap_out, int64_t* nout) {
-    const int64_t na = obs_count(d_na, cap_a), nb = obs_count(d_nb, cap_b);
+    const int64_t na = pkt::count(d_na, cap_a), nb = pkt::count(d_nb, cap_b);
     const int64_t tot = na + nb, nw = tot < cap_out ? tot : cap_out;
     const int64_t stride = (int64_t)gridDim.x * kObsThreads;
     for (int64_t i = (int64_t)blockIdx.x * kObsThreads + threadIdx.x; i < nw; i += stride)
@@ -208,8 +199,8 @@ hipError_t launch_concat_packets(const uint64_t* a, const int64_t* d_na, int64_t
                                  const int64_t* d_nb, int64_t cap_b, uint64_t* out, int64_t cap_out, int64_t* nout,
                                  int32_t ncu, hipStream_t s) {
     const int64_t most = cap_a + cap_b < cap_out ? cap_a + cap_b : cap_out;
-    const int64_t need = (most + kObsThreads - 1) / kObsThreads, cap = (int64_t)(ncu > 0 ? ncu : 256) * 8;
-    const int64_t blocks = need < 1 ? 1 : (need < cap ? need : cap);
+    const int64_t need = pkt::grid_stride_blocks(most, kObsThreads, ncu, 8);
+    const int64_t blocks = need < 1 ? 1 : need;   // the counts are written even where nothing is copied
     hipLaunchKernelGGL(k_obs_concat, dim3((unsigned)blocks), dim3(kObsThreads), 0, s, a, d_na, cap_a, b, d_nb, cap_b, out,
                        cap_out, nout);
     return hipGetLastError();

@@ -4,7 +4,7 @@
 // A run is a maximal stretch of the list whose packets share a cell (or an `outside` counter); in
 // the device's order a cell's packets of a call are one run. Packet i goes to slot
 // base + (i - head) of its cell's row: head, the index of the first packet of its run, and base,
-// the cell's count before the run. The list is cut into slices (plan_photons), workgroup b taking
+// the cell's count before the run. The list is cut into slices (pkt::slices), workgroup b taking
 // slice b tile by tile, and the order between the steps comes from the kernel boundaries alone:
 // k_ph_heads  a packet is a run head when its left neighbour is of another cell (k_obs_count's
 //             test). head[i] = the last head at or before i inside the slice (a max-scan of
@@ -21,9 +21,12 @@
 //             cell's row, the height (and dt) copied into the slot found; the two counters of a
 //             workgroup go out as one atomic each.
 // No workgroup waits for another inside a kernel, and no floating-point atomic is used.
-// The ring forms (mkid_list_photons_ring, mkid_fill_photon_heights_ring) are the same kernels built
-// with obs::ring_cell for the cell: a slot's cells are distinct inside the window, so a cell's
-// packets of a call are still one run, and each of the four `outside` kinds is a run of its own.
+// The cell is obs::ring_cell's over the call's window: a slot's cells are distinct inside the window,
+// so a cell's packets of a call are one run, and each of the four `outside` kinds is a run of its
+// own. The plain forms (mkid_list_photons, mkid_fill_photon_heights) are the whole window. There
+// ring_cell is obs::cell, and the three list kernels are built a second time with it (kWhole): the
+// window's compares and its 64-bit modulo, two cells per packet, cost the list call 7 to 13 % at the
+// operating shape; the fill, one cell and a binary search per packet, has one build.
 #include "mkid_internal.h"
 #include "obs_common.h"
 
@@ -31,51 +34,26 @@ namespace mkid {
 
 constexpr int kPhThreads = 256;
 
-__device__ __forceinline__ int64_t ph_count(const int64_t* d_n, int64_t n) {
-    if (!d_n) return n;
-    const int64_t v = *d_n;
-    return v < 0 ? 0 : (v < n ? v : n);
+// The cell of a decoded packet in the call's window (PhotonArgs and PhotonFillArgs name it alike);
+// kWhole: the window is obs::whole(n_slots).
+template <bool kWhole, class A>
+__device__ __forceinline__ int64_t ph_cell(const A& a, const pkt::Stamp& st) {
+    if (kWhole) return obs::cell(st, a.C, a.N, a.fs, a.n_slots);
+    return obs::ring_cell(st, a.C, a.N, a.fs, obs::Window{a.sec0, a.sec_end, a.n_slots});
 }
 
-// The cell of a decoded packet by the form's arguments: the plain forms', or the ring forms' with
-// the window (n_seconds holds n_slots there). Each kernel below is built once for each.
-__device__ __forceinline__ int64_t ph_cell_of(const PhotonArgs& a, const fit::Stamp& st) {
-    return obs::cell(st, a.C, a.N, a.fs, a.n_seconds);
-}
-__device__ __forceinline__ int64_t ph_cell_of(const PhotonRingArgs& a, const fit::Stamp& st) {
-    return obs::ring_cell(st, a.C, a.N, a.fs, obs::Window{a.sec0, a.sec_end, a.n_seconds});
-}
-__device__ __forceinline__ int64_t ph_cell_of(const PhotonFillArgs& a, const fit::Stamp& st) {
-    return obs::cell(st, a.C, a.N, a.fs, a.n_seconds);
-}
-__device__ __forceinline__ int64_t ph_cell_of(const PhotonFillRingArgs& a, const fit::Stamp& st) {
-    return obs::ring_cell(st, a.C, a.N, a.fs, obs::Window{a.sec0, a.sec_end, a.n_seconds});
-}
-template <class A>
-__device__ __forceinline__ int64_t ph_cell(const A& a, int64_t i) {
-    return ph_cell_of(a, fit::decode(a.events[i], a.j0));
-}
-
-ObsPlan plan_photons(int64_t n) {
-    ObsPlan p{};
-    const int64_t want = (n + kObsSlice - 1) / kObsSlice;
-    p.blocks = (int32_t)(want < 1 ? 1 : (want > kObsMaxBlocks ? kObsMaxBlocks : want));
-    const int64_t per = (n + p.blocks - 1) / p.blocks;
-    p.slice = (per + kPhThreads - 1) / kPhThreads * kPhThreads;
-    return p;
-}
-
-template <class A>
-__global__ __launch_bounds__(kPhThreads) void k_ph_heads(A a) {
+template <bool kWhole>
+__global__ __launch_bounds__(kPhThreads) void k_ph_heads(PhotonArgs a) {
     __shared__ int64_t wlast[kPhThreads / 64];
-    const int64_t n = ph_count(a.d_n, a.n);
-    const int64_t b0 = (int64_t)blockIdx.x * a.slice;
-    const int64_t b1 = b0 + a.slice < n ? b0 + a.slice : n;
+    const int64_t n = pkt::count(a.d_n, a.n);
+    int64_t b0, b1;
+    pkt::bounds(blockIdx.x, a.slice, n, b0, b1);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     int64_t run = -1;   // the last head of the tiles walked so far
     for (int64_t t0 = b0; t0 < b1; t0 += kPhThreads) {   // workgroup-uniform trip count
         const int64_t i = t0 + threadIdx.x;
-        const bool head = i < b1 && (i == 0 || ph_cell(a, i - 1) != ph_cell(a, i));
+        const bool head = i < b1 && (i == 0 || ph_cell<kWhole>(a, pkt::decode(a.events[i - 1], a.j0)) !=
+                                                   ph_cell<kWhole>(a, pkt::decode(a.events[i], a.j0)));
         const uint64_t m = __ballot(head);
         const int64_t w0 = t0 + w * 64;
         if (lane == 0) wlast[w] = m ? w0 + 63 - __clzll(m) : -1;
@@ -117,17 +95,17 @@ __global__ __launch_bounds__(kObsMaxBlocks) void k_ph_scan(int64_t* carry, int32
     if (t < blocks) carry[t] = ex;
 }
 
-template <class A>
-__global__ __launch_bounds__(kPhThreads) void k_ph_base(A a) {
-    const int64_t n = ph_count(a.d_n, a.n);
-    const int64_t b0 = (int64_t)blockIdx.x * a.slice;
-    const int64_t b1 = b0 + a.slice < n ? b0 + a.slice : n;
+template <bool kWhole>
+__global__ __launch_bounds__(kPhThreads) void k_ph_base(PhotonArgs a) {
+    const int64_t n = pkt::count(a.d_n, a.n);
+    int64_t b0, b1;
+    pkt::bounds(blockIdx.x, a.slice, n, b0, b1);
     const int64_t carry = a.carry[blockIdx.x];
     for (int64_t i = b0 + threadIdx.x; i < b1; i += kPhThreads) {
         int64_t h = a.head[i];
         if (h < 0) a.head[i] = h = carry;   // packet 0 is a head, so a slice after the first has one before it
-        const int64_t k = ph_cell(a, i);
-        if (i != n - 1 && ph_cell(a, i + 1) == k) continue;
+        const int64_t k = ph_cell<kWhole>(a, pkt::decode(a.events[i], a.j0));
+        if (i != n - 1 && ph_cell<kWhole>(a, pkt::decode(a.events[i + 1], a.j0)) == k) continue;
         const uint64_t len = (uint64_t)(i + 1 - h);
         if (k >= 0)
             a.base[h] = atomicAdd(reinterpret_cast<unsigned int*>(a.image) + k, (unsigned int)len);
@@ -136,19 +114,19 @@ __global__ __launch_bounds__(kPhThreads) void k_ph_base(A a) {
     }
 }
 
-template <class A>
-__global__ __launch_bounds__(kPhThreads) void k_ph_rows(A a) {
+template <bool kWhole>
+__global__ __launch_bounds__(kPhThreads) void k_ph_rows(PhotonArgs a) {
     __shared__ unsigned int s_drop;
-    const int64_t n = ph_count(a.d_n, a.n);
-    const int64_t b0 = (int64_t)blockIdx.x * a.slice;
-    const int64_t b1 = b0 + a.slice < n ? b0 + a.slice : n;
+    const int64_t n = pkt::count(a.d_n, a.n);
+    int64_t b0, b1;
+    pkt::bounds(blockIdx.x, a.slice, n, b0, b1);
     if (threadIdx.x == 0) s_drop = 0;
     __syncthreads();
     unsigned int drop = 0;
     for (int64_t i = b0 + threadIdx.x; i < b1; i += kPhThreads) {
         const uint64_t word = a.events[i];
-        const fit::Stamp st = fit::decode(word, a.j0);
-        const int64_t k = ph_cell_of(a, st);
+        const pkt::Stamp st = pkt::decode(word, a.j0);
+        const int64_t k = ph_cell<kWhole>(a, st);
         if (k < 0) continue;
         const int64_t h = a.head[i];
         const uint32_t slot = a.base[h] + (uint32_t)(i - h);   // modulo 2^32, as the image counts
@@ -165,41 +143,41 @@ __global__ __launch_bounds__(kPhThreads) void k_ph_rows(A a) {
         atomicAdd(reinterpret_cast<unsigned long long*>(a.dropped), (unsigned long long)s_drop);
 }
 
-template <class A>
-static hipError_t launch_list(const A& a0, const ObsPlan& p, hipStream_t s) {
-    if (a0.n <= 0) return hipSuccess;
-    A a = a0;
-    a.slice = p.slice;
+template <bool kWhole>
+static hipError_t launch_list(const PhotonArgs& a, const pkt::Slices& p, hipStream_t s) {
     const dim3 grid((unsigned)p.blocks), wg(kPhThreads);
-    hipLaunchKernelGGL(k_ph_heads<A>, grid, wg, 0, s, a);
+    hipLaunchKernelGGL(k_ph_heads<kWhole>, grid, wg, 0, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_ph_scan, dim3(1), dim3(kObsMaxBlocks), 0, s, a.carry, p.blocks);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_ph_base<A>, grid, wg, 0, s, a);
+    hipLaunchKernelGGL(k_ph_base<kWhole>, grid, wg, 0, s, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_ph_rows<A>, grid, wg, 0, s, a);
+    hipLaunchKernelGGL(k_ph_rows<kWhole>, grid, wg, 0, s, a);
     return hipGetLastError();
 }
 
-hipError_t launch_list_photons(const PhotonArgs& a, const ObsPlan& p, hipStream_t s) { return launch_list(a, p, s); }
-hipError_t launch_list_photons_ring(const PhotonRingArgs& a, const ObsPlan& p, hipStream_t s) {
-    return launch_list(a, p, s);
+hipError_t launch_list_photons(const PhotonArgs& a0, hipStream_t s) {
+    if (a0.n <= 0) return hipSuccess;
+    const pkt::Slices p = pkt::slices(a0.n, kPhThreads);
+    PhotonArgs a = a0;
+    a.slice = p.slice;
+    const bool whole = a.sec0 == 0 && a.sec_end == a.n_slots;   // obs::whole: every plain call
+    return whole ? launch_list<true>(a, p, s) : launch_list<false>(a, p, s);
 }
 
 // ---- heights into the rows ---------------------------------------------------------------------
-template <class A>
-__global__ __launch_bounds__(kPhThreads) void k_ph_fill(A a) {
+__global__ __launch_bounds__(kPhThreads) void k_ph_fill(PhotonFillArgs a) {
     __shared__ unsigned int s_fill[2];
-    const int64_t n = ph_count(a.d_n, a.n);
+    const int64_t n = pkt::count(a.d_n, a.n);
     if (threadIdx.x < 2) s_fill[threadIdx.x] = 0;
     __syncthreads();
     unsigned int found = 0, missed = 0;
     const int64_t stride = (int64_t)gridDim.x * kPhThreads;
     for (int64_t i = (int64_t)blockIdx.x * kPhThreads + threadIdx.x; i < n; i += stride) {
-        const fit::Stamp st = fit::decode(a.events[i], a.j0);
+        const pkt::Stamp st = pkt::decode(a.events[i], a.j0);
         if (st.ch >= a.C || obs::deferred(a.heights[i], st.jg, a.j_defer)) continue;
-        const int64_t k = ph_cell_of(a, st);
+        const int64_t k = ph_cell<false>(a, st);
         const int64_t at = k < 0 ? -1 : obs::find_stamp(a.stamps + k * a.K, obs::row_fill(a.image[k], a.K), st.jg);
         if (at < 0) {
             ++missed;
@@ -216,15 +194,11 @@ __global__ __launch_bounds__(kPhThreads) void k_ph_fill(A a) {
         atomicAdd(reinterpret_cast<unsigned long long*>(a.fill) + threadIdx.x, (unsigned long long)s_fill[threadIdx.x]);
 }
 
-template <class A>
-static hipError_t launch_fill(const A& a, hipStream_t s) {
+hipError_t launch_fill_photon_heights(const PhotonFillArgs& a, hipStream_t s) {
     if (a.n <= 0) return hipSuccess;
-    const int64_t need = (a.n + kPhThreads - 1) / kPhThreads, cap = (int64_t)(a.ncu > 0 ? a.ncu : 256) * 8;
-    hipLaunchKernelGGL(k_ph_fill<A>, dim3((unsigned)(need < cap ? need : cap)), dim3(kPhThreads), 0, s, a);
+    const int64_t blocks = pkt::grid_stride_blocks(a.n, kPhThreads, a.ncu, 8);
+    hipLaunchKernelGGL(k_ph_fill, dim3((unsigned)blocks), dim3(kPhThreads), 0, s, a);
     return hipGetLastError();
 }
-
-hipError_t launch_fill_photon_heights(const PhotonFillArgs& a, hipStream_t s) { return launch_fill(a, s); }
-hipError_t launch_fill_photon_heights_ring(const PhotonFillRingArgs& a, hipStream_t s) { return launch_fill(a, s); }
 
 }  // namespace mkid

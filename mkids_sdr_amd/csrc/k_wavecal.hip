@@ -102,11 +102,7 @@ __device__ __forceinline__ int64_t wcal_cell(const WcalCubeArgs& a, const wcal::
 }
 
 __global__ __launch_bounds__(kWcalThreads) void k_wcal_cube(WcalCubeArgs a) {
-    int64_t n = a.n;
-    if (a.d_n) {
-        const int64_t v = *a.d_n;
-        n = v < 0 ? 0 : (v < n ? v : n);
-    }
+    const int64_t n = pkt::count(a.d_n, a.n);
     const wcal::CubeRule r{a.j0, a.j_defer, a.C, a.nb, a.mode, a.hc, a.vlo, a.vinv};
     const int64_t stride = (int64_t)gridDim.x * kWcalThreads;
     for (int64_t i = (int64_t)blockIdx.x * kWcalThreads + threadIdx.x; i < n; i += stride) {
@@ -118,15 +114,14 @@ __global__ __launch_bounds__(kWcalThreads) void k_wcal_cube(WcalCubeArgs a) {
         const bool first = i == 0 || wcal_cell(a, r, i - 1, &en, &pn) != k;
         const bool last = i == n - 1 || wcal_cell(a, r, i + 1, &en, &pn) != k;
         if (!first && !last) continue;
-        const uint32_t d = (last ? (uint32_t)(i + 1) : 0u) - (first ? (uint32_t)i : 0u);
-        atomicAdd(reinterpret_cast<unsigned int*>(a.cube) + k, d);
+        atomicAdd(reinterpret_cast<unsigned int*>(a.cube) + k, (unsigned int)pkt::run_delta(i, first, last));
     }
 }
 
 hipError_t launch_energy_cube(const WcalCubeArgs& a, hipStream_t s) {
     if (a.n <= 0) return hipSuccess;
-    const int64_t need = (a.n + kWcalThreads - 1) / kWcalThreads, cap = (int64_t)(a.ncu > 0 ? a.ncu : 256) * 8;
-    hipLaunchKernelGGL(k_wcal_cube, dim3((unsigned)(need < cap ? need : cap)), dim3(kWcalThreads), 0, s, a);
+    const int64_t blocks = pkt::grid_stride_blocks(a.n, kWcalThreads, a.ncu, 8);
+    hipLaunchKernelGGL(k_wcal_cube, dim3((unsigned)blocks), dim3(kWcalThreads), 0, s, a);
     return hipGetLastError();
 }
 

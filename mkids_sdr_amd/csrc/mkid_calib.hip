@@ -30,31 +30,19 @@ int mkid_replay_trigger(mkid_ctx* c, const int16_t* d_raw, int64_t n, int64_t ld
     HIPCHK(c, hipSetDevice(c->device));
     const size_t nf = (size_t)nch * (size_t)((n + 31) / 32);
     const size_t nm = rc->mode == MKID_REPLAY_BLOCK ? (size_t)nch * (size_t)(n / rc->length) : 0;
-    if (nf > c->rflags_n || nm > c->rmeans_n) {   // grow the workspace
-        DevBuf<uint32_t> fl;
-        DevBuf<double> mn;
-        if (nf > c->rflags_n) HIPCHK(c, fl.alloc(nf));
-        if (nm > c->rmeans_n) HIPCHK(c, mn.alloc(nm));
-        HIPCHK(c, hipStreamSynchronize(c->stream));   // an earlier replay may still read the old ones
-        if (fl.get()) c->d_rflags = std::move(fl), c->rflags_n = nf;
-        if (mn.get()) c->d_rmeans = std::move(mn), c->rmeans_n = nm;
-    }
+    if (int err = c->rflags.reserve(c, nf)) return err;
+    if (int err = c->rmeans.reserve(c, nm)) return err;
     HIPCHK(c, launch_replay(d_raw, n, ld, nch, rc->mode, rc->length, rc->start, rc->need, rc->skip,
-                            rc->wrap_negative, rc->threshold_deg, c->d_rflags.get(), c->d_rmeans.get(), d_hits, cap,
+                            rc->wrap_negative, rc->threshold_deg, c->rflags.get(), c->rmeans.get(), d_hits, cap,
                             d_counts, c->stream));
     return MKID_OK;
 }
 
-// The workspace tables of `a` for one group of the plan `w`, in the context's bank workspace; a
-// smaller workspace is grown first (allocate, synchronise once, move in).
+// The workspace tables of `a` for one group of the plan `w`, in the context's bank workspace (grown
+// first where it is smaller).
 static int bank_tables(mkid_ctx* c, const plan::BankWs& w, BankArgs& a) {
-    if ((size_t)w.bytes > c->bankws_n) {
-        DevBuf<char> ws;
-        HIPCHK(c, ws.alloc((size_t)w.bytes));
-        HIPCHK(c, hipStreamSynchronize(c->stream));   // an earlier call may still use the old one
-        c->d_bankws = std::move(ws), c->bankws_n = (size_t)w.bytes;
-    }
-    char* p = c->d_bankws.get();
+    if (int rc = c->bankws.reserve(c, (size_t)w.bytes)) return rc;
+    char* p = c->bankws.get();
     a.rows = (double*)(p + w.rows), a.nrows = (double*)(p + w.nrows), a.peaks = (double*)(p + w.peaks);
     a.scratch = (double*)(p + w.scratch), a.tP = (double*)(p + w.tP), a.tPf = (double*)(p + w.tPf);
     a.noise = (double*)(p + w.noise), a.stats = (double*)(p + w.stats), a.work = (double*)(p + w.work);
@@ -277,7 +265,7 @@ int mkid_pulse_fit_host(const float* phase, int64_t rows, int32_t C, int64_t j0,
         return MKID_E_ARG;
     double H[2 * fit::kMaxSearch + 1];
     for (int64_t p = 0; p < n; ++p) {
-        const fit::Stamp st = fit::decode(events[p], j0);
+        const pkt::Stamp st = pkt::decode(events[p], j0);
         const int64_t r0 = st.jg - j0 - pre;
         fit::Result<double> r{NAN, NAN, NAN, INT32_MIN};
         if (fit::inside(st.ch, C, r0, search, ncoeff, 0, rows)) {
@@ -388,13 +376,8 @@ int mkid_phase_thresholds(mkid_ctx* c, const int16_t* d_raw, int64_t rows, int64
         FAIL(c, MKID_E_ARG, "phase_thresholds: need pointers, 1 <= rows < 2^31, 1 <= nch <= ld, finite nsigma >= 0");
     HIPCHK(c, hipSetDevice(c->device));
     const plan::ThrPlan p = plan::plan_thresholds(rows, ld, nch, ((uintptr_t)d_raw & 15) == 0, c->ncu);
-    if ((size_t)p.bytes > c->thrws_n) {   // grow the workspace
-        DevBuf<char> ws;
-        HIPCHK(c, ws.alloc((size_t)p.bytes));
-        HIPCHK(c, hipStreamSynchronize(c->stream));   // an earlier call may still use the old one
-        c->d_thrws = std::move(ws), c->thrws_n = (size_t)p.bytes;
-    }
-    HIPCHK(c, launch_thresholds(d_raw, rows, ld, nch, nsigma, p, c->d_thrws.get(), d_thr, d_stats, c->stream));
+    if (int rc = c->thrws.reserve(c, (size_t)p.bytes)) return rc;
+    HIPCHK(c, launch_thresholds(d_raw, rows, ld, nch, nsigma, p, c->thrws.get(), d_thr, d_stats, c->stream));
     return MKID_OK;
 }
 

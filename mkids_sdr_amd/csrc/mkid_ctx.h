@@ -42,6 +42,17 @@ public:
     }
 };
 
+// A workspace grown on demand. reserve() does nothing while the buffer holds `need` elements;
+// otherwise it allocates into a local, synchronises the context's stream once (an enqueued call may
+// still use the old buffer) and moves the new one in. A failed allocation leaves buffer and size.
+template <typename T>
+struct GrowBuf {
+    DevBuf<T> buf;
+    size_t n = 0;
+    T* get() const { return buf.get(); }
+    int reserve(mkid_ctx* c, size_t need);   // MKID_OK, or MKID_E_HIP with the context's error set
+};
+
 // A history carried between calls: `rows` rows of `row_bytes` in `cur`, rolled into `spare` (the
 // last `rows` of old rows + fresh rows), after which the two swap roles — enqueued kernels keep the
 // pointers they were launched with, so there is no device-to-device copy per call.
@@ -202,18 +213,15 @@ struct mkid_ctx : CtxHandles {
     DevBuf<int16_t> d_slot_ch;
     bool slot_order_on = true;
     // replay-trigger workspace (lazy, grown on demand)
-    DevBuf<uint32_t> d_rflags;
-    DevBuf<double> d_rmeans;
-    size_t rflags_n = 0, rmeans_n = 0;
+    GrowBuf<uint32_t> rflags;
+    GrowBuf<double> rmeans;
     // workspace of mkid_bank_filters and mkid_make_template (lazy, grown on demand; plan::plan_bank
     // carves it), and what mkid_make_template's one channel reads and writes besides (lazy)
-    DevBuf<char> d_bankws;
-    size_t bankws_n = 0;
+    GrowBuf<char> bankws;
     struct TplSlot { mkid_bank_result result; int32_t ready; };
     DevBuf<TplSlot> d_tplslot;
     // workspace of mkid_phase_thresholds (lazy, grown on demand; plan::plan_thresholds carves it)
-    DevBuf<char> d_thrws;
-    size_t thrws_n = 0;
+    GrowBuf<char> thrws;
     // tables of mkid_phase_noise_spectra for the last call's n (lazy; noise_plan.n == 0: none;
     // plan::noise_pack_tables lays them out; noise_plan keeps the passes and offsets only)
     DevBuf<char> d_noisetab;
@@ -221,8 +229,7 @@ struct mkid_ctx : CtxHandles {
     // mkid_welch_psd and mkid_iq_noise: the workspace (strip sums and the four-step transform's
     // segments; lazy, grown on demand inside plan::kBankBudget unless one channel needs more) and the
     // window and twiddle tables kept per nfft (lazy; a context sees a handful of lengths)
-    DevBuf<char> d_welchws;
-    size_t welchws_n = 0;
+    GrowBuf<char> welchws;
     struct WelchTab {
         int32_t nfft = 0;
         double S2 = 0.0;
@@ -238,8 +245,7 @@ struct mkid_ctx : CtxHandles {
     bool obs_lds = false;
     // workspace of mkid_list_photons (lazy, grown on demand with the list's n or cap;
     // mkid_internal.h photon_ws_bytes)
-    DevBuf<char> d_phws;
-    size_t phws_n = 0;
+    GrowBuf<char> phws;
     // host-API staging (lazy)
     DevBuf<uint32_t> d_in;
     DevBuf<float> d_phase_ws;
@@ -265,6 +271,16 @@ struct mkid_ctx : CtxHandles {
             return MKID_E_HIP;                                                             \
         }                                                                                  \
     } while (0)
+
+template <typename T>
+int GrowBuf<T>::reserve(mkid_ctx* c, size_t need) {
+    if (need <= n) return MKID_OK;
+    DevBuf<T> fresh;
+    HIPCHK(c, fresh.alloc(need));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    buf = std::move(fresh), n = need;
+    return MKID_OK;
+}
 
 // per-kernel timing (mkid_api.hip): events around a launch when kernel k is in the timing mask
 void tstart(mkid_ctx* c, int k, KTime* kt, hipStream_t s);

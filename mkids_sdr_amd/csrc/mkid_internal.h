@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "mkidgpu.h"
+#include "pkt_common.h"
 
 namespace mkid {
 
@@ -159,7 +160,7 @@ struct HeightArgs {
     float* heights;          // [n] out (NaN: window outside the rows or unknown channel)
     int64_t rows, j0, n;    // n: packets (or the bound on *d_n)
     int32_t C, ncoeff, pre;
-    const int64_t* d_n;     // nullable: device packet count (min(*d_n, n) packets are processed)
+    const int64_t* d_n;     // nullable: device packet count (pkt::count(d_n, n) packets are processed)
     // carried phase history: rows j0 - hrows .. j0 - 1 ([hrows][C]), read for windows that start
     // before the call's first row (hrows = 0: none)
     const float* hist;
@@ -175,7 +176,7 @@ struct FitArgs {
     const float* hist;       // [hrows][C] carried rows j0 - hrows .. j0 - 1 (hrows = 0: none)
     const uint64_t* events;  // [n] wide packets
     const float* coeff;      // [C][ncoeff]
-    const int64_t* d_n;      // nullable: device packet count (min(*d_n, n) packets are processed)
+    const int64_t* d_n;      // nullable: device packet count (pkt::count(d_n, n) packets are processed)
     float* heights;          // [n] fitted height (NaN: window outside the rows or unknown channel)
     float* dt;               // [n] nullable: vertex position in rows relative to the stamp
     int32_t* lag;            // [n] nullable: chosen lag (INT32_MIN where the height is NaN)
@@ -192,7 +193,7 @@ hipError_t launch_pulse_fit(FitArgs a, const plan::FitPlan& p, hipStream_t s);
 // mkid_count_photons (k_observe.hip): the count image and the two `outside` counters
 struct ObsCountArgs {
     const uint64_t* events;  // [n] wide packets
-    const int64_t* d_n;      // nullable: device packet count (min(*d_n, n) packets are read)
+    const int64_t* d_n;      // nullable: device packet count (pkt::count(d_n, n) packets are read)
     int32_t* image;          // [n_seconds][C]
     int64_t* outside;        // [2]
     int64_t n, j0, N, fs;    // fs: samples per second (an integer, obs_common.h fs_ok)
@@ -200,24 +201,22 @@ struct ObsCountArgs {
 };
 hipError_t launch_count_photons(const ObsCountArgs& a, hipStream_t s);
 
-// mkid_height_spectra (k_observe.hip). A call's grid and LDS table come from plan_spectra: at most
-// kObsMaxBlocks workgroups (one thread each in the scan of their deferred counts) of contiguous
-// slices of about kObsSlice packets, and an LDS table of as many channel rows as fit kObsLdsBytes,
-// kObsMaxRows at the most (a slice of the device's order spans few channels, and the table is
-// zeroed and flushed in full), none in the plain form.
-constexpr int kObsMaxBlocks = 1024;
-constexpr int kObsSlice = 2048;
+// mkid_height_spectra (k_observe.hip). A call's grid and LDS table come from plan_spectra: the
+// list's cut into slices (pkt_common.h slices, where kObsMaxBlocks and kObsSlice are), and an LDS
+// table of as many channel rows as fit kObsLdsBytes, kObsMaxRows at the most (a slice of the
+// device's order spans few channels, and the table is zeroed and flushed in full), none in the
+// plain form.
 constexpr int kObsLdsBytes = 32768;
 constexpr int kObsMaxRows = 16;
 struct ObsPlan {
-    int32_t blocks, lds_rows, lds_bytes, pad;
-    int64_t slice;
+    pkt::Slices cut;
+    int32_t lds_rows, lds_bytes;
 };
 ObsPlan plan_spectra(int64_t n, int32_t nbins, bool lds);
 struct ObsSpectraArgs {
     const uint64_t* events;  // [n] wide packets
     const float* heights;    // [n]
-    const int64_t* d_n;      // nullable: device packet count (min(*d_n, n) packets are read)
+    const int64_t* d_n;      // nullable: device packet count (pkt::count(d_n, n) packets are read)
     const float* lo;         // [C] lower edge of bin 0
     const float* inv;        // [C] 1 / bin width
     int32_t* spectra;        // [C][nbins + 3]
@@ -233,23 +232,26 @@ hipError_t launch_concat_packets(const uint64_t* a, const int64_t* d_na, int64_t
                                  const int64_t* d_nb, int64_t cap_b, uint64_t* out, int64_t cap_out, int64_t* nout,
                                  int32_t ncu, hipStream_t s);
 
-// mkid_list_photons and mkid_fill_photon_heights (k_photons.hip). The list call runs over slices
-// planned as the spectra's (plan_photons: at most kObsMaxBlocks of about kObsSlice packets) and
-// keeps, per packet, the index of the first packet of its run, and per run (at its head's index)
-// the cell's count before the run: photon_ws_bytes(n) of workspace, carved as below.
+// mkid_list_photons and mkid_fill_photon_heights (k_photons.hip) and their ring forms: the tables
+// are [n_slots][C][K] and the cell is obs::ring_cell's over the window (sec0, sec_end, n_slots); the
+// plain forms pass the whole window obs::whole(n_seconds). The list call runs over slices cut as the
+// spectra's (pkt::slices) and keeps, per packet, the index of the first packet of its run, and per
+// run (at its head's index) the cell's count before the run: photon_ws_bytes(n) of workspace,
+// carved as below.
 struct PhotonArgs {
     const uint64_t* events;  // [n] wide packets
-    const int64_t* d_n;      // nullable: device packet count (min(*d_n, n) packets are read)
-    int32_t* image;          // [n_seconds][C]
-    int64_t* outside;        // [2]
-    uint64_t* words;         // [n_seconds][C][K]
-    int64_t* stamps;         // [n_seconds][C][K]
+    const int64_t* d_n;      // nullable: device packet count (pkt::count(d_n, n) packets are read)
+    int32_t* image;          // [n_slots][C]
+    int64_t* outside;        // [4]; the whole window reaches only [0] and [1]
+    uint64_t* words;         // [n_slots][C][K]
+    int64_t* stamps;         // [n_slots][C][K]
     int64_t* dropped;        // [1]
     int64_t* head;           // workspace [n]: index of the first packet of packet i's run
     int64_t* carry;          // workspace [kObsMaxBlocks]: last run head of a slice, then of the slices before it
     uint32_t* base;          // workspace [n]: at a run head's index, the cell's count before the run
     int64_t n, j0, N, fs, slice;
-    int32_t C, n_seconds, K, layout;
+    int32_t C, n_slots, K, layout;
+    int64_t sec0, sec_end;   // the window's seconds (obs_common.h Window)
 };
 inline size_t photon_ws_bytes(int64_t n) { return (size_t)n * 12 + (size_t)kObsMaxBlocks * 8; }
 inline void photon_ws_carve(PhotonArgs& a, char* ws) {
@@ -257,32 +259,22 @@ inline void photon_ws_carve(PhotonArgs& a, char* ws) {
     a.carry = a.head + a.n;
     a.base = reinterpret_cast<uint32_t*>(a.carry + kObsMaxBlocks);
 }
-// the ring forms: the tables are [n_slots][C][K] with n_seconds holding n_slots, outside is [4]
-// (obs_common.h ring_cell); the plain forms keep the kernels without the window
-struct PhotonRingArgs : PhotonArgs {
-    int64_t sec0, sec_end;
-};
-ObsPlan plan_photons(int64_t n);
-hipError_t launch_list_photons(const PhotonArgs& a, const ObsPlan& p, hipStream_t s);
-hipError_t launch_list_photons_ring(const PhotonRingArgs& a, const ObsPlan& p, hipStream_t s);
+hipError_t launch_list_photons(const PhotonArgs& a, hipStream_t s);
 struct PhotonFillArgs {
     const uint64_t* events;  // [n] wide packets
     const float* heights;    // [n]
     const float* dt;         // nullable [n]
     const int64_t* d_n;      // nullable: device packet count
-    const int32_t* image;    // [n_seconds][C]
-    const int64_t* stamps;   // [n_seconds][C][K]
-    float* row_height;       // [n_seconds][C][K]
+    const int32_t* image;    // [n_slots][C]
+    const int64_t* stamps;   // [n_slots][C][K]
+    float* row_height;       // [n_slots][C][K]
     float* row_dt;           // nullable, the same shape
     int64_t* fill;           // [2] {found, not found}
     int64_t n, j0, j_defer, N, fs;
-    int32_t C, n_seconds, K, ncu;
-};
-struct PhotonFillRingArgs : PhotonFillArgs {
+    int32_t C, n_slots, K, ncu;
     int64_t sec0, sec_end;
 };
 hipError_t launch_fill_photon_heights(const PhotonFillArgs& a, hipStream_t s);
-hipError_t launch_fill_photon_heights_ring(const PhotonFillRingArgs& a, hipStream_t s);
 
 // mkid_pack_second and mkid_clear_second (k_pack.hip): slot sec mod n_slots of the [n_slots][C][K]
 // tables. A wave takes one (channel, tile of kPackTile slots) of the copy and of the clear.
@@ -318,7 +310,7 @@ struct CaptureArgs {
     const float* phase;      // [rows][C] rad, global phase rows j0 .. j0 + rows - 1
     const float* hist;       // [hrows][C] carried rows j0 - hrows .. j0 - 1 (hrows = 0: none)
     const uint64_t* events;  // [n] wide packets, channel-major, time-ascending within a channel
-    const int64_t* d_n;      // nullable: device packet count (min(*d_n, n) packets are read)
+    const int64_t* d_n;      // nullable: device packet count (pkt::count(d_n, n) packets are read)
     float* records;          // [C][R][L] caller's bank
     int64_t* stamps;         // [C][R] unwrapped stamp of each record
     int32_t* info;           // [C][2] {ready, dropped}
@@ -431,7 +423,7 @@ hipError_t launch_spectrum_lines(const WcalLinesArgs& a, int32_t nch, hipStream_
 struct WcalCubeArgs {
     const uint64_t* events;  // [n] wide packets
     const float* heights;    // [n]
-    const int64_t* d_n;      // nullable: device packet count (min(*d_n, n) packets are read)
+    const int64_t* d_n;      // nullable: device packet count (pkt::count(d_n, n) packets are read)
     const float* cal_f;      // [C][4]
     int32_t* cube;           // [C][nb + 3]
     float* energy;           // nullable [n]

@@ -43,16 +43,6 @@ WelchWs plan_welch(int64_t n, int32_t nfft, int32_t nch, int32_t want) {
     return w;
 }
 
-int grow_workspace(mkid_ctx* c, int64_t bytes) {
-    if ((size_t)bytes > c->welchws_n) {
-        DevBuf<char> ws;
-        HIPCHK(c, ws.alloc((size_t)bytes));
-        HIPCHK(c, hipStreamSynchronize(c->stream));   // an earlier call may still use the old one
-        c->d_welchws = std::move(ws), c->welchws_n = (size_t)bytes;
-    }
-    return MKID_OK;
-}
-
 // the context's tables for nfft, made and uploaded when a call first brings that length
 int tables_for(mkid_ctx* c, int32_t nfft, const mkid_ctx::WelchTab** out) {
     for (const auto& t : c->welch_tabs)
@@ -80,8 +70,8 @@ int run_groups(mkid_ctx* c, WelchArgs a, const WelchWs& w, const mkid_ctx::Welch
     a.nfft = nfft, a.nseg = w.nseg, a.nstrips = w.nstrips;
     a.w = t.w.get(), a.tw = t.tw.get();
     a.den = fs * t.S2;
-    a.part = (double*)c->d_welchws.get();
-    a.y = w.y_ch ? (double*)(c->d_welchws.get() + w.y_off) : nullptr;
+    a.part = (double*)c->welchws.get();
+    a.y = w.y_ch ? (double*)(c->welchws.get() + w.y_off) : nullptr;
     for (int64_t c0 = 0; c0 < nch; c0 += w.group) {   // the stream orders the groups' use of the workspace
         a.c0 = (int32_t)c0;
         a.g = (int32_t)std::min<int64_t>(w.group, nch - c0);
@@ -100,7 +90,7 @@ int mkid_welch_psd(mkid_ctx* c, const double* d_a, const double* d_b, int64_t n,
     if (!welch::psd_args_ok(d_a, n, ld, nch, nfft, fs, group, d_pa)) FAIL(c, MKID_E_ARG, "welch_psd: " WELCH_ARGS_MSG);
     HIPCHK(c, hipSetDevice(c->device));
     const WelchWs w = plan_welch(n, nfft, nch, group);
-    if (int rc = grow_workspace(c, w.bytes)) return rc;
+    if (int rc = c->welchws.reserve(c, (size_t)w.bytes)) return rc;
     const mkid_ctx::WelchTab* t = nullptr;
     if (int rc = tables_for(c, nfft, &t)) return rc;
     WelchArgs a{};
@@ -130,7 +120,7 @@ int mkid_iq_noise(mkid_ctx* c, const int16_t* d_i, const int16_t* d_q, int64_t n
         FAIL(c, MKID_E_ARG, "iq_noise: " IQN_ARGS_MSG);
     HIPCHK(c, hipSetDevice(c->device));
     const WelchWs wl = plan_welch(n, cfg->nfft_low, nch, cfg->group), wh = plan_welch(n, cfg->nfft_high, nch, cfg->group);
-    if (int rc = grow_workspace(c, std::max(wl.bytes, wh.bytes))) return rc;
+    if (int rc = c->welchws.reserve(c, (size_t)std::max(wl.bytes, wh.bytes))) return rc;
     const mkid_ctx::WelchTab *tl = nullptr, *th = nullptr;
     if (int rc = tables_for(c, cfg->nfft_low, &tl)) return rc;
     if (int rc = tables_for(c, cfg->nfft_high, &th)) return rc;

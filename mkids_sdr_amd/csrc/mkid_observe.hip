@@ -88,8 +88,10 @@ int mkid_concat_packets(mkid_ctx* c, const uint64_t* d_a, const int64_t* d_na, i
     return MKID_OK;
 }
 
-// The plain forms (w == nullptr: n_seconds, the kernels without the window) and the ring forms
-// (n_seconds holds n_slots) share everything but the argument check and the kernels' cell.
+// The plain forms (w == nullptr) are the ring forms over the whole window obs::whole(n_seconds), with
+// an argument check and a message of their own. For that window obs::ring_cell gives neither kEarly
+// (no second is below sec0 = 0) nor kOverrun (sec < sec_end = n_slots is inside the slots), so the
+// kernels touch only outside[0] and outside[1] of the plain forms' int64 [2].
 static int list_photons(mkid_ctx* c, const uint64_t* d_events, const int64_t* d_n, int64_t n, int64_t j0,
                         int32_t n_seconds, const obs::Window* w, int32_t K, int32_t layout, int32_t* d_image,
                         int64_t* d_outside, uint64_t* d_words, int64_t* d_stamps, int64_t* d_dropped) {
@@ -107,24 +109,14 @@ static int list_photons(mkid_ctx* c, const uint64_t* d_events, const int64_t* d_
              "(REFERENCE: C <= 254), an integer sample rate <= 2^43");
     HIPCHK(c, hipSetDevice(c->device));
     if (n == 0) return MKID_OK;
-    const size_t bytes = photon_ws_bytes(n);
-    if (bytes > c->phws_n) {   // grow the workspace
-        DevBuf<char> ws;
-        HIPCHK(c, ws.alloc(bytes));
-        HIPCHK(c, hipStreamSynchronize(c->stream));   // an earlier call may still use the old one
-        c->d_phws = std::move(ws), c->phws_n = bytes;
-    }
-    PhotonRingArgs a{};
+    if (int rc = c->phws.reserve(c, photon_ws_bytes(n))) return rc;
+    const obs::Window win = w ? *w : obs::whole(n_seconds);   // whole: outside[2] and [3] are never reached (above)
+    PhotonArgs a{};
     a.events = d_events, a.d_n = d_n, a.image = d_image, a.outside = d_outside, a.words = d_words, a.stamps = d_stamps;
     a.dropped = d_dropped, a.n = n, a.j0 = j0, a.N = c->N, a.fs = (int64_t)c->cfg.sample_rate;
-    a.C = c->C, a.n_seconds = w ? w->n_slots : n_seconds, a.K = K, a.layout = layout;
-    photon_ws_carve(a, c->d_phws.get());
-    if (w) {
-        a.sec0 = w->sec0, a.sec_end = w->sec_end;
-        HIPCHK(c, launch_list_photons_ring(a, plan_photons(n), c->stream));
-    } else {
-        HIPCHK(c, launch_list_photons(a, plan_photons(n), c->stream));
-    }
+    a.C = c->C, a.n_slots = win.n_slots, a.K = K, a.layout = layout, a.sec0 = win.sec0, a.sec_end = win.sec_end;
+    photon_ws_carve(a, c->phws.get());
+    HIPCHK(c, launch_list_photons(a, c->stream));
     return MKID_OK;
 }
 
@@ -177,17 +169,13 @@ static int fill_photon_heights(mkid_ctx* c, const uint64_t* d_events, const floa
              "0 <= sec0 <= sec_end ((sec_end + 1) sample_rate inside int64), 1 <= K <= 65536, an integer sample rate "
              "<= 2^43");
     HIPCHK(c, hipSetDevice(c->device));
-    PhotonFillRingArgs a{};
+    const obs::Window win = w ? *w : obs::whole(n_seconds);   // outside is not written: see list_photons
+    PhotonFillArgs a{};
     a.events = d_events, a.heights = d_heights, a.dt = d_dt, a.d_n = d_n, a.image = d_image, a.stamps = d_stamps;
     a.row_height = d_row_height, a.row_dt = d_row_dt, a.fill = d_fill;
     a.n = n, a.j0 = j0, a.j_defer = j_defer, a.N = c->N, a.fs = (int64_t)c->cfg.sample_rate;
-    a.C = c->C, a.n_seconds = w ? w->n_slots : n_seconds, a.K = K, a.ncu = c->ncu;
-    if (w) {
-        a.sec0 = w->sec0, a.sec_end = w->sec_end;
-        HIPCHK(c, launch_fill_photon_heights_ring(a, c->stream));
-    } else {
-        HIPCHK(c, launch_fill_photon_heights(a, c->stream));
-    }
+    a.C = c->C, a.n_slots = win.n_slots, a.K = K, a.ncu = c->ncu, a.sec0 = win.sec0, a.sec_end = win.sec_end;
+    HIPCHK(c, launch_fill_photon_heights(a, c->stream));
     return MKID_OK;
 }
 

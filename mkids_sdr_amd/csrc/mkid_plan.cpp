@@ -2,6 +2,7 @@
 // -fsanitize=address,undefined, into the CPU fuzz driver tools/plan_fuzz.cpp.
 #include <array>
 #include "mkid_plan.h"
+#include "pkt_common.h"
 
 #include <algorithm>
 #include <climits>
@@ -266,12 +267,9 @@ void merge_channel_major(uint64_t* ev, int64_t n) {
 int pack_reference(const uint64_t* wide, int64_t n, uint64_t* out) {
     for (int64_t i = 0; i < n; ++i) {
         const uint64_t w = wide[i];
-        const uint64_t ch = (w >> MKID_PKT_CH_SHIFT) & 0xFFF;
+        const int32_t ch = pkt::channel(w);
         if (ch >= 255) return -1;  // 8-bit channel field, 255 = end-of-second marker
-        const uint64_t pk = (w >> MKID_PKT_PEAK_SHIFT) & 0xFFF, bs = (w >> MKID_PKT_BASE_SHIFT) & 0xFFF;
-        const uint64_t p1 = (uint64_t)std::min<int64_t>(4095, std::max<int64_t>(0, (int64_t)pk - (int64_t)bs + 2048));
-        const uint64_t ts = w & 0xFFFFF;
-        out[i] = (ch << 56) | (pk << 44) | (p1 << 32) | (bs << 20) | ts;
+        out[i] = pkt::reference_word((uint64_t)ch, pkt::peak(w), pkt::base(w), w);   // the stamp's low 20 bits
     }
     return 0;
 }

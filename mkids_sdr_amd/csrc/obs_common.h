@@ -5,13 +5,14 @@
 // height, and which packets wait for their height; and, further down, the photon rows of
 // mkid_list_photons / mkid_fill_photon_heights (k_photons.hip), their ring forms, and the packed
 // second of mkid_pack_second / mkid_clear_second (k_pack.hip), with their host entry points. A
-// packet's channel and unwrapped stamp are fit::decode's. The host loops below are the whole of the host entry points, so that the CPU
-// sanitizer build (tools/plan_fuzz.cpp) runs them without HIP.
+// packet's channel and unwrapped stamp are pkt::decode's (pkt_common.h). The host loops below are the
+// whole of the host entry points, so that the CPU sanitizer build (tools/plan_fuzz.cpp) runs them
+// without HIP.
 #pragma once
 #include <stdint.h>
 
-#include "fit_common.h"
 #include "mkidgpu.h"
+#include "pkt_common.h"
 
 #if defined(__HIPCC__)
 #define OBS_HD __host__ __device__ inline
@@ -39,7 +40,7 @@ OBS_HD int64_t second(int64_t jg, int64_t N, int64_t fs) { return jg * N / fs; }
 
 // Where a packet is counted: cell sec C + ch of the image, or one of the two `outside` counters.
 constexpr int64_t kNonPixel = -1, kLate = -2;   // outside[0], outside[1]
-OBS_HD int64_t cell(const fit::Stamp& st, int32_t C, int64_t N, int64_t fs, int32_t n_seconds) {
+OBS_HD int64_t cell(const pkt::Stamp& st, int32_t C, int64_t N, int64_t fs, int32_t n_seconds) {
     if (st.ch >= C) return kNonPixel;
     const int64_t sec = second(st.jg, N, fs);
     return sec < n_seconds ? sec * C + st.ch : kLate;
@@ -75,7 +76,7 @@ inline bool count_args_ok(const uint64_t* events, int64_t n, int64_t j0, int32_t
 inline void count_host(const uint64_t* events, int64_t n, int64_t j0, int32_t N, double fs, int32_t C,
                        int32_t n_seconds, int32_t* image, int64_t* outside) {
     for (int64_t p = 0; p < n; ++p) {
-        const int64_t k = cell(fit::decode(events[p], j0), C, N, (int64_t)fs, n_seconds);
+        const int64_t k = cell(pkt::decode(events[p], j0), C, N, (int64_t)fs, n_seconds);
         if (k >= 0)
             ++image[k];
         else
@@ -94,7 +95,7 @@ inline void spectra_host(const uint64_t* events, const float* heights, int64_t n
                          int32_t C, const float* lo, const float* inv, int32_t nbins, int32_t* spectra,
                          uint64_t* deferred_out, int64_t cap_def, int64_t* ndef) {
     for (int64_t p = 0; p < n; ++p) {
-        const fit::Stamp st = fit::decode(events[p], j0);
+        const pkt::Stamp st = pkt::decode(events[p], j0);
         if (st.ch >= C) continue;
         if (deferred_out && deferred(heights[p], st.jg, j_defer)) {
             ++ndef[0];
@@ -121,15 +122,10 @@ OBS_HD bool layout_fits(int32_t layout, int32_t C) { return layout != MKID_ROW_R
 OBS_HD int64_t microsecond(int64_t jg, int64_t N, int64_t fs) { return jg * N % fs * 1000000 / fs; }
 
 // The word stored for wide packet w at microsecond us: the packet with its time field replaced
-// (packets.encode_wire wide), or the reference's fields (packets.encode_wire; p1 as
-// mkid_pack_reference).
+// (packets.encode_wire wide), or the reference's word with us as its time (pkt::reference_word).
 OBS_HD uint64_t row_word(uint64_t w, int64_t us, int32_t layout) {
     if (layout == MKID_ROW_WIDE) return (w & ~(uint64_t)MKID_PKT_TS_MASK) | (uint64_t)us;
-    const uint64_t ch = (w >> MKID_PKT_CH_SHIFT) & 0xFFF;
-    const int64_t peak = (int64_t)((w >> MKID_PKT_PEAK_SHIFT) & 0xFFF), base = (int64_t)((w >> MKID_PKT_BASE_SHIFT) & 0xFFF);
-    const int64_t d = peak - base + 2048;
-    const uint64_t p1 = (uint64_t)(d < 0 ? 0 : (d > 4095 ? 4095 : d));
-    return ch << 56 | (uint64_t)peak << 44 | p1 << 32 | (uint64_t)base << 20 | ((uint64_t)us & 0xFFFFF);
+    return pkt::reference_word((uint64_t)pkt::channel(w), pkt::peak(w), pkt::base(w), (uint64_t)us);
 }
 
 // Slots of a row that hold a packet, from the cell's count (modulo 2^32, as the image is kept).
@@ -164,7 +160,7 @@ OBS_HD bool window_ok(const Window& w, double fs) {
     return w.n_slots >= 1 && w.n_slots <= kMaxSlots && w.sec0 >= 0 && w.sec0 <= w.sec_end && fs_ok(fs) &&
            w.sec_end <= INT64_MAX / (int64_t)fs - 1;
 }
-OBS_HD int64_t ring_cell(const fit::Stamp& st, int32_t C, int64_t N, int64_t fs, const Window& w) {
+OBS_HD int64_t ring_cell(const pkt::Stamp& st, int32_t C, int64_t N, int64_t fs, const Window& w) {
     if (st.ch >= C) return kNonPixel;
     const int64_t sec = second(st.jg, N, fs);
     if (sec >= w.sec_end) return kLate;
@@ -184,7 +180,7 @@ inline void list_ring_host(const uint64_t* events, int64_t n, int64_t j0, int32_
                            const Window& w, int32_t K, int32_t layout, int32_t* image, int64_t* outside,
                            uint64_t* words, int64_t* stamps, int64_t* dropped) {
     for (int64_t p = 0; p < n; ++p) {
-        const fit::Stamp st = fit::decode(events[p], j0);
+        const pkt::Stamp st = pkt::decode(events[p], j0);
         const int64_t k = ring_cell(st, C, N, (int64_t)fs, w);
         if (k < 0) {
             ++outside[-1 - k];
@@ -236,7 +232,7 @@ inline void fill_ring_host(const uint64_t* events, const float* heights, const f
                            const int32_t* image, const int64_t* stamps, float* row_height, float* row_dt,
                            int64_t* fill) {
     for (int64_t p = 0; p < n; ++p) {
-        const fit::Stamp st = fit::decode(events[p], j0);
+        const pkt::Stamp st = pkt::decode(events[p], j0);
         if (st.ch >= C || deferred(heights[p], st.jg, j_defer)) continue;
         const int64_t k = ring_cell(st, C, N, (int64_t)fs, w);
         const int64_t at = k < 0 ? -1 : find_stamp(stamps + k * K, row_fill(image[k], K), st.jg);

@@ -296,7 +296,7 @@ struct CubeRule {
 // Where packet (word, h) is counted: ch (nb + 3) + column, or -1 for a packet that touches no cell
 // (ch >= C, or deferred); *e_out = its energy and *pixel = (ch < C).
 WCAL_HD int64_t cube_cell(uint64_t word, float h, const float* cal_f, const CubeRule& r, float* e_out, bool* pixel) {
-    const fit::Stamp st = fit::decode(word, r.j0);
+    const pkt::Stamp st = pkt::decode(word, r.j0);
     *pixel = st.ch < r.C;
     if (!*pixel) return -1;
     const float e = energy(h, cal_f + (int64_t)st.ch * 4);

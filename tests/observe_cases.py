@@ -26,7 +26,7 @@ def pack(ch, jg, rng=None):
 
 
 def decode(ev, j0):
-    """(ch, jg) as fit::decode: base = max(j0 - 2^27, 0), jg = base + ((ts - base) mod 2^28)."""
+    """(ch, jg) as pkt::decode: base = max(j0 - 2^27, 0), jg = base + ((ts - base) mod 2^28)."""
     ev = np.asarray(ev, np.uint64)
     ch = ((ev >> np.uint64(52)) & np.uint64(0xFFF)).astype(np.int64)
     ts = (ev & np.uint64(TS_MASK)).astype(np.int64)

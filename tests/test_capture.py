@@ -281,6 +281,31 @@ def test_capture_unwrap(gpu, j0):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize('count', [-1, 0])
+def test_capture_counted_none(gpu, count):
+    """A device-side count of 0, or below it, reads no packet: bank, stamps and info are those of
+    the call with n = 0 on the same rows."""
+    import torch
+    d = _one_call()
+    (phase, j0, ev), = _ref_run(d)[1]
+    ch = _channelizer(d)
+    try:
+        d_ph = torch.from_numpy(phase).cuda()
+        d_ev = torch.from_numpy(ev.view(np.int64)).cuda()
+        d_count = torch.tensor([count], dtype=torch.int64, device='cuda')
+        none, got = ch.capture_bank(), ch.capture_bank()
+        torch.cuda.synchronize()
+        ch.capture_pulses_device(d_ph, phase.shape[0], j0, d_ev, 0, *none)
+        ch.capture_pulses_counted(d_ph, phase.shape[0], j0, d_ev, d_count, len(ev), *got)   # j0 again: a new segment
+        torch.cuda.synchronize()
+        none, got = _host(none), _host(got)
+    finally:
+        ch.close()
+    assert len(ev) > 100 and not none[2].any()
+    assert all(np.array_equal(a.view(np.uint32), b.view(np.uint32)) for a, b in zip(none, got))
+
+
+@pytest.mark.gpu
 def test_capture_segment_break_and_reset(gpu):
     """A call whose j0 skips ahead, and reset_stream, forget the carried rows and the pending
     packets and keep the bank; info handed in by the caller continues a bank."""

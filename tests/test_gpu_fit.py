@@ -199,7 +199,7 @@ def test_fit_independence(ctx):
 
 
 def test_fit_counted(ctx):
-    """The counted form processes min(*d_count, cap) packets and leaves the other outputs alone."""
+    """The counted form processes min(max(*d_count, 0), cap) packets and leaves the other outputs alone."""
     import torch
     phase, coeff, ev, ts = _stream(seed=5, n=600)
     d_phase, d_ev = _dev(phase), _dev(ev)
@@ -207,14 +207,14 @@ def test_fit_counted(ctx):
     ctx.set_pulse_fit(LS, SS)
     whole = _one_call(ctx, d_phase, 1200, 0, ev)
     cap = 400
-    for count in (250, 400, 600):
+    for count in (-1, 0, 250, 400, 600):
         d_count = torch.tensor([count], dtype=torch.int64, device='cuda')
         outs = _outputs(len(ev), fill=-7)
         torch.cuda.synchronize()
         ctx.set_pulse_fit(LS, SS)
         ctx.pulse_fit_counted(d_phase, 1200, 0, d_ev, d_count, cap, *outs)
         got = _host(outs)
-        m = min(count, cap)
+        m = min(max(count, 0), cap)
         assert _same([w[:m] for w in whole], [g[:m] for g in got])
         assert all(np.all(g[m:] == -7) for g in got)
 

@@ -16,7 +16,7 @@ from mkids_sdr_amd import _lib, observe, packets
 
 pytestmark = pytest.mark.gpu
 C = 64
-SLICE, MAX_BLOCKS = 2048, 1024      # csrc/mkid_internal.h kObsSlice, kObsMaxBlocks
+SLICE, MAX_BLOCKS = 2048, 1024      # csrc/pkt_common.h kObsSlice, kObsMaxBlocks
 
 
 @pytest.fixture(scope='module')

@@ -16,7 +16,7 @@ from mkids_sdr_amd import _lib, observe, packets
 pytestmark = pytest.mark.gpu
 C = 64
 N = 2 * C
-SLICE = 2048                        # csrc/mkid_internal.h kObsSlice
+SLICE = 2048                        # csrc/pkt_common.h kObsSlice
 FIELDS = ('image', 'outside', 'words', 'stamps', 'dropped', 'height', 'dt', 'fill')
 
 

@@ -58,6 +58,58 @@ def _check(phase, ev, coeff, pre, j0, got):
     assert np.all(np.abs(got[ok] - ref[ok]) <= 1e-5 * scale + 1e-6)
 
 
+@pytest.fixture(scope='module')
+def small_ctx(gpu):
+    from mkids_sdr_amd.channelizer import Channelizer
+    ch = Channelizer(64, max_chunk=2 ** 14)
+    yield ch
+    ch.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('nco', [20, 70])
+@pytest.mark.parametrize('j0', [0, 1000, (1 << 28) - 7, 3 << 28])
+def test_heights_unwrap_and_counts_on_device(small_ctx, j0, nco):
+    """The stamps of test_oracle_heights_match_loop through the device's unwrap at every j0, with
+    one tap per lane and with two (nco = 70), in the smallest context there is (64 channels); a
+    packet of a channel the context does not have comes back NaN. Then the counted form at device
+    counts below, at and above 0 .. n: the first min(max(count, 0), n) heights are the uncounted
+    call's bits and the rest of the output is not written."""
+    import torch
+    ch, C, rows, pre = small_ctx, 64, 300, 6
+    rng = np.random.default_rng(5)
+    phase = rng.normal(size=(rows, C)).astype(np.float32)
+    coeff = rng.normal(size=(C, nco)).astype(np.float32)
+    ts = j0 + np.array([0, 5, 6, 50, 200, 273, 274, 299, 320])
+    ev = np.array([_pack(c, t) for c, t in zip(rng.integers(0, C, ts.size), ts)] + [_pack(C, j0 + 100)], np.uint64)
+    n = len(ev)
+    ch.set_pulse_filter(coeff, pre=pre)
+    d_ph = torch.from_numpy(phase).cuda()
+    d_ev = torch.from_numpy(ev.view(np.int64)).cuda()
+    d_h = torch.full((n,), -7.0, dtype=torch.float32, device='cuda')
+    torch.cuda.synchronize()
+    ch.pulse_heights_device(d_ph, rows, j0, d_ev, n, d_h)
+    torch.cuda.synchronize()
+    got = d_h.cpu().numpy()
+    assert np.isnan(got[9])
+    ref = oh.pulse_heights(phase, ev[:9], coeff.astype(np.float64), pre, j0)
+    assert np.array_equal(np.isnan(ref), np.isnan(got[:9]))
+    ok = ~np.isnan(ref)
+    assert (~ok).sum() == (4 if nco == 20 else 6)   # windows before row 0 (ts 0, 5) or past the last row
+    chs = (ev[:9][ok] >> np.uint64(52)).astype(np.int64)
+    scale = np.abs(coeff[chs].astype(np.float64)).sum(axis=1) * np.abs(phase).max()
+    assert np.all(np.abs(got[:9][ok] - ref[ok]) <= 1e-5 * scale + 1e-6)      # _check's bar
+    for count in (-1, 0, 3, n, n + 5):
+        d_count = torch.tensor([count], dtype=torch.int64, device='cuda')
+        d_c = torch.full((n,), -7.0, dtype=torch.float32, device='cuda')
+        torch.cuda.synchronize()
+        ch.pulse_heights_counted(d_ph, rows, j0, d_ev, d_count, n, d_c)
+        torch.cuda.synchronize()
+        m = min(max(count, 0), n)
+        c = d_c.cpu().numpy()
+        assert np.array_equal(c[:m].view(np.uint32), got[:m].view(np.uint32)) and np.all(c[m:] == -7.0)
+
+
 def _noise_iq(S, seed):
     """Random int16 I/Q: the chain turns it into noise-like phase that crosses the thresholds
     often, which is all the pulse-height check needs (it runs on the device's own phase and

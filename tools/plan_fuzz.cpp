@@ -5,10 +5,11 @@
 // buffers of exactly the planned size, so an undersized plan is an ASan heap overflow, not a
 // silent miscount (the ADVICE r02 scratch-sizing bug is that class).
 // fuzz_observe, fuzz_photons and fuzz_pack drive the observing rules and the host twins' loops
-// (csrc/obs_common.h) likewise, fuzz_wavecal those of the laser-line calibration and the energy cube
-// (csrc/wavecal_common.h), fuzz_loopfit the resonator loop fits (csrc/loopfit_common.h), fuzz_magfit the
-// resonator magnitude fits (csrc/magfit_common.h), fuzz_welch the
-// Welch transforms' index maps and the IQ noise analysis (csrc/welch_common.h).
+// (csrc/obs_common.h) likewise, fuzz_pkt the packet list's host side (csrc/pkt_common.h),
+// fuzz_wavecal those of the laser-line calibration and the energy cube (csrc/wavecal_common.h),
+// fuzz_loopfit the resonator loop fits (csrc/loopfit_common.h), fuzz_magfit the resonator magnitude
+// fits (csrc/magfit_common.h), fuzz_welch the Welch transforms' index maps and the IQ noise analysis
+// (csrc/welch_common.h).
 //   plan_fuzz [iterations] [seed]
 #include <stdint.h>
 #include <stdio.h>
@@ -25,6 +26,7 @@
 #include "magfit_common.h"
 #include "mkid_plan.h"
 #include "obs_common.h"
+#include "pkt_common.h"
 #include "wavecal_common.h"
 #include "welch_common.h"
 
@@ -306,6 +308,47 @@ static void fuzz_merge_pack(int iters) {
             for (size_t i = 0; i < m.size(); ++i)
                 CHECK((out[i] >> 56) == (m[i] >> MKID_PKT_CH_SHIFT) && (out[i] & 0xFFFFF) == (m[i] & 0xFFFFF),
                       "packed fields");
+    }
+}
+
+// The packet list's host side (pkt_common.h): the valid count, the slices and their bounds (disjoint,
+// in order, covering exactly the first `valid` packets, at most kObsMaxBlocks of them), the grid of a
+// grid-stride pass, and the run ends' deltas, which must add up to every run's length.
+static void fuzz_pkt(int iters) {
+    using namespace mkid::pkt;
+    for (int it = 0; it < iters; ++it) {
+        const int64_t n = rint_(0, 3) == 0 ? rint_(0, 600) : rint_(0, (int64_t)1 << rint_(10, 33));
+        const int64_t dn = rint_(0, 2) == 0 ? rint_(-5, 5) : rint_(-n - 5, n + 5);
+        const int64_t valid = count(&dn, n);
+        CHECK(count(nullptr, n) == n && valid == std::min(std::max<int64_t>(dn, 0), n), "count %lld of %lld",
+              (long long)dn, (long long)n);
+        const int32_t threads = (int32_t)(64 * rint_(1, 16));
+        const Slices p = slices(n, threads);
+        CHECK(p.blocks >= 1 && p.blocks <= mkid::kObsMaxBlocks && p.slice % threads == 0 && p.blocks * p.slice >= n &&
+                  (p.blocks == mkid::kObsMaxBlocks || p.slice <= mkid::kObsSlice + threads),
+              "slices of %lld: %d x %lld", (long long)n, p.blocks, (long long)p.slice);
+        int64_t at = 0;
+        for (int32_t b = 0; b < p.blocks; ++b) {
+            int64_t b0, b1;
+            bounds(b, p.slice, valid, b0, b1);
+            if (b0 >= b1) continue;   // the count ended before this slice
+            CHECK(b0 == at && b1 <= valid, "slice %d of %lld: [%lld, %lld)", b, (long long)valid, (long long)b0, (long long)b1);
+            at = b1;
+        }
+        CHECK(at == valid, "the slices cover %lld of %lld", (long long)at, (long long)valid);
+        const int32_t ncu = (int32_t)rint_(-1, 400), per = (int32_t)rint_(1, 32);
+        const int64_t g = grid_stride_blocks(n, threads, ncu, per);
+        CHECK(g >= 0 && g <= (int64_t)(ncu > 0 ? ncu : 256) * per && g * threads < n + threads && (g > 0) == (n > 0),
+              "grid %lld for %lld", (long long)g, (long long)n);
+        uint64_t sum = 0;   // runs of random length from a random start
+        int64_t i = rint_(0, (int64_t)1 << 40), runs = rint_(1, 20), total = 0;
+        for (int64_t r = 0; r < runs; ++r) {
+            const int64_t len = rint_(1, 5);
+            for (int64_t k = 0; k < len; ++k, ++i)
+                if (k == 0 || k == len - 1) sum += run_delta(i, k == 0, k == len - 1);
+            total += len;
+        }
+        CHECK(sum == (uint64_t)total, "run deltas add up to %llu of %lld", (unsigned long long)sum, (long long)total);
     }
 }
 
@@ -642,7 +685,7 @@ static void fuzz_fit(int iters) {
     for (int it = 0; it < iters; ++it)
         check_fit((int32_t)(rint_(0, 1) ? rint_(1, 300) : rint_(1, mkid::fit::kMaxCoeff)), (int32_t)rint_(0, mkid::fit::kMaxSearch),
                   (int)rint_(1, 512));
-    mkid::fit::Stamp st = mkid::fit::decode(((uint64_t)5 << MKID_PKT_CH_SHIFT) | 3, ((int64_t)1 << 28) + 1);
+    mkid::pkt::Stamp st = mkid::pkt::decode(((uint64_t)5 << MKID_PKT_CH_SHIFT) | 3, ((int64_t)1 << 28) + 1);
     CHECK(st.ch == 5 && st.jg == ((int64_t)1 << 28) + 3, "decode: channel %d stamp %lld", st.ch, (long long)st.jg);
     CHECK(mkid::fit::inside(0, 1, -3, 3, 10, 6, 10) && !mkid::fit::inside(0, 1, -4, 3, 10, 6, 10) &&
               !mkid::fit::inside(0, 1, -2, 3, 10, 6, 10) && !mkid::fit::inside(1, 1, -3, 3, 10, 6, 10),
@@ -702,7 +745,7 @@ static void fuzz_observe(int iters) {
             const uint64_t w = ev[(size_t)p];
             const int64_t ch = (int64_t)(w >> 52), ts = (int64_t)(w & 0xFFFFFFF);
             const int64_t jg = base + (((ts - base) % (1 << 28)) + (1 << 28)) % (1 << 28);
-            const mkid::fit::Stamp st = mkid::fit::decode(w, j0);
+            const mkid::pkt::Stamp st = mkid::pkt::decode(w, j0);
             CHECK(st.ch == ch && st.jg == jg, "decode");
             if (ch >= C) {
                 ++ref_outside[0];
@@ -805,7 +848,7 @@ static void fuzz_photons(int iters) {
         for (int64_t p = 0; p < n; ++p) {
             const uint64_t w = ev[(size_t)p];
             const int64_t ch = (int64_t)(w >> 52), jg = jgs[(size_t)p];
-            CHECK(mkid::fit::decode(w, j0c).jg == jg, "decode near the wrap");
+            CHECK(mkid::pkt::decode(w, j0c).jg == jg, "decode near the wrap");
             if (ch >= C) {
                 ++ref_outside[0];
                 continue;
@@ -1539,6 +1582,7 @@ int main(int argc, char** argv) {
     fuzz_slot_order(iters / 10 + 2);
     fuzz_quantize(iters / 3 + 1);
     fuzz_merge_pack(iters);
+    fuzz_pkt(iters);
     fuzz_carry(iters);
     fuzz_bank(iters);
     fuzz_thresholds(iters / 2 + 1);
