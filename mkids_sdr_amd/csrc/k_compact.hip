@@ -1,5 +1,6 @@
 // Packet compaction (exclusive scan over (channel, segment) counts) and stream-history rolls.
 #include "mkid_internal.h"
+#include "wg_common.h"
 
 namespace mkid {
 
@@ -10,9 +11,9 @@ namespace mkid {
 // history rolls as extra blocks (round 6: one launch fewer per call). Round 6 also: one entry per
 // thread (with 8 the copy ran eight dependent load -> store chains in a row per thread:
 // k_gather_events 16.7 -> 8.2 us per step at config 3, 13.3 -> 5.3 us at config 2); the block
-// scans are wave scans plus one exchange of wave totals (k_tile_scan 7.8 -> 4.8 us); the tile scan
-// folded into (1) as a last-block pass was slower (1024 blocks serialise on the done counter:
-// k_tile_sums 4.9 -> 27 us).
+// scans are wg_common.h's (k_tile_scan 7.8 -> 4.8 us; the round-5 Hillis-Steele form over LDS took
+// 2 log2(NT) barriers); the tile scan folded into (1) as a last-block pass was slower (1024 blocks
+// serialise on the done counter: k_tile_sums 4.9 -> 27 us).
 constexpr int kCmpThreads = 256;
 constexpr int kCmpEpt = 1;                       // entries per thread
 constexpr int kCmpTile = kCmpThreads * kCmpEpt;  // entries per tile
@@ -32,38 +33,17 @@ __device__ __forceinline__ void load_counts(const int32_t* counts, int64_t n_ent
     }
 }
 
-// inclusive scan over the 64 lanes of a wave (6 shuffle steps, no barrier)
-__device__ __forceinline__ int64_t wave_incl_scan(int64_t x) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int64_t y = __shfl_up(x, off, 64);
-        x += lane >= off ? y : 0;
-    }
-    return x;
-}
-
-// block-wide exclusive scan of one int64 per thread (NT threads), returns the block total: wave
-// scans, then every thread adds the totals of the waves before it (two barriers; the round-5
-// Hillis-Steele form over LDS took 2 log2(NT) barriers)
+// block-wide exclusive scan of one int64 per thread (NT threads), returns the block total: wave scan, fold
+// and a second barrier, since every caller scans again through the same ws
 template <int NT>
 __device__ __forceinline__ int64_t block_excl_scan(int64_t x, int64_t& excl) {
-    constexpr int NW = NT / 64;
-    __shared__ int64_t ws[NW];
-    const int w = threadIdx.x >> 6;
-    const int64_t inc = wave_incl_scan(x);
-    if ((threadIdx.x & 63) == 63) ws[w] = inc;
-    __syncthreads();
-    int64_t base = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < NW; ++i) {
-        const int64_t v = ws[i];
-        base += i < w ? v : 0;
-        tot += v;
-    }
-    excl = base + inc - x;
+    __shared__ int64_t ws[NT / 64];
+    int64_t before, total;
+    const int64_t inc = wg::wave_scan(x, (int64_t)0, wg::Add{});
+    wg::fold_waves((threadIdx.x & 63) == 63, inc, ws, NT / 64, (int64_t)0, wg::Add{}, before, total);
+    excl = before + inc - x;
     __syncthreads();   // ws is reused by the next scan
-    return tot;
+    return total;
 }
 
 __global__ __launch_bounds__(kCmpThreads) void k_tile_sums(const int32_t* counts, int64_t n_ent,

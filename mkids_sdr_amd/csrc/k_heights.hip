@@ -4,13 +4,14 @@
 // Float32Col(100)); mkid_optimal_filter fills the stub and this kernel applies a per-channel
 // filter of that form to the phase stream at every photon packet:
 //     h_p = sum_{i < ncoeff} coeff[ch_p][i] * phase[ts_p - pre + i][ch_p]
-// One wave per packet: lane l accumulates taps l, l + 64, ... in fp32, then a fixed-order xor
-// butterfly over the wave (deterministic). The phase rows of one packet's window are strided by
+// One wave per packet: lane l accumulates taps l, l + 64, ... in fp32, then wg::wave_reduce's
+// fixed-order butterfly (deterministic). The phase rows of one packet's window are strided by
 // C floats, so each lane's read is its own cache line; the volume is small (ncoeff x 4 B per
 // packet). Windows that start before the call's first row read the context's carried history of
 // the previous call's last rows (mkid_calib.hip pulse_heights), so a streamed run loses heights
 // only at the stream start and for windows past the call's last row.
 #include "mkid_internal.h"
+#include "wg_common.h"
 
 namespace mkid {
 
@@ -35,8 +36,7 @@ __global__ __launch_bounds__(64 * kHeightWaves) void k_pulse_heights(HeightArgs 
                 acc = fmaf(cf[i], v, acc);
             }
         }
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
+        acc = wg::wave_reduce(acc, wg::Add{});   // the order that gives the height its bits
         if (lane == 0) a.heights[p] = inside ? acc : __builtin_nanf("");
     }
 }

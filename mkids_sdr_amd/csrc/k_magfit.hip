@@ -7,10 +7,10 @@
 //            sweep is staged in afterwards.
 //   Data:    thread t takes points t, t + T, ..: x and the magnitude go to LDS (2 x 8 KiB at 1024
 //            points), a value that is not finite raises a flag in LDS, and the largest magnitude is
-//            reduced by __shfl_xor in the wave and through LDS across waves (magnitudes are >= 0 or
-//            NaN and a NaN never wins, so the maximum of the others in any order is the serial scan's
-//            from mag[0], unless mag[0] itself is NaN, which is then the result as it is there). Each
-//            thread then divides its own points by norm. Thread 0 makes the bounds and the start's f0.
+//            wg::reduce's from 0 (magnitudes are >= 0 or NaN and a NaN never wins, so the maximum of the
+//            others in any order is the serial scan's from mag[0], unless mag[0] itself is NaN, which is
+//            then the result as it is there). Each thread then divides its own points by norm. Thread 0
+//            makes the bounds and the start's f0.
 //   Starts:  wave w takes starts w, w + W, .. one at a time. In an evaluation lane l takes points l,
 //            l + 64, .. and keeps the 21 + 6 + 1 float64 partial sums in registers; the lanes combine
 //            by __shfl_xor, m = 32 .. 1, so that every lane ends with the same bits. Lane 0 runs the
@@ -32,6 +32,7 @@
 
 #include "magfit_common.h"
 #include "mkid_internal.h"
+#include "wg_common.h"
 
 namespace mkid {
 
@@ -67,16 +68,8 @@ __global__ __launch_bounds__(kMfitMaxThreads) void k_magfit(MagfitArgs a) {
         s_x[i] = x, s_y[i] = mag;
         mx = mag > mx ? mag : mx;
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const double v = __shfl_xor(mx, m, 64);
-        mx = v > mx ? v : mx;
-    }
-    if (lane == 0) s_wmax[wv] = mx;
-    if (bad) s_bad = 1;   // every writer stores the same value
-    __syncthreads();
-    double norm = s_wmax[0];
-    for (int i = 1; i < W; ++i) norm = s_wmax[i] > norm ? s_wmax[i] : norm;
+    if (bad) s_bad = 1;   // every writer stores the same value; wg::reduce has the barrier
+    double norm = wg::reduce(mx, s_wmax, W, 0.0, wg::Max{});
     const double mag0 = s_y[0];
     if (mag0 != mag0) norm = mag0;
     const bool nonfinite = s_bad != 0;

@@ -25,6 +25,7 @@
 // Integer adds commute: image and spectra are the same bits from run to run.
 #include "mkid_internal.h"
 #include "obs_common.h"
+#include "wg_common.h"
 
 namespace mkid {
 
@@ -110,22 +111,11 @@ __global__ __launch_bounds__(kObsThreads) void k_obs_spectra(ObsSpectraArgs a) {
 __global__ __launch_bounds__(kObsMaxBlocks) void k_obs_scan(const int32_t* wg_count, int32_t blocks, int64_t* wg_off,
                                                             int64_t cap_def, int64_t* ndef) {
     __shared__ int64_t wsum[kObsMaxBlocks / 64];
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int t = threadIdx.x;
     const int64_t x = t < blocks ? wg_count[t] : 0;
-    int64_t inc = x;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int64_t y = __shfl_up(inc, off, 64);
-        inc += lane >= off ? y : 0;
-    }
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    int64_t before = 0, total = 0;
-    for (int i = 0; i < kObsMaxBlocks / 64; ++i) {
-        const int64_t v = wsum[i];
-        before += i < w ? v : 0;
-        total += v;
-    }
+    int64_t before, total;
+    const int64_t inc = wg::wave_scan(x, (int64_t)0, wg::Add{});
+    wg::fold_waves((t & 63) == 63, inc, wsum, kObsMaxBlocks / 64, (int64_t)0, wg::Add{}, before, total);
     const int64_t base = ndef[1];
     __syncthreads();   // every thread has read ndef[1] before thread 0 replaces it
     if (t < blocks) wg_off[t] = base + before + inc - x;
@@ -142,7 +132,6 @@ __global__ __launch_bounds__(kObsThreads) void k_obs_scatter(ObsSpectraArgs a) {
     const int64_t n = pkt::count(a.d_n, a.n);
     int64_t b0, b1;
     pkt::bounds(blockIdx.x, a.slice, n, b0, b1);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     int64_t o = a.wg_off[blockIdx.x];
     for (int64_t t0 = b0; t0 < b1; t0 += kObsThreads) {   // workgroup-uniform trip count
         const int64_t i = t0 + threadIdx.x;
@@ -153,17 +142,11 @@ __global__ __launch_bounds__(kObsThreads) void k_obs_scatter(ObsSpectraArgs a) {
             const pkt::Stamp st = pkt::decode(word, a.j0);
             q = st.ch < a.C && obs::deferred(a.heights[i], st.jg, a.j_defer);
         }
-        const uint64_t m = __ballot(q);
-        if (lane == 0) wtot[w] = __popcll(m);
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int k = 0; k < kObsThreads / 64; ++k) {
-            const int v = wtot[k];
-            before += k < w ? v : 0;
-            total += v;
-        }
-        const int64_t pos = o + before + __popcll(m & (((uint64_t)1 << lane) - 1));
+        const wg::Rank r = wg::wave_rank(q);   // then the rank in the workgroup: the waves' counts folded
+        int before, total;
+        wg::fold_waves((threadIdx.x & 63) == 0, r.count, wtot, kObsThreads / 64, 0, wg::Add{}, before,
+                       total);
+        const int64_t pos = o + before + r.below;
         if (q && pos >= 0 && pos < a.cap_def) a.deferred[pos] = word;
         o += total;
         __syncthreads();   // wtot is rewritten by the next tile

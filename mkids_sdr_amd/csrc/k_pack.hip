@@ -5,8 +5,7 @@
 // and row c holds m_c = row_fill(image[row0 + c], K) photons. The order between the steps comes
 // from the kernel boundaries alone:
 // k_pk_scan   one workgroup: counts[c] = the raw count, offsets = the exclusive prefix sum of m_c
-//             (kPackPer consecutive channels a thread, per wave by shuffles, across the waves
-//             through LDS; the k_obs_scan pattern), and thread 0 writes offsets[C] and total.
+//             (kPackPer consecutive channels a thread, wg::wave_scan, the fold here); thread 0: offsets[C], total.
 // k_pk_copy   a wave per (channel, tile of kPackTile slots), a wave whose tile starts at or past
 //             m_c leaving at once, so that one long row is spread over many waves and many short
 //             rows cost a wave each. The lanes walk consecutive slots: the loads from the row and
@@ -18,6 +17,7 @@
 // No atomics, no scratch, nothing read back by the host.
 #include "mkid_internal.h"
 #include "obs_common.h"
+#include "wg_common.h"
 
 namespace mkid {
 
@@ -40,13 +40,8 @@ __global__ __launch_bounds__(kPackScanThreads) void k_pk_scan(PackArgs a) {
         }
         x += m[j];
     }
-    int64_t inc = x;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int64_t y = __shfl_up(inc, off, 64);
-        inc += lane >= off ? y : 0;
-    }
-    if (lane == 63) wsum[w] = inc;
+    const int64_t inc = wg::wave_scan(x, (int64_t)0, wg::Add{});
+    if (lane == 63) wsum[w] = inc;   // wg::fold_waves' text: through it the kernel takes 62 VGPRs for 50
     __syncthreads();
     int64_t before = 0, total = 0;
     for (int i = 0; i < kPackScanThreads / 64; ++i) {

@@ -8,10 +8,9 @@
 //               smoothing sum (ds_read_b32, conflict-free), and s is recomputed from the row each
 //               time: an int64 table of s beside the row would be 192 KiB, more than a CU has.
 //               Selection: P rounds; in a round every thread takes the largest key (s 2^15 + 32767 -
-//               b, wavecal_common.h candidate_key) of its candidates that no chosen line excludes,
-//               the wave reduces by __shfl_xor, the four wave maxima meet in LDS, and every thread
-//               takes their maximum, so the round's end is workgroup-uniform; no atomics. Thread p <
-//               found then fits line p (one lane per line: the float64 sums in ascending bin order),
+//               b, wavecal_common.h candidate_key) of its candidates that no chosen line excludes, and
+//               wg::reduce gives every thread their maximum, so the round's end is workgroup-uniform;
+//               no atomics. Thread p < found then fits line p (one lane per line: float64 sums by ascending bin),
 //               thread 0 makes the calibration from the fits in LDS, threads p < P store the lines.
 // k_wcal_cube   grid-stride over the packets as k_obs_count: thread i computes the cell of packet i
 //               and of both neighbours; the first packet of a run of equal cells adds -i and the
@@ -24,6 +23,7 @@
 
 #include "mkid_internal.h"
 #include "wavecal_common.h"
+#include "wg_common.h"
 
 namespace mkid {
 
@@ -32,9 +32,9 @@ constexpr int kWcalWaves = kWcalThreads / 64;
 
 __global__ __launch_bounds__(kWcalThreads) void k_wcal_lines(WcalLinesArgs a) {
     extern __shared__ int32_t wcal_row[];
-    __shared__ uint64_t wmax[kWcalWaves];
+    __shared__ unsigned long long wmax[kWcalWaves];   // the type the shuffles take
     __shared__ mkid_line_fit s_fit[wcal::kMaxLines];
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int t = threadIdx.x;
     const int64_t ch = blockIdx.x;
     const int32_t nbins = a.nbins;
     const int32_t* src = a.spectra + ch * (nbins + obs::kExtraCols) + 1;
@@ -43,22 +43,13 @@ __global__ __launch_bounds__(kWcalThreads) void k_wcal_lines(WcalLinesArgs a) {
     int32_t chosen[wcal::kMaxLines] = {0, 0, 0};
     int32_t found = 0;
     for (int32_t r = 0; r < a.P; ++r) {   // workgroup-uniform trip count
-        uint64_t best = 0;
+        unsigned long long best = 0;
         for (int32_t b = t; b < nbins; b += kWcalThreads) {
             if (wcal::excluded(b, chosen, r, a.min_sep)) continue;
             const uint64_t k = wcal::candidate_key(wcal_row, nbins, a.w, a.min_peak, b);
             best = k > best ? k : best;
         }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const uint64_t o = __shfl_xor((unsigned long long)best, off, 64);
-            best = o > best ? o : best;
-        }
-        if (lane == 0) wmax[wv] = best;
-        __syncthreads();
-        uint64_t top = 0;
-#pragma unroll
-        for (int i = 0; i < kWcalWaves; ++i) top = wmax[i] > top ? wmax[i] : top;
+        const unsigned long long top = wg::reduce(best, wmax, kWcalWaves, 0ull, wg::Max{});
         __syncthreads();   // wmax is rewritten by the next round
         if (!top) break;   // every thread holds the same maximum
         chosen[found++] = wcal::key_bin(top);

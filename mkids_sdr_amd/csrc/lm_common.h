@@ -252,7 +252,8 @@ inline int32_t run_starts_host(int32_t status, int32_t S, int32_t max_iter, doub
 // differently, and k_loopfit 0.6 % slower (profiles/lmsolver/).
 #if defined(__HIPCC__)
 // The combined sums of a wave: partial(p, &sums) is the lane's share, then the butterfly: the lanes
-// combine by __shfl_xor, m = 32 .. 1, and every lane ends with the same bits.
+// combine by __shfl_xor, m = 32 .. 1, and every lane ends with the same bits. It is the contract of
+// wg_common.h's wave_reduce, written out here: through it k_loopfit's instruction stream changes.
 template <int32_t N, class Partial>
 struct WaveEval {
     Partial partial;
